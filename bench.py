@@ -11,8 +11,11 @@
                                            ranks (vimure_amd.batch.fit_datasets(dist=...)); metric = fits/s
   Both refuse (exit code 2) on a node with fewer GPUs than asked for.
 
-The timed block of K steps is repeated REPEATS times inside the run; `value` is the median block (min / max in
-`timing_blocks`).  After the timed region, under a time budget, the default run adds two blocks measured on the same GPU:
+The timed region is exactly K steps, one block unless --repeats splits it into consecutive blocks (each block ends in a
+synchronize: their spread in `timing_blocks`); `value` is K over the summed time of the blocks.  Before the warm-up,
+--settle-sweeps untimed sweeps bring the GPU to its steady pace and the initial state is set again.  `--dump-outputs DIR`
+writes what the timed steps computed to DIR/*.npy.  After the timed region, under a time budget, the default run adds two
+blocks measured on the same GPU:
 `c5_layer` (one layer of configs[4] at its stated size: ms per sweep, per-kernel rates) and `small_fits` (the configs[3]
 workload of tools/bench_batch.py: fits/s from ONE process).
 
@@ -73,10 +76,18 @@ def draw_state(cfg, seed, sum_x, coverage):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=40)
+    ap.add_argument("--steps", type=int, default=40, help="timed sweeps, in all")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS) + ["c4", "c5"])
-    ap.add_argument("--repeats", type=int, default=5, help="timed blocks of --steps sweeps; value = the median block")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="the --steps timed sweeps are timed in this many consecutive blocks (their spread: timing_blocks; every "
+                         "block adds a synchronize); value = --steps over the summed time of the blocks")
+    ap.add_argument("--settle-sweeps", type=int, default=300,
+                    help="untimed sweeps from the initial state before the warm-up, after which the state is set back to it: the "
+                         "GPU reaches its steady pace (about 100 sweeps at config 3) without changing what the timed steps compute")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed sweeps, write what they computed (the posteriors get_state hands a caller; rho as a fixed "
+                         "seeded sample of its ties) and the last ELBO to DIR/<name>.npy, float64")
     ap.add_argument("--no-kernel-events", action="store_true", help="diagnostic: no HIP events around the kernels in the timed region (roofline then has no live launch time)")
     ap.add_argument("--no-extra", action="store_true", help="skip the c5_layer / small_fits blocks after the timed region")
     ap.add_argument("--extra-seconds", type=float, default=150.0, help="time budget of the extra blocks")
@@ -89,6 +100,10 @@ def main():
                     help="engine data layout (VMR_FORMAT): report lists unless X is dense; 'dense' forces the tile path")
     ap.add_argument("--no-converge", action="store_true", help="skip the time-to-ELBO-converge fit")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.config in ("c4", "c5"):
+        ap.error("--dump-outputs: the single-fit configurations only (" + ", ".join(sorted(CONFIGS)) + ")")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # plain `python bench.py --gpus N`: start the N ranks ourselves (fresh child processes under
@@ -170,27 +185,34 @@ def main():
                 it = nxt
         return last
 
+    if args.settle_sweeps > 0:
+        run(1, args.settle_sweeps)
+        eng.sync()
+        eng.set_state(host.gamma_shp, host.gamma_rte, host.phi_shp, host.phi_rte, host.nu_shp, host.nu_rte, pr)
     run(1, args.warmup)
     eng.sync()
     if not args.no_kernel_events:
         eng.profile(2)   # events around the passes over the data only (the roofline kernels), not the finalize kernels
+    # EXACTLY --steps timed sweeps in all, in consecutive blocks whose sizes differ by at most one
+    nblk = max(1, min(args.repeats, args.steps))
+    sizes = [args.steps // nblk + (1 if b < args.steps % nblk else 0) for b in range(nblk)]
     blocks = []
     elbo = None
     it0 = args.warmup + 1
-    for _ in range(max(1, args.repeats)):   # every block: barrier + synchronize, EXACTLY --steps sweeps, synchronize + barrier
+    for n in sizes:   # every block: barrier + synchronize, its sweeps, synchronize + barrier
         if dist is not None:
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        e_ = run(it0, args.steps)
+        e_ = run(it0, n)
         eng.sync()
         torch.cuda.synchronize()
         if dist is not None:
             dist.barrier()
         blocks.append(time.perf_counter() - t0)
         elbo = e_ if e_ is not None else elbo
-        it0 += args.steps
-    own_ms = 1e3 * float(np.median(blocks)) / args.steps   # this rank's own pace, before the MAX over ranks
+        it0 += n
+    own_ms = 1e3 * sum(blocks) / args.steps   # this rank's own pace, before the MAX over ranks
     per_rank_ms = [own_ms]
     if dist is not None:   # MAX over ranks, block by block
         tt = torch.tensor(blocks, dtype=torch.float64, device=cdev)
@@ -202,11 +224,13 @@ def main():
         if rank == 0 and max(per_rank_ms) > 1.10 * min(per_rank_ms):
             # independent fits of the same dataset (weak scaling): every rank should run at the single-GPU pace
             print(f"bench.py: WARNING ranks differ by more than 10 % in ms per sweep: {['%.4f' % v for v in per_rank_ms]}", file=sys.stderr, flush=True)
-    dt = float(np.median(blocks))
+    dt = sum(blocks)
     prof = eng.profile_read()
     eng.profile(False)
     if elbo is None:
         elbo = eng.elbo()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng.get_state(rho=True), elbo)
     if dist is not None:
         # the path's only exchange: gather the per-fit ELBOs (RCCL over xGMI)
         mine = torch.tensor([elbo], dtype=torch.float64, device=cdev)
@@ -233,7 +257,7 @@ def main():
             "metric": "CAVI iterations/sec (L=4 N=2000 M=200 K=2 synthetic, mutuality on)" if args.config == "c3"
                       else f"CAVI iterations/sec ({args.config})",
             "value": world * args.steps / dt, "unit": "iter/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True,
+            "warmup": args.warmup, "settle_sweeps": args.settle_sweeps, "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic" if not rehearse else "synthetic (REHEARSAL: ranks share a GPU, gloo)",
             "config": {"workload": f"BASELINE configs[2]: StandardSBM-style synthetic L={L} N={N} M={M} K={K}, "
                                    f"eta={cfg['eta']}, R dense all-ones, one seed-fit per GPU" if args.config == "c3"
@@ -256,8 +280,10 @@ def main():
                             "GBps": (v["bytes_per_launch"] / (v["ms"] / max(1, v["launches"]) * 1e-3) / 1e9)
                             if v["ms"] > 0 and v["bytes_per_launch"] > 0 else None} for k, v in prof.items()},
             "elbo": elbos, "gen_seconds": t_gen,
-            "timing_blocks": {"repeats": len(blocks), "steps_per_block": args.steps, "median_s": dt, "min_s": min(blocks),
-                              "max_s": max(blocks), "value_from": "median block"},
+            "timing_blocks": {"repeats": len(blocks), "steps_per_block": sizes, "total_s": dt,
+                              "min_ms_per_step": 1e3 * min(b / n for b, n in zip(blocks, sizes)),
+                              "max_ms_per_step": 1e3 * max(b / n for b, n in zip(blocks, sizes)),
+                              "value_from": "all --steps timed sweeps (the blocks' summed time)"},
             "per_rank_ms_per_step": per_rank_ms,   # each rank's own pace (weak scaling: every entry should equal the 1-GPU ms_per_step)
         }
         # whole-sweep view: SURVEY 8(d)'s canonical DENSE bytes per iteration (three passes over X,R + ELBO share)
@@ -298,6 +324,26 @@ def main():
     if dist is not None:
         dist.barrier()   # rank 0 may still be in its (untimed) convergence fit
         dist.destroy_process_group()
+
+
+DUMP_RHO_BYTES = 48 << 20   # --dump-outputs: rho beyond this is written as a fixed sample of its ties
+
+
+def dump_outputs(out_dir, st, elbo):
+    """What the timed sweeps computed, as a caller of the engine receives it (CaviEngine.get_state), to out_dir/<name>.npy in
+    float64: gamma / phi shape and rate, nu = [shape, rate], the ELBO the JSON line reports (the last one the timed sweeps
+    returned, else that of their final state), and rho [ties, K] at the ties listed (flat l, i, j index, ascending) in
+    rho_ties -- all of them when they fit DUMP_RHO_BYTES, else a sample drawn with a fixed seed, the same for the same shape."""
+    os.makedirs(out_dir, exist_ok=True)
+    rho = st["rho"]
+    K = rho.shape[-1]
+    rho = rho.reshape(-1, K)
+    n = min(len(rho), DUMP_RHO_BYTES // (8 * (K + 1)))
+    ties = np.arange(len(rho)) if n == len(rho) else np.sort(np.random.RandomState(0).choice(len(rho), n, replace=False))
+    arrays = {"gamma_shp": st["gamma_shp"], "gamma_rte": st["gamma_rte"], "phi_shp": st["phi_shp"], "phi_rte": st["phi_rte"],
+              "nu": [st["nu_shp"], st["nu_rte"]], "elbo": [elbo], "rho": rho[ties], "rho_ties": ties}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def c5_layer_block(device, N=8000, M=1000, K=3, sweeps=10):
