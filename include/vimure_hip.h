@@ -82,11 +82,15 @@ int vmr_create(vmr_handle* out, int device, int L, int N, int M, int K, int mutu
  * sptensor built by `read_from_edgelist` (_io.py:132-295) or `preprocess` (utils.py:220-248), and `R.subs` of a sparse
  * reporter mask; `__check_fit_params` derives `data_T_vals` from them with an O(nnz^2) lookup (model.py:148-161).  No dense
  * [L,N,N,M] tensor is built anywhere: the lists are sorted on the device and become the report lists directly.
- *   nx reports: xl, xi, xj, xm (int32 subscripts) and xv (counts, 1..2047); no duplicates.
+ *   nx reports: xl, xi, xj, xm (int32 subscripts) and xv (counts, 1 .. 2^31 - 1); no duplicates.
  *   nr mask entries rl, ri, rj, rm (R = 1 there, 0 elsewhere); nr < 0: every reporter may report on every tie
  *   (model.py:206-211).
  *   data_on_device != 0: all index arrays are device pointers on `device`.
- * Needs M <= 8192 and (largest count + 1) * M <= 2^20; wider tensors go through vmr_create.
+ * Limits (VMR_EINVAL with a message naming the one exceeded, checked before the kernels that need them): M <= 65535 (the
+ * mask lists hold 16-bit reporters); L N^2 2^mb < 2^64 with mb = max(13, ceil(log2 Mp)) reporter bits of the 64-bit sort keys
+ * (Mp: M rounded up to 16); (largest count + 1) * Mp < 2^32; fewer than 2^31 coordinates per list, fewer than 2^31 ties and
+ * fewer than 2^32 entry slots per layer.  M <= 8192 with (largest count + 1) * M <= 2^20 and K <= 8 runs the specialised
+ * kernels; beyond that the general ones (wider M: reporter tables read through L2).
  */
 int vmr_create_coo(vmr_handle* out, int device, int L, int N, int M, int K, int mutuality,
                    int64_t nx, const int32_t* xl, const int32_t* xi, const int32_t* xj, const int32_t* xm, const int32_t* xv,

@@ -92,22 +92,35 @@ def _check_params_consistency(df, nodes, reporters, ego, alter, reporter, layer,
 
 
 def self_reporter_coo(L, N, reporter_ids):
-    """COO subscripts of R[l,i,j,m] = 1 iff m is a reporter and m in {i, j}, i != j (reference _io.py:230-242)."""
+    """COO subscripts of R[l,i,j,m] = 1 iff m is a reporter and m in {i, j}, i != j (reference _io.py:230-242).
+    Layer after layer, reporter after reporter (sorted), each reporter's 2 (N - 1) entries in the reference's order inside its
+    N x N matrix: np.nonzero (row-major) of max(A, A^T), i.e. by (i, j) -- (i, r) for i < r, then (r, j) for every j != r, then
+    (i, r) for i > r.  Built by position, in blocks of reporters (at N = 9000 that is 162 M entries per layer)."""
     rep = np.asarray(sorted(reporter_ids), dtype=np.int64)
-    others = np.arange(N, dtype=np.int64)
-    subs = [[], [], [], []]
-    for l in range(L):
-        for r in rep:
-            o = others[others != r]
-            # reference order inside a reporter's N x N matrix: np.nonzero (row-major) of max(A, A^T)
-            i = np.concatenate([np.full(N - 1, r), o])
-            j = np.concatenate([o, np.full(N - 1, r)])
-            order = np.lexsort((j, i))
-            subs[0].append(np.full(2 * (N - 1), l)); subs[1].append(i[order]); subs[2].append(j[order])
-            subs[3].append(np.full(2 * (N - 1), r))
-    if not subs[0]:
+    nr, n = len(rep), 2 * (N - 1)
+    if L == 0 or nr == 0:
         return tuple(np.zeros(0, np.int64) for _ in range(4))
-    return tuple(np.concatenate(s) for s in subs)
+    per = nr * n
+    bi, bj = np.empty(per, np.int64), np.empty(per, np.int64)
+    p = np.arange(n, dtype=np.int64)
+    step = max(1, (1 << 22) // max(n, 1))
+    for c0 in range(0, nr, step):
+        r = rep[c0:c0 + step, None]
+        q = p - r                                   # position inside the (r, j) run
+        mid = (q >= 0) & (q < N - 1)
+        i = np.where(p < r, p, np.where(mid, r, p - (N - 2)))
+        j = np.where(mid, q + (q >= r), r)          # (the run skips j = r)
+        bi[c0 * n:(c0 + len(r)) * n] = i.ravel()
+        bj[c0 * n:(c0 + len(r)) * n] = j.ravel()
+    bm = np.repeat(rep, n)
+    out = tuple(np.empty(L * per, np.int64) for _ in range(4))
+    for l in range(L):
+        sl = slice(l * per, (l + 1) * per)
+        out[0][sl] = l
+        out[1][sl] = bi
+        out[2][sl] = bj
+        out[3][sl] = bm
+    return out
 
 
 def read_from_edgelist(df, nodes: list = [], reporters: list = [], is_weighted: bool = False,

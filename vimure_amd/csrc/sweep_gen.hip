@@ -20,6 +20,7 @@ struct GenArgs {
   const uint8_t* cls;          // by position; null: every mask row is all ones
   const unsigned* Qt;          // by position
   const uint64_t* Rb; const unsigned* rq; const unsigned short* Rm; const unsigned long long* rbase;   // partial mask rows, by tie
+  const unsigned* rm2;         // by position, wide handles whose lists hold at most two reporters: m0 | m1 << 16 (vmr_ctx::rm2); null: the lists
   double* rho; const double* logpr; const double* par;
   double *slotR, *Hg, *slotF, *slotA;
   int Gl, update, elbo, hist, sum_a;
@@ -82,7 +83,7 @@ __global__ __launch_bounds__(512) void k_sweep_gen(GenArgs a, Geo g) {
   const unsigned* rsl = a.rs + (size_t)l * (NS + 1);
   const unsigned* El = a.E + a.ebase[l];
   const unsigned* EXl = a.EX ? a.EX + a.ebase[l] : nullptr;
-  const unsigned* pl = a.perm + (size_t)l * NS * 64;
+  const unsigned* pl = (a.rm2 ? a.rm2 : a.perm) + (size_t)l * NS * 64;   // (the `tie` of a partial row: the tie, or its packed list)
   const uint8_t* cl = a.cls ? a.cls + (size_t)l * T : nullptr;
   const unsigned* Ql = a.Qt ? a.Qt + (size_t)l * T : nullptr;
   const uint64_t* Rl = a.Rb ? a.Rb + (size_t)l * T * g.W : nullptr;
@@ -94,7 +95,11 @@ __global__ __launch_bounds__(512) void k_sweep_gen(GenArgs a, Geo g) {
   double* Al = a.slotA + ((size_t)l * NSLOT + (gb % NSLOT)) * (size_t)g.W * 64 * K;
   // the reporters of a partial mask row: f(m) for every m with R[l, tie, m] = 1
   auto for_reporters = [&](unsigned tie, auto&& f) {
-    if (rql) {
+    if (a.rm2) {   // tie = m0 | m1 << 16, 0xffff: none -- the list's order, without the perm / rq / Rm reads
+      const unsigned m0 = tie & 0xffffu, m1 = tie >> 16;
+      if (m0 != 0xffffu) f((int)m0);
+      if (m1 != 0xffffu) f((int)m1);
+    } else if (rql) {
       const unsigned q0 = rql[tie], q1 = rql[tie + 1];
       for (unsigned q = q0; q < q1; ++q) f((int)Rml[q]);
     } else if (Rl) {
@@ -588,7 +593,7 @@ __global__ __launch_bounds__(64) void k_sample_gen(const double* __restrict__ rh
 static int gen_pass(vmr_ctx* h, int update, int elbo, int hist, int sum_a) {
   const Geo& g = h->g;
   const long long NS = ((long long)g.N * g.N + 63) / 64;
-  GenArgs a{h->E, h->EX, h->rs, h->ebase, h->perm, h->cls_p, h->Qt_p, h->Rb, h->rq, h->Rm, h->rbase, h->rho, h->logpr, h->par,
+  GenArgs a{h->E, h->EX, h->rs, h->ebase, h->perm, h->cls_p, h->Qt_p, h->Rb, h->rq, h->Rm, h->rbase, h->rm2, h->rho, h->logpr, h->par,
             h->slotR, h->Hg, h->slotF, h->slotA, 1, update, elbo, hist, sum_a, 0,
             reinterpret_cast<unsigned long long*>(h->gen_s1 + (size_t)g.L * (g.Mp + g.K)), 0, 0};
   HIPCHK(h, hipMemsetAsync(a.ctr, 0, (size_t)g.L * 8, h->stream));

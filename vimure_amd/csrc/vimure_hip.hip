@@ -2303,7 +2303,8 @@ static int launch_rho(vmr_ctx* h, int mode, bool commit_nu, bool raw_nu = false,
   return VMR_OK;
 }
 
-static int choose_geo(Geo& g, int ncu, std::string& err) {
+// lists_only: a vmr_create_coo handle, which never launches the dense tiles (their LDS bound does not limit M there)
+static int choose_geo(Geo& g, int ncu, std::string& err, bool lists_only) {
   g.Mp = (g.M + 15) / 16 * 16;
   g.nchunk = g.Mp / 16;
   g.stride = (g.nchunk % 2 == 1) ? g.Mp : g.Mp + 16;
@@ -2314,7 +2315,7 @@ static int choose_geo(Geo& g, int ncu, std::string& err) {
   auto lds = [&](int b_) { return (size_t)2 * b_ * b_ * (g.stride + (size_t)g.W * 8 + 2 * g.K * 8 + 4) + tables; };
   int b = 8;
   while (b > 1 && ((size_t)2 * b * b * g.stride > budget || lds(b) > 160 * 1024)) b >>= 1;
-  if ((size_t)2 * b * b * g.stride > budget) { err = "M too large for the LDS tile (M <= ~24500 supported)"; return VMR_EINVAL; }
+  if ((size_t)2 * b * b * g.stride > budget && !lists_only) { err = "M too large for the LDS tile (M <= ~24500 supported)"; return VMR_EINVAL; }
   g.b = b; g.lb = (b == 8) ? 3 : (b == 4) ? 2 : (b == 2) ? 1 : 0;
   g.nb = (g.N + b - 1) / b;
   g.nt = 2 * b * b;
@@ -2353,7 +2354,7 @@ const char* vmr_last_error(vmr_handle h) { return h ? h->err.c_str() : g_create_
 // ------------------------------------------------------------------------------------------
 
 // context, geometry, streams and the small per-dataset arrays
-static int create_ctx(vmr_ctx** out, hipDeviceProp_t* prop, int device, int L, int N, int M, int K, int mutuality, double eps) {
+static int create_ctx(vmr_ctx** out, hipDeviceProp_t* prop, int device, int L, int N, int M, int K, int mutuality, double eps, bool lists_only = false) {
   if (L < 1 || N < 1 || M < 1) return fail(nullptr, VMR_EINVAL, "L, N, M must be positive");
   if (K < 2 || K > KGEN_MAX) return fail(nullptr, VMR_EINVAL, "K must be in [2, 256]");
   int ndev = 0;
@@ -2368,7 +2369,7 @@ static int create_ctx(vmr_ctx** out, hipDeviceProp_t* prop, int device, int L, i
   g.L = L; g.N = N; g.M = M; g.K = K; g.mut = mutuality ? 1 : 0; g.eps = eps;
   g.gen = K > KMAX ? 1 : 0; g.wide = 0;   // (wide entries: decided once the largest count is known)
   std::string err;
-  if (choose_geo(g, prop->multiProcessorCount, err) != VMR_OK) return fail(nullptr, VMR_EINVAL, err.c_str());
+  if (choose_geo(g, prop->multiProcessorCount, err, lists_only) != VMR_OK) return fail(nullptr, VMR_EINVAL, err.c_str());
   memset(h->prof_ms, 0, sizeof h->prof_ms); memset(h->prof_n, 0, sizeof h->prof_n);
   CK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
   CK(hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
@@ -2589,7 +2590,8 @@ static int create_tail(vmr_ctx* h, const hipDeviceProp_t& prop) {
   Geo& g = h->g;
   const int L = g.L, K = g.K;
   g.ml = (h->sparse && h->rq) ? 1 : 0;
-  if (g.ml && !g.gen && h->rm_maxrow <= 2 && !getenv("VMR_NO_RM2")) {   // (the self-reporter mask of survey data: lists of two)
+  // (the self-reporter mask of survey data: lists of two; the general kernels take it on wide handles only, Mp > 8192)
+  if (g.ml && (!g.gen || g.Mp > 8192) && h->rm_maxrow <= 2 && !getenv("VMR_NO_RM2")) {
     const size_t T_ = (size_t)g.N * g.N, NS_ = (T_ + 63) / 64, n_ = (size_t)L * NS_ * 64;
     CK(hipMalloc(&h->rm2, n_ * 4));
     hipLaunchKernelGGL(k_rm2, dim3((unsigned)std::min<size_t>(4096, (n_ + 255) / 256)), dim3(256), 0, h->stream, h->perm, h->rq, h->Rm, h->rbase, h->rm2, T_, NS_, L);
@@ -2599,7 +2601,6 @@ static int create_tail(vmr_ctx* h, const hipDeviceProp_t& prop) {
     // the general kernels: one copy of H with every category, nothing in LDS, no constants C (sweep_gen.h)
     if (g.det) return fail(nullptr, VMR_EINVAL, "VMR_DETERMINISTIC=1 needs the specialised kernels: K <= 8, counts <= 2047, (largest count + 1) * M <= 2^20");
     g.ml = 0; g.hc = 0; g.yt = 0; g.two_pass = 0;
-    if (h->rm2) { CK(hipFree(h->rm2)); h->rm2 = nullptr; }
     const double hb = (double)L * g.Y * g.Mp * K * 8.0;
     size_t fr = 0, tot = 0;
     CK(hipMemGetInfo(&fr, &tot));
@@ -2925,16 +2926,19 @@ extern "C" int vmr_create(vmr_handle* out, int device, int L, int N, int M, int 
 // Reports and mask entries are sorted by (layer, tie, reporter) (one 64-bit radix sort each); sorted order IS the tie-major
 // order k_sp_round consumes, the mirror count and the mask bit of a report are binary searches in the sorted keys, and a
 // sparse mask becomes the mask lists directly.
+// A key is tie << mb | m, with mb = max(13, ceil(log2 Mp)) bits for the reporter (vmr_ctx::coo_mb): 13 up to Mp = 8192, up to
+// 16 at M = 65535 (the mask lists hold 16-bit reporters).
 // ------------------------------------------------------------------------------------------
-#define COO_KEY(tie, m) (((unsigned long long)(tie) << 13) | (unsigned long long)(m))
+#define COO_KEY(tie, m, mb) (((unsigned long long)(tie) << (mb)) | (unsigned long long)(m))
+#define COO_M(key, mb) ((unsigned)((key) & ((1ull << (mb)) - 1ull)))
 
 __global__ void k_coo_keys(const int32_t* __restrict__ sl, const int32_t* __restrict__ si, const int32_t* __restrict__ sj,
-                           const int32_t* __restrict__ sm, long long n, int L, int N, int M, unsigned long long* __restrict__ keys,
+                           const int32_t* __restrict__ sm, long long n, int L, int N, int M, int mb, unsigned long long* __restrict__ keys,
                            int* bad) {
   for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
     const int l = sl[e], i = si[e], j = sj[e], m = sm[e];
     if (l < 0 || l >= L || i < 0 || i >= N || j < 0 || j >= N || m < 0 || m >= M) { atomicOr(bad, 1); keys[e] = ~0ull; continue; }
-    keys[e] = COO_KEY(((unsigned long long)l * N + i) * N + j, m);
+    keys[e] = COO_KEY(((unsigned long long)l * N + i) * N + j, m, mb);
   }
 }
 // index of `key` in the sorted keys, or -1
@@ -2947,10 +2951,10 @@ __device__ __forceinline__ long long coo_find(const unsigned long long* __restri
   return (a < n && k[a] == key) ? a : -1;
 }
 // per-tie counts of the sorted keys (cnt [L][T+1], layer-relative ties); duplicates flagged
-__global__ void k_coo_count(const unsigned long long* __restrict__ k, long long n, size_t T, unsigned* __restrict__ cnt, int* bad) {
+__global__ void k_coo_count(const unsigned long long* __restrict__ k, long long n, size_t T, int mb, unsigned* __restrict__ cnt, int* bad) {
   for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
     if (e > 0 && k[e] == k[e - 1]) atomicOr(bad, 2);
-    const unsigned long long tie = k[e] >> 13, l = tie / T;
+    const unsigned long long tie = k[e] >> mb, l = tie / T;
     atomicAdd(&cnt[l * (T + 1) + (tie - l * T)], 1u);
   }
 }
@@ -2975,22 +2979,22 @@ __global__ void k_coo_class(const unsigned* __restrict__ cx, const unsigned* __r
 // the reports' entries in tie-major (= sorted) order, the mirror sums Qt, sum and maximum of the counts
 template <bool MUT>
 __global__ void k_coo_entries(const unsigned long long* __restrict__ kx, const unsigned* __restrict__ vx, long long nx,
-                              const unsigned long long* __restrict__ kr, long long nr /* < 0: all ones */, int N, int Mp,
+                              const unsigned long long* __restrict__ kr, long long nr /* < 0: all ones */, int N, int Mp, int mb,
                               unsigned* __restrict__ etmp, unsigned* __restrict__ etmp2, unsigned* __restrict__ Qt, unsigned long long* sumx, unsigned* xmax, int* bad) {
   unsigned long long s = 0;
   unsigned mx = 0;
   const unsigned long long T = (unsigned long long)N * N;
   for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < nx; e += (long long)gridDim.x * blockDim.x) {
-    const unsigned long long key = kx[e], tie = key >> 13, l = tie / T, t = tie - l * T, i = t / N, j = t - i * N;
-    const unsigned m = (unsigned)(key & 0x1fffu), x = vx[e];
+    const unsigned long long key = kx[e], tie = key >> mb, l = tie / T, t = tie - l * T, i = t / N, j = t - i * N;
+    const unsigned m = COO_M(key, mb), x = vx[e];
     if (x == 0u || x > 0x7fffffffu) { atomicOr(bad, 4); continue; }   // (int32 values: zero or negative)
     s += x; mx = max(mx, x);
     const unsigned long long tm = l * T + j * N + i;
     unsigned y = 0;
     if (MUT) {
-      const long long f = coo_find(kx, nx, COO_KEY(tm, m));
+      const long long f = coo_find(kx, nx, COO_KEY(tm, m, mb));
       y = f >= 0 ? vx[f] : 0u;
-      if (nr < 0 || coo_find(kr, nr, COO_KEY(tm, m)) >= 0) atomicAdd(&Qt[tm], x);   // R[mirror, m] X[this, m]
+      if (nr < 0 || coo_find(kr, nr, COO_KEY(tm, m, mb)) >= 0) atomicAdd(&Qt[tm], x);   // R[mirror, m] X[this, m]
     }
     const unsigned inr = (nr < 0 || coo_find(kr, nr, key) >= 0) ? 1u : 0u;
     // two words per entry (sweep_sl.h, wide entries); k_coo_pack folds them into one where the packed format holds the tensor
@@ -3009,9 +3013,9 @@ __global__ void k_coo_pack(unsigned* __restrict__ etmp, const unsigned* __restri
   }
 }
 // first sorted key of every layer (starts[L] = n)
-__global__ void k_coo_layer_starts(const unsigned long long* __restrict__ k, long long n, unsigned long long T, int L, unsigned long long* starts) {
+__global__ void k_coo_layer_starts(const unsigned long long* __restrict__ k, long long n, unsigned long long T, int L, int mb, unsigned long long* starts) {
   for (int l = threadIdx.x; l <= L; l += blockDim.x) {
-    const unsigned long long k0 = ((unsigned long long)l * T) << 13;
+    const unsigned long long k0 = ((unsigned long long)l * T) << mb;
     long long a = 0, b = n;
     while (a < b) { const long long c = a + ((b - a) >> 1); if (k[c] < k0) a = c + 1; else b = c; }
     starts[l] = (unsigned long long)a;
@@ -3025,22 +3029,22 @@ __global__ void k_coo_listed(const unsigned* __restrict__ cr, const uint8_t* __r
   }
 }
 // reporters of the partial rows into the mask lists (rq scanned per layer; rbase: layer offsets)
-__global__ void k_coo_rm(const unsigned long long* __restrict__ kr, long long nr, size_t T, const uint8_t* __restrict__ rcls,
+__global__ void k_coo_rm(const unsigned long long* __restrict__ kr, long long nr, size_t T, int mb, const uint8_t* __restrict__ rcls,
                          const unsigned* __restrict__ rq, const unsigned long long* __restrict__ rbase, unsigned short* __restrict__ Rm) {
   for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < nr; e += (long long)gridDim.x * blockDim.x) {
-    const unsigned long long tie = kr[e] >> 13, l = tie / T, t = tie - l * T;
+    const unsigned long long tie = kr[e] >> mb, l = tie / T, t = tie - l * T;
     if (rcls[tie] != 2) continue;
-    long long a = 0, b = e;   // first entry of this tie: lower bound of tie << 13 in [0, e]
-    const unsigned long long k0 = tie << 13;
+    long long a = 0, b = e;   // first entry of this tie: lower bound of tie << mb in [0, e]
+    const unsigned long long k0 = tie << mb;
     while (a < b) { const long long c = a + ((b - a) >> 1); if (kr[c] < k0) a = c + 1; else b = c; }
-    Rm[rbase[l] + rq[l * (T + 1) + t] + (unsigned long long)(e - a)] = (unsigned short)(kr[e] & 0x1fffu);
+    Rm[rbase[l] + rq[l * (T + 1) + t] + (unsigned long long)(e - a)] = (unsigned short)COO_M(kr[e], mb);
   }
 }
 // a mask whose partial rows are long: bit-packed words as in the dense path
-__global__ void k_coo_rbits(const unsigned long long* __restrict__ kr, long long nr, int W, unsigned long long* __restrict__ Rb) {
+__global__ void k_coo_rbits(const unsigned long long* __restrict__ kr, long long nr, int W, int mb, unsigned long long* __restrict__ Rb) {
   for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < nr; e += (long long)gridDim.x * blockDim.x) {
-    const unsigned long long tie = kr[e] >> 13;
-    const unsigned m = (unsigned)(kr[e] & 0x1fffu);
+    const unsigned long long tie = kr[e] >> mb;
+    const unsigned m = COO_M(kr[e], mb);
     atomicOr(&Rb[tie * W + (m >> 6)], 1ull << (m & 63));
   }
 }
@@ -3068,10 +3072,11 @@ static int coo_sorted(vmr_ctx* h, long long n, const int32_t* sl, const int32_t*
   CK(hipMalloc(&k1, nn * 8));
   if (sv) CK(hipMalloc(&v1, nn * 4));
   const unsigned grid = (unsigned)std::min<long long>(4096, (n + 255) / 256 + 1);
-  hipLaunchKernelGGL(k_coo_keys, dim3(grid), dim3(256), 0, h->stream, src[0], src[1], src[2], src[3], n, g.L, g.N, g.M, k0, bad_dev);
+  const int mb = h->coo_mb;
+  hipLaunchKernelGGL(k_coo_keys, dim3(grid), dim3(256), 0, h->stream, src[0], src[1], src[2], src[3], n, g.L, g.N, g.M, mb, k0, bad_dev);
   CK(hipGetLastError());
-  int bits = 13;
-  { unsigned long long ties = (unsigned long long)g.L * g.N * g.N; while ((1ull << (bits - 13)) < ties && bits < 64) ++bits; }
+  int bits = mb;   // (the sort's bit range: mb reporter bits and ceil(log2(L N^2)) tie bits; create_coo checked it is <= 64)
+  { unsigned long long ties = (unsigned long long)g.L * g.N * g.N; while ((1ull << (bits - mb)) < ties && bits < 64) ++bits; }
   size_t tb = 0;
   void* td = nullptr;
   if (n > 0) {
@@ -3096,7 +3101,7 @@ static int create_coo(vmr_ctx* h, const hipDeviceProp_t& prop, long long nx, con
   Geo& g = h->g;
   const int L = g.L, N = g.N, M = g.M, K = g.K;
   const size_t T = (size_t)N * N, rows = (size_t)L * T, n1 = (size_t)L * (T + 1);
-  if (g.Mp > 8192) return fail(nullptr, VMR_EINVAL, "report lists hold 13-bit reporter indices: M <= 8192 (use vmr_create for wider tensors)");
+  const int mb = h->coo_mb;
   if (nx >= 0x7fffffffll || nr >= 0x7fffffffll) return fail(nullptr, VMR_EINVAL, "more than 2^31 coordinates in one call");
   int* bad_dev = nullptr;
   CK(hipMalloc(&bad_dev, 4));
@@ -3118,11 +3123,11 @@ static int create_coo(vmr_ctx* h, const hipDeviceProp_t& prop, long long nx, con
   CKC(hipMalloc(&cx, n1 * 4));
   CKC(hipMemsetAsync(cx, 0, n1 * 4, h->stream));
   const unsigned gx = (unsigned)std::min<long long>(8192, (nx + 255) / 256 + 1), gr = (unsigned)std::min<long long>(8192, (std::max<long long>(nr, 0) + 255) / 256 + 1);
-  hipLaunchKernelGGL(k_coo_count, dim3(gx), dim3(256), 0, h->stream, kx, nx, T, cx, bad_dev);
+  hipLaunchKernelGGL(k_coo_count, dim3(gx), dim3(256), 0, h->stream, kx, nx, T, mb, cx, bad_dev);
   if (nr >= 0) {
     CKC(hipMalloc(&cr, n1 * 4));
     CKC(hipMemsetAsync(cr, 0, n1 * 4, h->stream));
-    hipLaunchKernelGGL(k_coo_count, dim3(gr), dim3(256), 0, h->stream, kr, nr, T, cr, bad_dev);
+    hipLaunchKernelGGL(k_coo_count, dim3(gr), dim3(256), 0, h->stream, kr, nr, T, mb, cr, bad_dev);
   }
   CKC(hipMalloc(&maxrow_dev, 4));
   CKC(hipMemsetAsync(maxrow_dev, 0, 4, h->stream));
@@ -3132,8 +3137,8 @@ static int create_coo(vmr_ctx* h, const hipDeviceProp_t& prop, long long nx, con
   CKC(hipMalloc(&etmp2, ((size_t)nx + 64) * 4));
   CKC(hipMalloc(&h->Qt, rows * 4));
   CKC(hipMemsetAsync(h->Qt, 0, rows * 4, h->stream));
-  if (g.mut) hipLaunchKernelGGL(k_coo_entries<true>, dim3(gx), dim3(256), 0, h->stream, kx, vx, nx, kr, nr, N, g.Mp, etmp, etmp2, h->Qt, h->sumx, h->xmax, bad_dev);
-  else hipLaunchKernelGGL(k_coo_entries<false>, dim3(gx), dim3(256), 0, h->stream, kx, vx, nx, kr, nr, N, g.Mp, etmp, etmp2, h->Qt, h->sumx, h->xmax, bad_dev);
+  if (g.mut) hipLaunchKernelGGL(k_coo_entries<true>, dim3(gx), dim3(256), 0, h->stream, kx, vx, nx, kr, nr, N, g.Mp, mb, etmp, etmp2, h->Qt, h->sumx, h->xmax, bad_dev);
+  else hipLaunchKernelGGL(k_coo_entries<false>, dim3(gx), dim3(256), 0, h->stream, kx, vx, nx, kr, nr, N, g.Mp, mb, etmp, etmp2, h->Qt, h->sumx, h->xmax, bad_dev);
   CKC(hipGetLastError());
   CKC(hipStreamSynchronize(h->stream));
   int bad = 0;
@@ -3157,7 +3162,7 @@ static int create_coo(vmr_ctx* h, const hipDeviceProp_t& prop, long long nx, con
   {
     unsigned long long* starts = nullptr;
     CKC(hipMalloc(&starts, (size_t)(L + 1) * 8));
-    hipLaunchKernelGGL(k_coo_layer_starts, dim3(1), dim3(64), 0, h->stream, kx, nx, (unsigned long long)T, L, starts);
+    hipLaunchKernelGGL(k_coo_layer_starts, dim3(1), dim3(64), 0, h->stream, kx, nx, (unsigned long long)T, L, mb, starts);
     std::vector<unsigned long long> st(L + 1);
     hipError_t e1 = hipMemcpyAsync(st.data(), starts, (size_t)(L + 1) * 8, hipMemcpyDeviceToHost, h->stream);
     if (e1 == hipSuccess) e1 = hipStreamSynchronize(h->stream);
@@ -3165,9 +3170,9 @@ static int create_coo(vmr_ctx* h, const hipDeviceProp_t& prop, long long nx, con
     CKC(e1);
     for (int l = 0; l < L; ++l) nl[l] = st[l + 1] - st[l];
   }
-  // packed entries (11-bit counts, 2^20 table rows) where they hold the tensor, two words per entry otherwise; the general
-  // kernels take over beyond KMAX categories or with wide entries (sweep_gen.h)
-  g.wide = (xmv <= SL_XMAX && (size_t)(xmv + 1) * g.Mp <= SL_YM_ROWS) ? 0 : 1;
+  // packed entries (13-bit reporters, 11-bit counts, 2^20 table rows) where they hold the tensor, two words per entry otherwise;
+  // the general kernels take over beyond KMAX categories or with wide entries (sweep_gen.h)
+  g.wide = (g.Mp <= 8192 && xmv <= SL_XMAX && (size_t)(xmv + 1) * g.Mp <= SL_YM_ROWS) ? 0 : 1;
   g.gen = (K > KMAX || g.wide) ? 1 : 0;
   if ((unsigned long long)xmv * (unsigned long long)M > 0xffffffffull) {
     cleanup();
@@ -3180,10 +3185,25 @@ static int create_coo(vmr_ctx* h, const hipDeviceProp_t& prop, long long nx, con
   rc = sl_place_entries(h, cx, nl, etmp, g.wide ? etmp2 : nullptr, nullptr);
   if (!rc) rc = sl_finish(h);
   if (rc) { cleanup(); return rc; }
-  // the mask: all ones needs nothing; partial rows become mask lists when they are short, bit-packed words otherwise
+  // the mask: all ones needs nothing; partial rows become mask lists when they are short, bit-packed words otherwise.  The LDS
+  // A[Mp][K] of k_mask_lists and of the K <= 8 sweep bounds the lists of narrow handles; a wide one (Mp > 8192: general kernels
+  // only, whose pass walks the lists from global memory) takes them whatever Mp K.
   if (nr >= 0 && h->n_partial > 0) {
     const double list_bytes = 2.0 * (double)nr + 4.0 * (double)rows, word_bytes = (double)h->n_partial * g.W * 8.0;
-    const bool lists = !getenv("VMR_NO_RLISTS") && maxrow <= 64 && (list_bytes * 4.0 <= word_bytes || g.N <= 1024) && (size_t)g.Mp * K * 8 <= 160 * 1024;
+    const bool lists = !getenv("VMR_NO_RLISTS") && maxrow <= 64 && (list_bytes * 4.0 <= word_bytes || g.N <= 1024) &&
+                       (g.Mp > 8192 || (size_t)g.Mp * K * 8 <= 160 * 1024);
+    {
+      size_t fr = 0, tot = 0;
+      CKC(hipMemGetInfo(&fr, &tot));
+      const double need = lists ? list_bytes + 4.0 * (double)n1 : (double)rows * g.W * 8.0;
+      if (need > (double)fr) {
+        char msg[320];
+        snprintf(msg, sizeof msg, "the mask's partial rows would take %.1f GB as %s (%llu partial rows, longest %u reporters, M = %d): more than the "
+                 "device memory left (%.1f GB)", need / 1e9, lists ? "mask lists" : "bit-packed words", (unsigned long long)h->n_partial, maxrow, M, fr / 1e9);
+        cleanup();
+        return fail(nullptr, VMR_EINVAL, msg);
+      }
+    }
     if (lists) {
       unsigned* bs = nullptr;
       CKC(hipMalloc(&h->rq, n1 * 4));
@@ -3202,12 +3222,12 @@ static int create_coo(vmr_ctx* h, const hipDeviceProp_t& prop, long long nx, con
       CKC(hipMalloc(&h->rbase, (size_t)L * 8));
       CKC(hipMemcpy(h->rbase, rb_.data(), (size_t)L * 8, hipMemcpyHostToDevice));
       CKC(hipMalloc(&h->Rm, ((size_t)h->n_rm + 64) * 2));
-      hipLaunchKernelGGL(k_coo_rm, dim3(gr), dim3(256), 0, h->stream, kr, nr, T, h->rcls, h->rq, h->rbase, h->Rm);
+      hipLaunchKernelGGL(k_coo_rm, dim3(gr), dim3(256), 0, h->stream, kr, nr, T, mb, h->rcls, h->rq, h->rbase, h->Rm);
       CKC(hipGetLastError());
     } else {
       CKC(hipMalloc(&h->Rb, rows * g.W * 8));
       CKC(hipMemsetAsync(h->Rb, 0, rows * g.W * 8, h->stream));
-      hipLaunchKernelGGL(k_coo_rbits, dim3(gr), dim3(256), 0, h->stream, kr, nr, g.W, reinterpret_cast<unsigned long long*>(h->Rb));
+      hipLaunchKernelGGL(k_coo_rbits, dim3(gr), dim3(256), 0, h->stream, kr, nr, g.W, mb, reinterpret_cast<unsigned long long*>(h->Rb));
       CKC(hipGetLastError());
     }
   }
@@ -3224,9 +3244,17 @@ extern "C" int vmr_create_coo(vmr_handle* out, int device, int L, int N, int M, 
   *out = nullptr;
   if (nx < 0 || (nx > 0 && (!xl || !xi || !xj || !xm || !xv))) return fail(nullptr, VMR_EINVAL, "X coordinate arrays missing");
   if (nr > 0 && (!rl || !ri || !rj || !rm)) return fail(nullptr, VMR_EINVAL, "R coordinate arrays missing");
+  // limits of the coordinate route, before anything is allocated
+  if (L < 1 || N < 1 || M < 1) return fail(nullptr, VMR_EINVAL, "L, N, M must be positive");
+  if (M > 65535) return fail(nullptr, VMR_EINVAL, "M exceeds 65535 (M_COO_MAX): the mask lists hold 16-bit reporter indices");
+  int mb = 13;   // reporter bits of a sort key (COO_KEY): 13 up to Mp = 8192, as before wider reporter dimensions were taken
+  while ((1 << mb) < (M + 15) / 16 * 16) ++mb;
+  if ((((unsigned __int128)L * (unsigned)N * (unsigned)N) << mb) >> 64)
+    return fail(nullptr, VMR_EINVAL, "L * N^2 * 2^ceil(log2 M) must stay below 2^64 (the 64-bit sort keys of the coordinates)");
   vmr_ctx* h = nullptr;
   hipDeviceProp_t prop;
-  int rc = create_ctx(&h, &prop, device, L, N, M, K, mutuality, eps);
+  int rc = create_ctx(&h, &prop, device, L, N, M, K, mutuality, eps, true);
+  if (!rc) h->coo_mb = mb;
   if (!rc) rc = create_coo(h, prop, nx, xl, xi, xj, xm, xv, nr, rl, ri, rj, rm, data_on_device);
   if (rc) { if (h) vmr_destroy(h); return rc; }
   *out = h;

@@ -126,7 +126,8 @@ struct vmr_ctx {
   unsigned long long* rbase = nullptr; // device [L]
   unsigned long long n_rm = 0;         // listed reporters in all
   unsigned rm_maxrow = 0;              // longest list
-  unsigned* rm2 = nullptr;             // [L][NS * 64] by sorted position, when no list is longer than 2 (SlArgs::rm2)
+  unsigned* rm2 = nullptr;             // [L][NS * 64] by sorted position, when no list is longer than 2 (SlArgs::rm2, GenArgs::rm2)
+  int coo_mb = 13;                     // vmr_create_coo: reporter bits of a sort key, max(13, ceil(log2 Mp))
   unsigned long long* sumx = nullptr;
   // state
   double *rho = nullptr, *logpr = nullptr;

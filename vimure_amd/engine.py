@@ -84,7 +84,9 @@ class CaviEngine:
         """Dataset from coordinate lists -- the reference's own containers (`X.subs`, `X.vals`, `R.subs`; reference
         model.py:136-171) -- without a dense [L,N,N,M] tensor on the host or the device (vmr_create_coo).
         subs: 4 index arrays (l, i, j, m); vals: counts in [1, 2^31); R: None (every reporter may report on every tie) or 4
-        index arrays of the mask's non-zeros; NumPy arrays or torch GPU tensors (int32 / int64)."""
+        index arrays of the mask's non-zeros; NumPy arrays or torch GPU tensors (int32 / int64).
+        Limits (ValueError naming the one exceeded): M <= 65535 (tensor.M_COO_MAX: 16-bit reporters in the mask lists),
+        L N^2 2^ceil(log2 M) < 2^64 (the sort keys), (largest count + 1) * M < 2^32; M > 8192 runs the general kernels."""
         self = cls.__new__(cls)
         self._h = C.c_void_p()
         self._staging = []

@@ -19,7 +19,7 @@ from scipy.stats import poisson
 
 from ._log import setup_logging
 from .engine import CaviEngine, host_buffer
-from .tensor import SparseTensor, engine_data, is_sparse_like, to_dense_u8
+from .tensor import M_COO_NARROW, SparseTensor, engine_data, is_sparse_like, to_dense_u8
 
 try:  # the reference is an sklearn estimator (model.py:28); keep that surface when sklearn is there
     from sklearn.base import BaseEstimator, TransformerMixin
@@ -87,7 +87,7 @@ class VimureModel(TransformerMixin, BaseEstimator):
             shape = tuple(int(s) for s in X.shape)
         else:
             Xd = engine_data(X, "X") if extra.get("engine") is None else to_dense_u8(X, "X")
-            if self.undirected and is_sparse_like(Xd) and (len(Xd.vals) == 0 or np.max(Xd.vals) <= 255):
+            if self.undirected and is_sparse_like(Xd) and int(Xd.shape[3]) <= M_COO_NARROW and (len(Xd.vals) == 0 or np.max(Xd.vals) <= 255):
                 Xd = to_dense_u8(Xd, "X")   # (the symmetry check below reads the array)
             coo = is_sparse_like(Xd)
             shape = tuple(int(s) for s in Xd.shape)

@@ -55,27 +55,43 @@ def is_sparse_like(X):
 
 
 COUNT_MAX = 2 ** 31 - 1   # counts travel as int32 coordinate values (vmr_create_coo); the reference holds int64 (utils.py:241-242)
-M_COO_MAX = 8192          # 13-bit reporter field of the coordinate keys
+M_COO_NARROW = 8192       # the 13-bit reporter keys of the coordinate lists before wider ones were taken: routing at and below it is unchanged
+M_COO_MAX = 65535         # the mask lists hold 16-bit reporters (vmr_create_coo)
+
+
+def _wide_coo(X, vals, what):
+    """A coordinate container with M > M_COO_NARROW: never densified (N = M = 9000 is 729 GB dense); explicit zeros are dropped."""
+    if int(X.shape[3]) > M_COO_MAX:
+        raise ValueError(f"{what}: the coordinate-list layout holds M <= {M_COO_MAX} reporters (M_COO_MAX), got M = {int(X.shape[3])}")
+    if len(vals) and vals.min() == 0:
+        keep = vals != 0
+        return SparseTensor(tuple(np.asarray(s)[keep] for s in X.subs), vals[keep], shape=tuple(int(v) for v in X.shape))
+    return X
 
 
 def engine_data(X, what="X"):
-    """The form a count tensor reaches the engine in: a coordinate container (-> vmr_create_coo: any count, M <= 8192) or a dense
-    uint8 array (-> vmr_create: counts <= 255, any M).  A dense array with larger counts becomes its coordinate lists."""
+    """The form a count tensor reaches the engine in: a coordinate container (-> vmr_create_coo: any count, M <= 65535) or a dense
+    uint8 array (-> vmr_create: counts <= 255).  A dense array with larger counts becomes its coordinate lists while M <=
+    M_COO_NARROW, and is refused beyond (wider tensors come as coordinate containers).  Up to M_COO_NARROW reporters a container
+    holding explicit zeros is densified, as it always was; beyond it, never."""
     if is_sparse_like(X):
         vals = np.asarray(X.vals)
         if len(vals) and (vals.min() < 0 or vals.max() > COUNT_MAX):
             raise ValueError(f"{what} entries must be integers in [0, 2^31)")
-        if int(X.shape[3]) <= M_COO_MAX and (len(vals) == 0 or vals.min() >= 1):
+        if int(X.shape[3]) > M_COO_NARROW:
+            return _wide_coo(X, vals, what)
+        if len(vals) == 0 or vals.min() >= 1:
             return X
         if len(vals) and vals.max() > 255:
-            raise ValueError(f"{what}: counts above 255 need the coordinate-list layout, which holds M <= {M_COO_MAX} reporters")
+            raise ValueError(f"{what}: counts above 255 need the coordinate-list layout, which holds M <= {M_COO_NARROW} reporters")
         return to_dense_u8(X, what)
     A = np.asarray(X)
     if A.size and A.dtype != np.uint8 and A.max() > 255:
         if A.min() < 0 or A.max() > COUNT_MAX:
             raise ValueError(f"{what} entries must be integers in [0, 2^31)")
-        if A.ndim != 4 or A.shape[3] > M_COO_MAX:
-            raise ValueError(f"{what}: counts above 255 need the coordinate-list layout, which holds M <= {M_COO_MAX} reporters")
+        if A.ndim != 4 or A.shape[3] > M_COO_NARROW:
+            raise ValueError(f"{what}: counts above 255 need the coordinate-list layout, which holds M <= {M_COO_NARROW} reporters "
+                             f"from a dense array (pass a wider tensor as a coordinate container: subs / vals, M <= {M_COO_MAX})")
         return SparseTensor.fromarray(A.astype(np.int64) if A.dtype.kind == "f" else A)
     return to_dense_u8(A, what)
 
