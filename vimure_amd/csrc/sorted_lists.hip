@@ -124,7 +124,7 @@ int sl_place_entries(vmr_ctx* h, unsigned* rp, const std::vector<unsigned long l
   int bits = 1;
   while (bits < 32 && (1ull << bits) <= (unsigned long long)g.M) ++bits;   // a tie holds at most M reports
   // (layers of long lists: a second key, k_sl_level_keys -- packed entries of a mutual network only)
-  const bool level_keys_ok = !wide && g.mut && 2 * bits <= 30 && !getenv("VMR_NO_LEVEL_SORT");
+  const bool level_keys_ok = !wide && g.mut && 2 * bits <= 30 && !h->opt.no_level_sort;
   CKS(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, tb, keys, keys2, vals, vals2, (int)T, 0, level_keys_ok ? 2 * bits : bits, h->stream));
   CKS(hipMalloc(&tmp, tb ? tb : 8));
   const unsigned tgrid = (unsigned)std::min<size_t>(8192, (T + 255) / 256), sgrid = (unsigned)std::min<size_t>(8192, (NS + 3) / 4);

@@ -598,7 +598,7 @@ static int gen_pass(vmr_ctx* h, int update, int elbo, int hist, int sum_a) {
             reinterpret_cast<unsigned long long*>(h->gen_s1 + (size_t)g.L * (g.Mp + g.K)), 0, 0};
   HIPCHK(h, hipMemsetAsync(a.ctr, 0, (size_t)g.L * 8, h->stream));
 #ifdef GEN_DEBUG
-  if (const char* d = getenv("VMR_GEN_DBG")) a.dbg = atoi(d);
+  a.dbg = h->opt.gen_dbg;
 #endif
   int lg = 1;
   while ((1 << lg) < g.K && lg < 6) ++lg;
@@ -613,7 +613,7 @@ static int gen_pass(vmr_ctx* h, int update, int elbo, int hist, int sum_a) {
   if (hist) {
     const size_t row = (size_t)g.Mp * g.K * 8, budget = (size_t)128 * 1024 - sm;   // (160 KB of LDS per CU, one workgroup on it)
     a.YL = (int)std::min<size_t>((size_t)g.Y, budget / row);
-    if (getenv("VMR_GEN_NO_LDS_H")) a.YL = 0;
+    if (h->opt.gen_no_lds_h) a.YL = 0;
     sm += (size_t)a.YL * row;
   }
   const void* fn = g.K <= 64 ? reinterpret_cast<const void*>(k_sweep_gen<1>) : g.K <= 128 ? reinterpret_cast<const void*>(k_sweep_gen<2>) : reinterpret_cast<const void*>(k_sweep_gen<4>);
@@ -646,8 +646,7 @@ int gen_hist(vmr_ctx* h) {
 static int gen_hsum_blocks(const vmr_ctx* h) {
   const Geo& g = h->g;
   const size_t rows = (size_t)g.Y * g.Mp, cells = rows * g.K;
-  const char* ev = getenv("VMR_GEN_HSUM");   // experiments and tests: force the number
-  if (ev && atoi(ev) > 0) return atoi(ev);
+  if (h->opt.gen_hsum > 0) return h->opt.gen_hsum;   // experiments and tests: force the number
   if (cells < 32768) return 1;
   int lg = 1;
   while ((1 << lg) < g.K && lg < 6) ++lg;

@@ -951,7 +951,7 @@ static int sl_launch_one(vmr_ctx* h, const SlShape& sh, SlArgs& a) {
 #ifdef SL_DEBUG
   // VMR_DEBUG_TIMES=<file>: every launch appends "<update><elbo> <waves>" and one line of four clock readings per wave
   static unsigned long long* dbg_buf = nullptr;
-  const char* tf = getenv("VMR_DEBUG_TIMES");
+  const char* tf = h->opt.debug_times[0] ? h->opt.debug_times : nullptr;
   const size_t nwv = (size_t)g.L * a.Gl * nw;
   a.dbg_t = nullptr;
   if (tf) {

@@ -1761,7 +1761,7 @@ static SlShape sl_shape(const vmr_ctx* h, bool update, bool elbo, bool hist) {
 static SlArgs sl_args(const vmr_ctx* h, const SlShape& sh, int do_hist, int sum_a = 0) {
   return SlArgs{h->E, h->rs, h->ebase, h->perm, h->sy, h->cls_p, h->Qt_p, h->Rb, h->rq, h->Rm, h->rbase, h->rm2, h->rho, h->logpr, h->par, h->slotR,
                 h->lutg, h->Hg, h->slotF, h->slotA, 1, do_hist, sh.yt, sh.hc, sum_a, nullptr, nullptr, 0, 0, nullptr, h->lp0 ? 1 : 0, h->g.farl, (do_hist == 1 && h->g.two_pass && sh.hc >= 1) ? h->h0s : nullptr, (do_hist == 1 && h->g.two_pass && sh.hc >= 1 && h->h0s) ? h->x0p : nullptr,
-                (h->h0s && h->g.two_pass && !getenv("VMR_NO_LV0R")) ? 1 : 0, h->E + h->n_slots, 0};   // (level 0 must be among the LDS levels: its deficits go there)
+                (h->h0s && h->g.two_pass && !h->opt.no_lv0r) ? 1 : 0, h->E + h->n_slots, 0};   // (level 0 must be among the LDS levels: its deficits go there)
 }
 static int sl_launch(vmr_ctx* h, int mode, const SlShape& sh, SlArgs& a) {
   sl_launch_fn fn = vmr_sl_launcher(h->g.K);
@@ -2147,7 +2147,7 @@ static int launch_gamma(vmr_ctx* h, bool with_phi) {
     if (rc) return rc;
   }
   // fork: the mask sums A = sum_ij R rho (memory-bound) run beside the statistics pass when one is needed
-  hipStream_t ms = (h->serial || h->h_valid) ? h->stream : h->stream2;
+  hipStream_t ms = h->h_valid ? h->stream : h->stream2;
   if (ms != h->stream) {
     HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));
     HIPCHK(h, hipStreamWaitEvent(ms, h->ev_fork, 0));
@@ -2267,7 +2267,7 @@ static int launch_rho(vmr_ctx* h, int mode, bool commit_nu, bool raw_nu = false,
     // (the re-write of ensure_rho takes the nu before that commit from SC_G_NU_STALE) or without mutuality, in one pass per sweep
     // -- and only where the pass itself sums rho over the mask rows: the mask kernels of launch_gamma read rho from memory
     const bool lazy = !store && mode == 0 && do_hist && (nu_in_pass ? commit_nu : !g.mut) && g.fuse_full && (h->n_partial == 0 || g.ml) &&
-                      !g.farl && !getenv("VMR_ALWAYS_STORE_RHO");   // (k_far_hist reads rho)
+                      !g.farl && !h->opt.always_store_rho;   // (k_far_hist reads rho)
     {
       Prof p(h, lazy ? VMR_KERNEL_RHO_NOSTORE : mode == 2 ? VMR_KERNEL_ELBO : mode == 1 ? VMR_KERNEL_RHO_ELBO : VMR_KERNEL_RHO);
       if ((rc = sl_launch(h, lazy ? 4 : mode, shs, as))) return rc;
@@ -2334,10 +2334,6 @@ static int choose_geo(Geo& g, int ncu, std::string& err, bool lists_only) {
   g.Gm = (int)gm;
   int need = (g.nt * g.nchunk + TPB - 1) / TPB;
   g.pf = need <= 4 ? 4 : need <= 8 ? 8 : 12;
-  const char* hv = getenv("VMR_HEAVY");
-  g.heavy = hv ? atoi(hv) : 8;   // in non-zero DWORDS of the share
-  const char* dbg = getenv("VMR_DEBUG");
-  g.dbg = dbg ? atoi(dbg) : 0;
   return VMR_OK;
 }
 
@@ -2352,6 +2348,37 @@ const char* vmr_last_error(vmr_handle h) { return h ? h->err.c_str() : g_create_
 // ------------------------------------------------------------------------------------------
 // vmr_create / vmr_create_coo
 // ------------------------------------------------------------------------------------------
+
+static void read_opts(VmrOpts& o) {
+  memset(&o, 0, sizeof o);   // (padding too: batch_kind compares records with memcmp)
+  auto set = [](const char* n) { return getenv(n) != nullptr; };
+  auto num = [](const char* n, int dflt) { const char* e = getenv(n); return e ? atoi(e) : dflt; };
+  if (const char* f = getenv("VMR_FORMAT")) o.format = !strcmp(f, "dense") ? 1 : !strcmp(f, "sparse") ? 2 : 0;
+  o.deterministic = num("VMR_DETERMINISTIC", 0) != 0;
+  o.graph = num("VMR_GRAPH", 0) != 0;
+  o.debug = num("VMR_DEBUG", 0);
+  o.levels = num("VMR_LEVELS", 64);
+  o.two_pass = num("VMR_TWO_PASS", 0);
+  o.farl = num("VMR_FARL", 0);
+  o.yt = set("VMR_YT") ? std::max(0, num("VMR_YT", 0)) : -1;
+  o.hc = set("VMR_HC") ? std::max(0, num("VMR_HC", 0)) : -1;
+  o.tpb = num("VMR_TPB", 0);
+  o.st_tpb = num("VMR_ST_TPB", 0);
+  o.no_level0 = set("VMR_NO_LEVEL0");
+  o.no_x0 = set("VMR_NO_X0");
+  o.no_lv0r = set("VMR_NO_LV0R");
+  o.no_level_sort = set("VMR_NO_LEVEL_SORT");
+  o.no_rlists = set("VMR_NO_RLISTS");
+  o.no_rm2 = set("VMR_NO_RM2");
+  o.no_lp0 = set("VMR_NO_LP0");
+  o.always_store_rho = set("VMR_ALWAYS_STORE_RHO");
+  o.debug_lazy_rho = set("VMR_DEBUG_LAZY_RHO");
+  o.gen_hsum = num("VMR_GEN_HSUM", 0);
+  o.gen_no_lds_h = set("VMR_GEN_NO_LDS_H");
+  o.gen_dbg = num("VMR_GEN_DBG", 0);
+  o.batch_fg = set("VMR_BATCH_FG") ? std::max(1, std::min(FG_G, num("VMR_BATCH_FG", 0))) : 0;
+  if (const char* t = getenv("VMR_DEBUG_TIMES")) snprintf(o.debug_times, sizeof o.debug_times, "%s", t);
+}
 
 // context, geometry, streams and the small per-dataset arrays
 static int create_ctx(vmr_ctx** out, hipDeviceProp_t* prop, int device, int L, int N, int M, int K, int mutuality, double eps, bool lists_only = false) {
@@ -2368,6 +2395,9 @@ static int create_ctx(vmr_ctx** out, hipDeviceProp_t* prop, int device, int L, i
   Geo& g = h->g;
   g.L = L; g.N = N; g.M = M; g.K = K; g.mut = mutuality ? 1 : 0; g.eps = eps;
   g.gen = K > KMAX ? 1 : 0; g.wide = 0;   // (wide entries: decided once the largest count is known)
+  read_opts(h->opt);
+  g.dbg = h->opt.debug;
+  g.det = h->opt.deterministic ? 1 : 0; g.det_sh = 0; g.det_shr = 0;   // sorted report lists unless the older step layout is asked for
   std::string err;
   if (choose_geo(g, prop->multiProcessorCount, err, lists_only) != VMR_OK) return fail(nullptr, VMR_EINVAL, err.c_str());
   memset(h->prof_ms, 0, sizeof h->prof_ms); memset(h->prof_n, 0, sizeof h->prof_n);
@@ -2376,9 +2406,7 @@ static int create_ctx(vmr_ctx** out, hipDeviceProp_t* prop, int device, int L, i
   CK(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
   CK(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
   h->ncu = prop->multiProcessorCount;
-  h->serial = getenv("VMR_SERIAL") != nullptr;
-  h->use_graphs = getenv("VMR_GRAPH") ? atoi(getenv("VMR_GRAPH")) != 0 : false;   // (off by default: see vmr_ctx::graphs)
-  { const char* dv = getenv("VMR_DETERMINISTIC"); g.det = (dv && atoi(dv) != 0) ? 1 : 0; g.det_sh = 0; g.det_shr = 0; }   // sorted report lists unless the older step layout is asked for
+  h->use_graphs = h->opt.graph;   // (off by default: see vmr_ctx::graphs)
   const size_t rows = (size_t)L * N * N;
   CK(hipMalloc(&h->cov, rows));
   CK(hipMalloc(&h->rcls, rows));
@@ -2437,7 +2465,7 @@ static int mask_lists_from_words(vmr_ctx* h) {
   Geo& g = h->g;
   const int L = g.L, K = g.K;
   const size_t T = (size_t)g.N * g.N, n = T + 1, rows = (size_t)L * T;
-  if (!(h->n_partial > 0) || getenv("VMR_NO_RLISTS")) return VMR_OK;
+  if (!(h->n_partial > 0) || h->opt.no_rlists) return VMR_OK;
   unsigned long long* tot_dev = nullptr;
   unsigned* max_dev = nullptr;
   unsigned* bsum = nullptr;
@@ -2519,11 +2547,6 @@ static int build_far_lists(vmr_ctx* h) {
   CK(hipStreamSynchronize(h->stream));
   unsigned long long far = 0;
   for (int y = std::min(g.hc, 64); y < 65; ++y) far += hist[y];   // (an upper bound: empty slots of a level count too)
-  if (getenv("VMR_VERBOSE")) {
-    fprintf(stderr, "vimure_hip: far lists from level %d; reports per level:", g.hc);
-    for (int y = 0; y < 65; ++y) if (hist[y]) fprintf(stderr, " %d:%llu", y, hist[y]);
-    fprintf(stderr, "\n");
-  }
   CK(hipMalloc(&h->far_pos, (size_t)(far + 64) * 4));
   CK(hipMalloc(&h->far_ent, (size_t)(far + 64) * 4));
   h->far_off.assign(g.L + 1, 0ull);
@@ -2591,7 +2614,7 @@ static int create_tail(vmr_ctx* h, const hipDeviceProp_t& prop) {
   const int L = g.L, K = g.K;
   g.ml = (h->sparse && h->rq) ? 1 : 0;
   // (the self-reporter mask of survey data: lists of two; the general kernels take it on wide handles only, Mp > 8192)
-  if (g.ml && (!g.gen || g.Mp > 8192) && h->rm_maxrow <= 2 && !getenv("VMR_NO_RM2")) {
+  if (g.ml && (!g.gen || g.Mp > 8192) && h->rm_maxrow <= 2 && !h->opt.no_rm2) {
     const size_t T_ = (size_t)g.N * g.N, NS_ = (T_ + 63) / 64, n_ = (size_t)L * NS_ * 64;
     CK(hipMalloc(&h->rm2, n_ * 4));
     hipLaunchKernelGGL(k_rm2, dim3((unsigned)std::min<size_t>(4096, (n_ + 255) / 256)), dim3(256), 0, h->stream, h->perm, h->rq, h->Rm, h->rbase, h->rm2, T_, NS_, L);
@@ -2632,8 +2655,8 @@ static int create_tail(vmr_ctx* h, const hipDeviceProp_t& prop) {
     // Sorted lists: the populous levels of F (read) and H (float atomics) in LDS, shared by all waves of a workgroup; no per-wave
     // LDS at all.  One pass per sweep when every level of both fits at >= 16 waves per CU (or the levels beyond hold under 0.1 %
     // of the reports), else the rho pass keeps F and a statistics pass rebuilds H (two passes over the entries).
-    auto env_i = [](const char* n, int dflt) { const char* e = getenv(n); return e ? atoi(e) : dflt; };
-    const int want = std::max(1, std::min(g.Y, env_i("VMR_LEVELS", 64)));   // as many levels as fit: with all of them in LDS nothing is "far"
+    const VmrOpts& o = h->opt;
+    const int want = std::max(1, std::min(g.Y, o.levels));   // as many levels as fit: with all of them in LDS nothing is "far"
     // a variant's largest workgroup / waves per CU (registers): the statistics-only variant is lighter than the update's
     auto cap_of = [&](bool upd) { return sl_tpb_max(K, false, h->all_full != 0, upd); };
     auto wcu_of = [&](bool upd) { return 4 * sl_wpe(K, false, h->all_full != 0, upd); };
@@ -2677,11 +2700,11 @@ static int create_tail(vmr_ctx* h, const hipDeviceProp_t& prop) {
         // to the front of every tie's list (k_far_first).  Measured on a BASELINE config-5 layer: 3.44 ms per sweep against 3.53
         // with two passes, and ELBO sweeps the other way round -- no gain over ten sweeps, so two passes stay.
         // Not in the deterministic mode (its sums are the integer shadows').
-        if (g.mut && !g.det && env_i("VMR_FARL", 0) && (double)far <= 0.125 * (double)tot) want_farl = true;
+        if (g.mut && !g.det && o.farl && (double)far <= 0.125 * (double)tot) want_farl = true;
         else one = false;
       }
     }
-    if (getenv("VMR_TWO_PASS")) one = one && !env_i("VMR_TWO_PASS", 0);
+    one = one && !o.two_pass;
     if (one) { g.yt = g.hc = lv1; h->sp_tpb = h->st_tpb = t1; g.farl = want_farl ? 1 : 0; }
     else {
       g.two_pass = 1;
@@ -2694,19 +2717,19 @@ static int create_tail(vmr_ctx* h, const hipDeviceProp_t& prop) {
       for (int* t : {&h->sp_tpb, &h->st_tpb})
         while (*t > 64 && NS * L < (long long)h->ncu * (*t / 64)) *t = std::max(64, (*t / 2) & ~63);   // (768 -> 384 -> 192 -> 64)
     }
-    g.yt = std::max(0, std::min(g.Y, env_i("VMR_YT", g.yt)));
-    g.hc = std::max(0, std::min(g.Y, env_i("VMR_HC", g.hc)));
-    { const int t = env_i("VMR_TPB", h->sp_tpb); if (t >= 64 && t <= 1024 && t % 64 == 0) h->sp_tpb = t; }
-    { const int t = env_i("VMR_ST_TPB", h->st_tpb); if (t >= 64 && t <= 1024 && t % 64 == 0) h->st_tpb = t; }
+    g.yt = std::max(0, std::min(g.Y, o.yt >= 0 ? o.yt : g.yt));
+    g.hc = std::max(0, std::min(g.Y, o.hc >= 0 ? o.hc : g.hc));
+    if (o.tpb >= 64 && o.tpb <= 1024 && o.tpb % 64 == 0) h->sp_tpb = o.tpb;
+    if (o.st_tpb >= 64 && o.st_tpb <= 1024 && o.st_tpb % 64 == 0) h->st_tpb = o.st_tpb;
     for (int v = 0; v < 4; ++v) need = std::max(need, sl_shape(h, v != 3, v == 1 || v == 2, v == 0 || v == 1 || v == 3).smem);
-    if (g.two_pass && g.mut && !g.det && g.Y > 1 && !getenv("VMR_NO_LEVEL0")) {
+    if (g.two_pass && g.mut && !g.det && g.Y > 1 && !o.no_level0) {
       // Two passes (a wide reporter dimension): the statistics pass is bound by its LDS adds, and at mirror count 0 -- more than half
       // of the reports of a mutual network -- none is needed (SlArgs::h0s): every tie's reports of count >= 1 go first, sy's high half
       // gets the first round of a step that holds level 0 only.
       const size_t T_ = (size_t)g.N * g.N, NS_ = (T_ + 63) / 64;
       std::vector<unsigned long long> eb(L);
       CK(hipMemcpy(eb.data(), h->ebase, (size_t)L * 8, hipMemcpyDeviceToHost));
-      if (!getenv("VMR_NO_X0")) CK(hipMalloc(&h->x0p, (size_t)L * NS_ * 64 * 4));
+      if (!o.no_x0) CK(hipMalloc(&h->x0p, (size_t)L * NS_ * 64 * 4));
       for (int l = 0; l < L; ++l)
         hipLaunchKernelGGL(k_far_first, dim3((unsigned)std::min<size_t>(8192, (NS_ + 3) / 4)), dim3(256), 0, h->stream, h->E + eb[l], h->rs + (size_t)l * (NS_ + 1),
                            h->sy + (size_t)l * NS_, NS_, (unsigned)g.Mp, h->x0p ? h->x0p + (size_t)l * NS_ * 64 : nullptr);
@@ -2835,8 +2858,7 @@ static int create_dense(vmr_ctx* h, const hipDeviceProp_t& prop, const uint8_t* 
   int rc = create_state(h, &xm);
   if (rc) return rc;
   // ---- data format: report lists unless X is dense enough that 1 B per (tie, reporter) is less to read ----
-  const char* fmt = getenv("VMR_FORMAT");   // "dense", "sparse" or unset/"auto"
-  const bool force_dense = fmt && !strcmp(fmt, "dense"), force_sparse = fmt && !strcmp(fmt, "sparse");
+  const bool force_dense = h->opt.format == 1, force_sparse = h->opt.format == 2;
   // 13-bit reporter field; the sorted lists hold counts <= 2047 and (max count + 1) * Mp <= 2^20 table rows, the step layout counts <= 63
   const bool packed_ok = g.Mp <= 8192 && xm <= SL_XMAX && (size_t)(xm + 1) * g.Mp <= SL_YM_ROWS;
   // beyond KMAX categories there is no dense-tile kernel: the general kernels run on report lists, with wide entries where the
@@ -2893,7 +2915,7 @@ static int create_dense(vmr_ctx* h, const hipDeviceProp_t& prop, const uint8_t* 
         if (!rc) rc = sl_finish(h);
       }
       if (!rc) rc = mask_lists_from_words(h);
-      if (!rc && !getenv("VMR_KEEP_X")) { CK(hipFree(h->X)); h->X = nullptr; }   // the lists replace the dense tensor
+      if (!rc) { CK(hipFree(h->X)); h->X = nullptr; }   // the lists replace the dense tensor
     }
     CK(hipFree(rp));
     if (rc) return rc;
@@ -3190,7 +3212,7 @@ static int create_coo(vmr_ctx* h, const hipDeviceProp_t& prop, long long nx, con
   // only, whose pass walks the lists from global memory) takes them whatever Mp K.
   if (nr >= 0 && h->n_partial > 0) {
     const double list_bytes = 2.0 * (double)nr + 4.0 * (double)rows, word_bytes = (double)h->n_partial * g.W * 8.0;
-    const bool lists = !getenv("VMR_NO_RLISTS") && maxrow <= 64 && (list_bytes * 4.0 <= word_bytes || g.N <= 1024) &&
+    const bool lists = !h->opt.no_rlists && maxrow <= 64 && (list_bytes * 4.0 <= word_bytes || g.N <= 1024) &&
                        (g.Mp > 8192 || (size_t)g.Mp * K * 8 <= 160 * 1024);
     {
       size_t fr = 0, tot = 0;
@@ -3360,7 +3382,7 @@ int vmr_set_state(vmr_handle h, const double* gamma_shp, const double* gamma_rte
     int nf = 1;
     HIPCHK(h, hipMemcpyAsync(&nf, flag, 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->lp0 = nf == 0 && !getenv("VMR_NO_LP0");
+    h->lp0 = nf == 0 && !h->opt.no_lp0;
   } else {
     if (!pr_rho_on_device) {
       // stage through logpr (overwritten by k_init_rho element-wise after being read)
@@ -3457,7 +3479,7 @@ int vmr_step(vmr_handle h, int n_iters, double* elbo_out) {
   if (h->restored) return fail(h, VMR_ESTATE, "vmr_step after vmr_restore: the restored state is read-only until the next vmr_set_state");
   if (n_iters < 0) return fail(h, VMR_EINVAL, "n_iters < 0");
   // (VMR_DEBUG_LAZY_RHO=1, diagnostics / tests: leave even the call's last rho unwritten, so that every reader goes through ensure_rho)
-  return step_n(h, n_iters, elbo_out, getenv("VMR_DEBUG_LAZY_RHO") == nullptr);
+  return step_n(h, n_iters, elbo_out, !h->opt.debug_lazy_rho);
 }
 static int step_n(vmr_ctx* h, int n_iters, double* elbo_out, bool store_last) {
   HIPCHK(h, hipSetDevice(h->device));
@@ -3546,7 +3568,7 @@ static bool batch_steady(const vmr_ctx* h) {
 static bool batch_kind(const vmr_ctx* h, const vmr_ctx* h0) {
   // (a sweep of such a handle is k_fin_gamma + the pass, + k_fin_rho with an ELBO: the pass sums rho over the mask itself)
   return h->sparse && !h->g.gen && !h->g.two_pass && !h->g.farl && !h->g.det && !h->prof && h->g.fuse_full && (h->n_partial == 0 || h->g.ml) && h->device == h0->device &&
-         h->g.K == h0->g.K && h->g.mut == h0->g.mut && (h->all_full != 0) == (h0->all_full != 0);
+         h->g.K == h0->g.K && h->g.mut == h0->g.mut && (h->all_full != 0) == (h0->all_full != 0) && !memcmp(&h->opt, &h0->opt, sizeof h->opt);
 }
 namespace {
 struct BatchTables {   // device copies of the unit tables of one lockstep loop
@@ -3568,14 +3590,13 @@ static int batch_tables(vmr_ctx* const* hs, const std::vector<int>& act, int n_a
   for (int u : act) steps += (((long long)hs[u]->g.N * hs[u]->g.N + 63) / 64) * hs[u]->g.L;
   std::vector<FinUnit> fu(act.size());
   std::vector<int> gmap, rmap;
-  const long long per_cap = getenv("VMR_BATCH_PER") ? atoll(getenv("VMR_BATCH_PER")) : 64;   // (experiments)
   for (int m = 0; m < 3; ++m) {
     const int tpb = sl_tpb_max_b(K, m == 1, allfull), nw = tpb / 64;
     // steps per wave: about one workgroup per CU in all (the tables in LDS allow few more, and a second round of workgroups
     // costs a workgroup's fixed part -- its tables, its share of nu: some ten steps' worth -- again), at least 4 steps each, at
     // most 64 (192 fits of N = 200..800, lockstep loops: cap 8 1.05 s, 16 0.88, 32 0.78, 64 0.72, none 0.96 -- a small unit
     // then is one workgroup that walks all its steps)
-    long long per = std::max<long long>(4, std::min<long long>(per_cap, (steps + (long long)nw * h0->ncu - 1) / ((long long)nw * h0->ncu)));
+    long long per = std::max<long long>(4, std::min<long long>(64, (steps + (long long)nw * h0->ncu - 1) / ((long long)nw * h0->ncu)));
     {
       // ... but never a FEW workgroups more than are resident at once: every workgroup of the launch gets the largest unit's LDS
       // (a village of N = 900: 130 KB, one workgroup per CU), and with 293 workgroups on 256 CUs the launch takes two rounds for
@@ -3589,7 +3610,7 @@ static int batch_tables(vmr_ctx* const* hs, const std::vector<int>& act, int n_a
         for (int u : act) { const Geo& g = hs[u]->g; const long long NS = ((long long)g.N * g.N + 63) / 64; t += (long long)g.L * ((NS + nw * p_ - 1) / (nw * p_)); }
         return t;
       };
-      if (total(per) > cap_wgs && !getenv("VMR_BATCH_PER")) {
+      if (total(per) > cap_wgs) {
         long long p2 = per;
         while (p2 < 512 && total(p2) > cap_wgs) p2 += std::max<long long>(1, p2 / 16);
         if (total(p2) <= cap_wgs) per = p2;
@@ -3621,7 +3642,7 @@ static int batch_tables(vmr_ctx* const* hs, const std::vector<int>& act, int n_a
     long long layers = 0;
     for (int u : act) layers += hs[u]->g.L;
     bt.fg = (int)std::max<long long>(2, std::min<long long>(FG_G, (1LL * h0->ncu) / std::max<long long>(1, layers)));   // (64 units: 4 -- measured 1 / 2 / 4 / 8 / 16: 3.29 / 3.06 / 2.95 / 3.11 / 3.33 s of loops)
-    if (getenv("VMR_BATCH_FG")) bt.fg = std::max(1, std::min(FG_G, atoi(getenv("VMR_BATCH_FG"))));   // (experiments)
+    if (h0->opt.batch_fg) bt.fg = h0->opt.batch_fg;   // (experiments)
   }
   for (size_t i = 0; i < act.size(); ++i) {
     vmr_ctx* h = hs[act[i]];
@@ -3732,7 +3753,7 @@ int vmr_fit_loop_batch(vmr_handle* hs, int n, int max_iter, double tol, int deci
   std::vector<double> be_host((size_t)n * 8);
   int rc = batch_tables(hs, act, n, bt, st);
   if (rc) return rc;
-  const bool lazy_rho = !getenv("VMR_ALWAYS_STORE_RHO");   // plain sweeps do not write rho: the ELBO sweep every loop ends with does
+  const bool lazy_rho = !h0->opt.always_store_rho;   // plain sweeps do not write rho: the ELBO sweep every loop ends with does
   auto launch_sweeps = [&](int mode) -> int {
     hipLaunchKernelGGL(k_fin_gamma_b, dim3(bt.ngb), dim3(FIN_TPB), bt.fsm, st, bt.fu, bt.gmap, bt.fg);
     const int pm = (mode == 0 && lazy_rho) ? 4 : mode;

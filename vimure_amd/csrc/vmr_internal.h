@@ -56,8 +56,7 @@ struct Geo {
   int two_pass; // wide reporter dimension: the LDS levels do not fit beside the rho pass' tables, so H is rebuilt by
                 // k_hist after the rho pass (two passes over X per sweep instead of one)
   int pf;       // 16-B chunks of a tile pair each thread stages (prefetch depth)
-  int heavy;    // a lane's share of a row with more non-zeros than this is processed by the whole wave
-  int dbg;      // timing experiments only (env VMR_DEBUG; results are wrong): dense path 1 = skip per-report math, 2 = skip
+  int dbg;      // timing experiments only (VmrOpts::debug; results are wrong): dense path 1 = skip per-report math, 2 = skip
                 // the scan; report lists 8 = no H flush, 16 = no walk 1, 32 = no walk 2, 64 = no exp in the tie update
   double eps;
   int det;      // VMR_DETERMINISTIC=1: bit-reproducible sweeps (one wave per workgroup, fixed step shares, integer cross-workgroup sums)
@@ -77,8 +76,28 @@ __device__ __forceinline__ double det_back(unsigned long long u, int sh) { retur
 
 #define NSLOT 8   // accumulation slots per layer for cross-workgroup sums (global f64 atomics)
 
+// The VMR_* environment switches (INTEGRATION.md §3 has the table), read by read_opts -- the only place that reads the
+// environment -- once per handle, in create_ctx: a handle keeps the settings it was created under.  bools: set at all; ints: atoi,
+// 0 when unset unless noted.
+struct VmrOpts {
+  int format;                  // VMR_FORMAT: 1 "dense", 2 "sparse", 0 otherwise (the automatic choice)
+  bool deterministic, graph;   // VMR_DETERMINISTIC, VMR_GRAPH: atoi != 0
+  int debug, levels;           // VMR_DEBUG -> Geo::dbg; VMR_LEVELS (64 when unset)
+  int two_pass, farl;          // VMR_TWO_PASS, VMR_FARL
+  int yt, hc;                  // VMR_YT, VMR_HC: max(0, atoi), -1 when unset
+  int tpb, st_tpb;             // VMR_TPB, VMR_ST_TPB: taken when a multiple of 64 in [64, 1024]
+  bool no_level0, no_x0, no_lv0r, no_level_sort, no_rlists, no_rm2, no_lp0;   // VMR_NO_*
+  bool always_store_rho, debug_lazy_rho;   // VMR_ALWAYS_STORE_RHO, VMR_DEBUG_LAZY_RHO
+  int gen_hsum;                // VMR_GEN_HSUM: taken when > 0
+  bool gen_no_lds_h;           // VMR_GEN_NO_LDS_H
+  int gen_dbg;                 // VMR_GEN_DBG (-DGEN_DEBUG builds)
+  int batch_fg;                // VMR_BATCH_FG: clamped to [1, FG_G], 0 when unset
+  char debug_times[256];       // VMR_DEBUG_TIMES (-DSL_DEBUG builds): "" when unset
+};
+
 struct vmr_ctx {
   Geo g;
+  VmrOpts opt;
   int device;
   hipStream_t stream;
   hipStream_t stream2 = nullptr;     // the mask half of the gamma update runs beside the counts half
@@ -169,7 +188,6 @@ struct vmr_ctx {
   double* nu_acc = nullptr;    // [2 + L] the nu update inside the sweep (SlArgs::nu_acc)
   double* lutg = nullptr;      // wide masks (W > 4): the nibble LUT of E[theta] lives in global memory [L][W*256]
   bool have_priors = false, have_state = false;
-  bool serial = false;
   int ncu = 256;
   std::vector<std::pair<const void*, int>> occ;   // kernel -> resident workgroups per CU   // a rho sub-step left an unconsumed nu partial in slotR
   // profiling
