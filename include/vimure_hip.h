@@ -70,9 +70,10 @@ enum {
  *   eps: the EPS white-noise constant (model.py:215-218), normally 1e-12.
  * The handle is reusable across realisations and seeds (vmr_set_state restarts it).
  * Environment, read here: VMR_DETERMINISTIC=1 makes the handle's sweeps bit-reproducible run to run (the reference's
- * single-threaded NumPy, model.py:623-660, is): cross-workgroup sums as 64-bit integers in fixed point, one wave per workgroup
- * with a fixed share of the work; report lists only (VMR_EINVAL otherwise), about a fifth of the default speed, vmr_sub_step
- * returns VMR_ESTATE.
+ * single-threaded NumPy, model.py:623-660, is): every sum whose order varies from run to run is a 64-bit integer sum in fixed
+ * point.  It covers every handle on report lists, the specialised kernels (K <= 8, packed entries) and the general ones (any K,
+ * two-word entries) alike; handles on dense tiles return VMR_EINVAL, and vmr_sub_step returns VMR_ESTATE on such a handle.
+ * Cost: DESIGN.md §3c.
  */
 int vmr_create(vmr_handle* out, int device, int L, int N, int M, int K, int mutuality,
                const uint8_t* X, const uint8_t* R, int data_on_device, double eps);
@@ -90,7 +91,8 @@ int vmr_create(vmr_handle* out, int device, int L, int N, int M, int K, int mutu
  * mask lists hold 16-bit reporters); L N^2 2^mb < 2^64 with mb = max(13, ceil(log2 Mp)) reporter bits of the 64-bit sort keys
  * (Mp: M rounded up to 16); (largest count + 1) * Mp < 2^32; fewer than 2^31 coordinates per list, fewer than 2^31 ties and
  * fewer than 2^32 entry slots per layer.  M <= 8192 with (largest count + 1) * M <= 2^20 and K <= 8 runs the specialised
- * kernels; beyond that the general ones (wider M: reporter tables read through L2).
+ * kernels; beyond that the general ones (wider M: reporter tables read through L2).  VMR_DETERMINISTIC=1 (see vmr_create) covers
+ * every handle this function creates, whichever kernels it runs.
  */
 int vmr_create_coo(vmr_handle* out, int device, int L, int N, int M, int K, int mutuality,
                    int64_t nx, const int32_t* xl, const int32_t* xi, const int32_t* xj, const int32_t* xm, const int32_t* xv,

@@ -11,7 +11,38 @@
 // A tie is spread over G = min(64, 2^ceil(log2 K)) lanes, one category per lane (NCH = ceil(K / 64) per lane beyond 64): the sum
 // over categories that normalises rho and the ELBO's inner sums are shuffles inside the group, the adds into H land on K
 // consecutive doubles.  The factor of a report, F = (E log theta_m + E log lambda_k) w1_k(m, y), is computed where it is used.
+//
+// DET (VMR_DETERMINISTIC=1, Geo::det): every sum whose order varies from run to run -- which workgroup draws which
+// step, which atomic lands first -- is an integer sum in fixed point, in the same cells: H (LDS rows and Hg), slotA, slotF and slotR
+// hold 64-bit integers in this mode, and gen_s1 does between the finalize kernels.  The readers convert them (det_back).  Sums of
+// one thread over a fixed share, and the shuffle / block trees, are already the same every run.
 #include "sweep_gen.h"
+
+// v 2^sh rounded to nearest as a 64-bit integer through the 1.5 * 2^52 trick: |v| scale < 2^51 (the host caps det_sh by the largest count)
+__device__ __forceinline__ unsigned long long gen_fxm(double v, double scale) {
+  return (unsigned long long)(__double_as_longlong(fma(v, scale, 6755399441055744.0)) - 0x4338000000000000ll);
+}
+// DET: a lane's integer sums and the scales of the fixed point; nothing at all in the default variants (whose code stays as it was)
+template <int NCH, bool DET> struct GenDet {
+  unsigned long long lin = 0ull, q = 0ull, log = 0ull, F[NCH] = {};
+  unsigned long long lin2 = 0ull, q2 = 0ull, log2 = 0ull;   // the ELBO partials' second words (gen_fx2)
+  double sc_h, sc_a;   // 2^det_sh (counts times rho), 2^det_sha (sums of rho)
+  __device__ explicit GenDet(const Geo& g) : sc_h(__builtin_amdgcn_ldexp(1.0, g.det_sh)), sc_a(__builtin_amdgcn_ldexp(1.0, g.det_sha)) {}
+};
+template <int NCH> struct GenDet<NCH, false> { __device__ explicit GenDet(const Geo&) {} };
+// The ELBO partials in two words: v 2^sh rounded (hi), and the remainder -- exact, at most 1/2 -- at 2^-(sh + DET_SH2) (lo).  sh is
+// bounded by the worst case of the whole sum; sums of ties that carry no report nearly cancel, and one word alone would lose them
+// step after step (-3e-4 of the ELBO on a 9000-node survey).
+__device__ __forceinline__ void gen_fx2(double v, int sh, unsigned long long& hi, unsigned long long& lo) {
+  const double t = ldexp(v, sh), h = rint(t);
+  hi += (unsigned long long)(long long)h;
+  lo += det_fx(t - h, DET_SH2);
+}
+__device__ __forceinline__ unsigned long long* as_u64(double* p) { return reinterpret_cast<unsigned long long*>(p); }
+__device__ __forceinline__ unsigned long long u64_xor_shfl(unsigned long long v, int o2) {   // (64-bit: two 32-bit shuffles)
+  const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, o2, 64), hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), o2, 64);
+  return ((unsigned long long)hi << 32) | lo;
+}
 
 struct GenArgs {
   const unsigned *E, *EX, *rs;
@@ -35,7 +66,7 @@ struct GenArgs {
 #define GEN_ON(bit) true
 #endif
 
-template <int NCH>
+template <int NCH, bool DET>
 __global__ __launch_bounds__(512) void k_sweep_gen(GenArgs a, Geo g) {
   __shared__ double red[16];
   __shared__ double s_tfull;
@@ -114,6 +145,7 @@ __global__ __launch_bounds__(512) void k_sweep_gen(GenArgs a, Geo g) {
   double accF[NCH];
 #pragma unroll
   for (int c = 0; c < NCH; ++c) accF[c] = 0.0;
+  GenDet<NCH, DET> dt(g);   // (DET: the same sums as integers -- a lane's ties depend on the steps its workgroup drew)
 
   constexpr int RB = 8;   // rounds of a step held in registers, one tie's per lane (coalesced loads), handed to the tie's lanes by shuffles
   // A step's G sub-steps (TPW ties each) are shared by sw waves of the workgroup: the longest steps (a tie with many reports: one
@@ -234,13 +266,17 @@ __global__ __launch_bounds__(512) void k_sweep_gen(GenArgs a, Geo g) {
       }
       if ((a.update || a.hist) && act && cls == 1u) {
 #pragma unroll
-        for (int c = 0; c < NCH; ++c) accF[c] += r[c];
+        for (int c = 0; c < NCH; ++c) {
+          if constexpr (DET) dt.F[c] += gen_fxm(r[c], dt.sc_a);
+          else accF[c] += r[c];
+        }
       }
       if (a.sum_a && act && cls == 2u) {
         for_reporters(tie, [&](int m) {
 #pragma unroll
           for (int c = 0; c < NCH; ++c)
-            if (kv[c]) atomicAdd(&Al[(size_t)m * K + (c * G + kk)], r[c]);
+            if constexpr (DET) { if (kv[c]) atomicAdd(as_u64(&Al[(size_t)m * K + (c * G + kk)]), gen_fxm(r[c], dt.sc_a)); }
+            else if (kv[c]) atomicAdd(&Al[(size_t)m * K + (c * G + kk)], r[c]);
         });
       }
       if (a.hist) {
@@ -250,12 +286,14 @@ __global__ __launch_bounds__(512) void k_sweep_gen(GenArgs a, Geo g) {
             if (ym < hs_rows) {   // (LDS adds)
 #pragma unroll
               for (int c = 0; c < NCH; ++c)
-                if (kv[c] && GEN_ON(1)) atomicAdd(&Hs[(size_t)ym * K + (c * G + kk)], dx * r[c]);
+                if constexpr (DET) { if (kv[c] && GEN_ON(1)) atomicAdd(as_u64(&Hs[(size_t)ym * K + (c * G + kk)]), gen_fxm(dx * r[c], dt.sc_h)); }
+                else if (kv[c] && GEN_ON(1)) atomicAdd(&Hs[(size_t)ym * K + (c * G + kk)], dx * r[c]);
             } else {
               double* hrow = Hl + (size_t)ym * K;
 #pragma unroll
               for (int c = 0; c < NCH; ++c)
-                if (kv[c] && GEN_ON(1)) atomicAdd(&hrow[c * G + kk], dx * r[c]);
+                if constexpr (DET) { if (kv[c] && GEN_ON(1)) atomicAdd(as_u64(&hrow[c * G + kk]), gen_fxm(dx * r[c], dt.sc_h)); }
+                else if (kv[c] && GEN_ON(1)) atomicAdd(&hrow[c * G + kk], dx * r[c]);
             }
           }
         });
@@ -285,10 +323,18 @@ __global__ __launch_bounds__(512) void k_sweep_gen(GenArgs a, Geo g) {
         }
       }
     }
+    if constexpr (DET) {
+      if (a.elbo) {   // (this wave's ties of the step are a fixed set, summed in a fixed order: one exact conversion per step)
+        const double v1 = wave_sum(e_lin), v2 = wave_sum(e_log), v3 = wave_sum(e_q);
+        if (lane == 0) { gen_fx2(v1, g.det_shr, dt.lin, dt.lin2); gen_fx2(v2, g.det_shr, dt.log, dt.log2); gen_fx2(v3, g.det_shr, dt.q, dt.q2); }
+        e_lin = 0.0; e_log = 0.0; e_q = 0.0;
+      }
+    }
   }
   if (hs_rows) {   // the workgroup's sums of the low rows: one global add per cell it touched
     __syncthreads();
     for (unsigned q = tid; q < hs_rows * (unsigned)K; q += blockDim.x) {
+      if constexpr (DET) { const unsigned long long iv = *as_u64(&Hs[q]); if (iv != 0ull) atomicAdd(as_u64(&Hl[q]), iv); continue; }
       const double v = Hs[q];
       if (v != 0.0) atomicAdd(&Hl[q], v);
     }
@@ -296,17 +342,35 @@ __global__ __launch_bounds__(512) void k_sweep_gen(GenArgs a, Geo g) {
   if (a.update || a.hist) {   // rho summed over the all-ones mask rows: lanes of equal category across the wave's groups
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
+      if constexpr (DET) {
+        unsigned long long v = dt.F[c];
+        for (int o2 = G; o2 < 64; o2 <<= 1) v += u64_xor_shfl(v, o2);
+        if (grp == 0 && kv[c] && v != 0ull) atomicAdd(as_u64(&a.slotF[((size_t)l * NSLOT + (gb % NSLOT)) * K + (c * G + kk)]), v);
+        continue;
+      }
       double v = accF[c];
       for (int o2 = G; o2 < 64; o2 <<= 1) v += __shfl_xor(v, o2, 64);
       if (grp == 0 && kv[c] && v != 0.0) atomicAdd(&a.slotF[((size_t)l * NSLOT + (gb % NSLOT)) * K + (c * G + kk)], v);
     }
   }
+  if constexpr (DET) {
+    if (a.elbo) {
+      // (only lane 0 holds anything: the per-step conversions).  Slots 0 .. NSLOT/2 - 1 take the first words, the others the second.
+      if (lane == 0) {
+        double* out = a.slotR + (size_t)(blockIdx.x % (NSLOT / 2)) * 4;
+        double* out2 = out + (NSLOT / 2) * 4;
+        atomicAdd(as_u64(&out[1]), dt.lin); atomicAdd(as_u64(&out[2]), dt.log); atomicAdd(as_u64(&out[3]), dt.q);
+        atomicAdd(as_u64(&out2[1]), dt.lin2); atomicAdd(as_u64(&out2[2]), dt.log2); atomicAdd(as_u64(&out2[3]), dt.q2);
+      }
+    }
+  } else {
   if (a.elbo) {
     const double v1 = wave_sum(e_lin), v2 = wave_sum(e_log), v3 = wave_sum(e_q);
     if (lane == 0) {
       double* out = a.slotR + (size_t)(blockIdx.x % NSLOT) * 4;
       atomicAdd(&out[1], v1); atomicAdd(&out[2], v2); atomicAdd(&out[3], v3);
     }
+  }
   }
 }
 
@@ -319,6 +383,9 @@ __global__ __launch_bounds__(512) void k_sweep_gen(GenArgs a, Geo g) {
 // shuffle inside the group and the groups of a wave add to different m; a lane keeps its categories' sums in registers.  (One
 // thread per cell instead costs a same-address LDS add per lane and a division per cell.)  FU rows per group are requested at once.
 // bi of nb: this workgroup's share of the rows (nb > 1: k_gen_hsum, sums in global memory); zero: the rows read are left zeroed.
+// DET: H holds integers (2^-det_sh), and so do by_m / by_k: what a group adds is converted at the same scale (w <= 1: a sum over
+// H's cells stays below the sum of all counts).
+template <bool DET>
 __device__ void h_weighted_sums(double* __restrict__ Hl, const Geo& g, const double* gth, const double* gla, double gnu,
                                 double* by_m, double* by_k, int bi = 0, int nb = 1, bool zero = false) {
   constexpr int FU = 8;
@@ -349,7 +416,8 @@ __device__ void h_weighted_sums(double* __restrict__ Hl, const Geo& g, const dou
         for (int u = 0; u < FU; ++u) {
           const size_t row = base + (size_t)u * rstep + (unsigned)r0;
           const bool on = row < rows && k < K;
-          hv[u] = on ? Hl[row * K + k] : 0.0;
+          if constexpr (DET) hv[u] = on ? det_back(*as_u64(&Hl[row * K + k]), g.det_sh) : 0.0;
+          else hv[u] = on ? Hl[row * K + k] : 0.0;
           if (zero && on) Hl[row * K + k] = 0.0;
         }
         const double gk = k < K ? gla[k] : 0.0;
@@ -360,7 +428,8 @@ __device__ void h_weighted_sums(double* __restrict__ Hl, const Geo& g, const dou
           if (hv[u] != 0.0 && m < M) v = (g.mut ? w1_of(gth[m] * gk, gnu * (double)yu[u]) : 1.0) * hv[u];
           if (by_m) {
             v = group_sum(v, G);
-            if (kk == 0 && v != 0.0) atomicAdd(&by_m[m], v);
+            if constexpr (DET) { if (kk == 0 && v != 0.0) atomicAdd(as_u64(&by_m[m]), det_fx(v, g.det_sh)); }
+            else if (kk == 0 && v != 0.0) atomicAdd(&by_m[m], v);
           } else {
             acc[c] += v;
           }
@@ -374,7 +443,8 @@ __device__ void h_weighted_sums(double* __restrict__ Hl, const Geo& g, const dou
       if (c * G < K) {
         double v = acc[c];
         for (int o2 = G; o2 < 64; o2 <<= 1) v += __shfl_xor(v, o2, 64);
-        if (grp == 0 && c * G + kk < K && v != 0.0) atomicAdd(&by_k[c * G + kk], v);
+        if constexpr (DET) { if (grp == 0 && c * G + kk < K && v != 0.0) atomicAdd(as_u64(&by_k[c * G + kk]), det_fx(v, g.det_sh)); }
+        else if (grp == 0 && c * G + kk < K && v != 0.0) atomicAdd(&by_k[c * G + kk], v);
       }
     }
   }
@@ -382,6 +452,7 @@ __device__ void h_weighted_sums(double* __restrict__ Hl, const Geo& g, const dou
 
 // Large tables (one workgroup walking a layer's H is bound by memory latency): the sums by several workgroups per layer into
 // global scratch, out[l][m] (by_k = 0, old G_theta: before k_fin_gamma_gen) or out[l][k] (by_k = 1, new G_theta: after it).
+template <bool DET>
 __global__ __launch_bounds__(1024) void k_gen_hsum(const double* __restrict__ par, double* Hg, double* out, int by_k, int zero, int nb, Geo g) {
   extern __shared__ double dyn[];   // G_lambda, K
   const int K = g.K, Mp = g.Mp, l = (int)blockIdx.x / nb, bi = (int)blockIdx.x - l * nb;
@@ -391,14 +462,16 @@ __global__ __launch_bounds__(1024) void k_gen_hsum(const double* __restrict__ pa
   double* Hl = Hg + (size_t)l * g.Y * Mp * K;
   const double* gth = par + o.G_th + (size_t)l * Mp;
   const double gnu = par[o.sc + SC_G_NU];
-  if (by_k) h_weighted_sums(Hl, g, gth, dyn, gnu, nullptr, out + (size_t)l * K, bi, nb, zero != 0);
-  else h_weighted_sums(Hl, g, gth, dyn, gnu, out + (size_t)l * Mp, nullptr, bi, nb, zero != 0);
+  if (by_k) h_weighted_sums<DET>(Hl, g, gth, dyn, gnu, nullptr, out + (size_t)l * K, bi, nb, zero != 0);
+  else h_weighted_sums<DET>(Hl, g, gth, dyn, gnu, out + (size_t)l * Mp, nullptr, bi, nb, zero != 0);
 }
 
 // One workgroup per layer.  gamma_shp[m] = alpha + sum_{y,k} w1_k(m,y) H (old parameters; model.py:698-703, 832-859),
 // gamma_rte[m] = beta + sum_k E[lambda_k] A[m,k] (model.py:704-718), then with the NEW theta: phi_rte[k] = beta + sum_m E[theta_m] A[m,k]
 // (model.py:742-749) and phi_shp[k] = alpha + sum_{m,y} w1_k(m,y) H (model.py:731-733, 861-887); A[m,k] = the pass' sums of rho over
 // the mask rows holding m (all-ones rows: slotF).  consume: H, slotF are left zeroed for the next pass; slotA always is.
+// DET: slotF / slotA / s1 / pss hold integers (sweep_gen.hip's head); prs is added wave by wave, in order.
+template <bool DET>
 __global__ __launch_bounds__(1024) void k_fin_gamma_gen(double* par, double* Hg, double* slotA, double* slotF, double* s1g, int s1_lds, int ext, int do_phi, int consume, Geo g) {
   extern __shared__ double dyn[];   // fk | ela_old | gla_old | prs | pss, K each; then (s1_lds) s1[Mp]
   const int K = g.K, Mp = g.Mp, M = g.M, l = blockIdx.x, tid = threadIdx.x, nthr = (int)blockDim.x, Wp = g.W * 64;
@@ -407,7 +480,13 @@ __global__ __launch_bounds__(1024) void k_fin_gamma_gen(double* par, double* Hg,
   double* s1 = s1_lds ? dyn + 5 * K : s1g + (size_t)l * Mp;   // (LDS while the reporters fit: the sums are then LDS adds)
   for (int k = tid; k < K; k += nthr) {
     double f = 0.0;
-    for (int sl = 0; sl < NSLOT; ++sl) f += slotF[((size_t)l * NSLOT + sl) * K + k];
+    if constexpr (DET) {
+      unsigned long long fi = 0ull;
+      for (int sl = 0; sl < NSLOT; ++sl) fi += *as_u64(&slotF[((size_t)l * NSLOT + sl) * K + k]);
+      f = det_back(fi, g.det_sha);
+    } else {
+      for (int sl = 0; sl < NSLOT; ++sl) f += slotF[((size_t)l * NSLOT + sl) * K + k];
+    }
     fk[k] = f;
     ela_old[k] = par[o.p_shp + l * K + k] / par[o.p_rte + l * K + k];
     gla_old[k] = par[o.G_la + l * K + k];
@@ -418,6 +497,12 @@ __global__ __launch_bounds__(1024) void k_fin_gamma_gen(double* par, double* Hg,
   double* A0 = slotA ? slotA + (size_t)l * NSLOT * Wp * K : nullptr;
   if (A0) {
     for (size_t q = tid; q < (size_t)M * K; q += nthr) {
+      if constexpr (DET) {   // (the integer sum of the slots, converted: slot 0 holds a double from here on)
+        unsigned long long iv = *as_u64(&A0[q]);
+        for (int sl = 1; sl < NSLOT; ++sl) { iv += *as_u64(&A0[(size_t)sl * Wp * K + q]); A0[(size_t)sl * Wp * K + q] = 0.0; }
+        A0[q] = det_back(iv, g.det_sha);
+        continue;
+      }
       double v = A0[q];
       for (int sl = 1; sl < NSLOT; ++sl) { v += A0[(size_t)sl * Wp * K + q]; A0[(size_t)sl * Wp * K + q] = 0.0; }
       A0[q] = v;
@@ -429,7 +514,7 @@ __global__ __launch_bounds__(1024) void k_fin_gamma_gen(double* par, double* Hg,
   const size_t hcs = (size_t)g.Y * Mp * K;
   double* Hl = Hg + (size_t)l * hcs;
   double* gth = par + o.G_th + (size_t)l * Mp;
-  if (!ext) h_weighted_sums(Hl, g, gth, gla_old, gnu, s1, nullptr);
+  if (!ext) h_weighted_sums<DET>(Hl, g, gth, gla_old, gnu, s1, nullptr);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   // no partial mask rows (A0 null): every reporter's rate sum is the same sum_k E[lambda_k] F_k, and phi's is F_k sum_m E[theta_m]
@@ -444,7 +529,9 @@ __global__ __launch_bounds__(1024) void k_fin_gamma_gen(double* par, double* Hg,
   }
   auto finish_m = [&](int m, double rsum, bool write) -> double {   // gamma of reporter m from its two sums; returns E[theta_m]
     const size_t q = (size_t)l * Mp + m;
-    const double shp = par[o.a_th + q] + ((s1_lds || ext) ? s1[m] : atomicAdd(&s1[m], 0.0));   // (global, this kernel's own adds: a device-scope read of what the atomics left at the memory side)
+    double shp;
+    if constexpr (DET) shp = par[o.a_th + q] + det_back((s1_lds || ext) ? *as_u64(&s1[m]) : atomicAdd(as_u64(&s1[m]), 0ull), g.det_sh);
+    else shp = par[o.a_th + q] + ((s1_lds || ext) ? s1[m] : atomicAdd(&s1[m], 0.0));   // (global, this kernel's own adds: a device-scope read of what the atomics left at the memory side)
     const double rte = par[o.b_th + q] + rsum;
     const double e = shp / rte, lg = digamma_pos(shp) - log(rte);
     if (write) {
@@ -495,7 +582,14 @@ __global__ __launch_bounds__(1024) void k_fin_gamma_gen(double* par, double* Hg,
       if (c * G < K) {
         double v = acc[c];
         for (int o2 = G; o2 < 64; o2 <<= 1) v += __shfl_xor(v, o2, 64);
+        if constexpr (DET) {   // (one wave at a time, in order: the sums are not counts, no fixed point fits them)
+          for (int w = 0; w < nwv; ++w) {
+            if (wv == w && grp == 0 && c * G + kk < K) prs[c * G + kk] += v;
+            __syncthreads();
+          }
+        } else {
         if (grp == 0 && c * G + kk < K) atomicAdd(&prs[c * G + kk], v);
+        }
       }
     }
   }
@@ -509,7 +603,7 @@ __global__ __launch_bounds__(1024) void k_fin_gamma_gen(double* par, double* Hg,
     return;
   }
   if ((do_phi && g.mut) || !g.mut) {
-    h_weighted_sums(Hl, g, gth, gla_old, gnu, nullptr, pss);
+    h_weighted_sums<DET>(Hl, g, gth, gla_old, gnu, nullptr, pss);
   }
   __syncthreads();
   for (int k = tid; k < K; k += nthr) {
@@ -518,7 +612,9 @@ __global__ __launch_bounds__(1024) void k_fin_gamma_gen(double* par, double* Hg,
     if (g.mut && !do_phi) {
       par[o.p_rte_pend + q] = rte;   // the PHI sub-step commits (k_fin_phi_gen)
     } else {
-      const double shp = par[o.a_la + q] + pss[k];
+      double shp;
+      if constexpr (DET) shp = par[o.a_la + q] + det_back(*as_u64(&pss[k]), g.det_sh);
+      else shp = par[o.a_la + q] + pss[k];
       par[o.p_shp + q] = shp; par[o.p_rte + q] = rte;
       if (g.mut) par[o.p_rte_pend + q] = rte;
       const double lg = digamma_pos(shp) - log(rte);
@@ -531,7 +627,8 @@ __global__ __launch_bounds__(1024) void k_fin_gamma_gen(double* par, double* Hg,
   }
 }
 
-// s2g != null: the sums come from k_gen_hsum (and are zeroed here for the next one).
+// s2g != null: the sums come from k_gen_hsum (and are zeroed here for the next one).  DET: they and pss hold integers.
+template <bool DET>
 __global__ __launch_bounds__(1024) void k_fin_phi_gen(double* par, double* Hg, double* s2g, Geo g) {
   extern __shared__ double dyn[];   // gla_old | pss, K each
   const int K = g.K, Mp = g.Mp, M = g.M, l = blockIdx.x, tid = threadIdx.x, nthr = (int)blockDim.x;
@@ -544,14 +641,18 @@ __global__ __launch_bounds__(1024) void k_fin_phi_gen(double* par, double* Hg, d
   double* Hl = Hg + (size_t)l * hcs;
   const double* gth = par + o.G_th + (size_t)l * Mp;   // new
   if (s2g) {
-    for (int k = tid; k < K; k += nthr) { pss[k] = s2g[l * K + k]; s2g[l * K + k] = 0.0; }
+    for (int k = tid; k < K; k += nthr) {
+      if constexpr (DET) *as_u64(&pss[k]) = *as_u64(&s2g[l * K + k]);
+      else pss[k] = s2g[l * K + k];
+      s2g[l * K + k] = 0.0;
+    }
   } else {
-    h_weighted_sums(Hl, g, gth, gla_old, gnu, nullptr, pss);
+    h_weighted_sums<DET>(Hl, g, gth, gla_old, gnu, nullptr, pss);
   }
   __syncthreads();
   for (int k = tid; k < K; k += nthr) {
     const int q = l * K + k;
-    const double shp = par[o.a_la + q] + pss[k], rte = par[o.p_rte_pend + q];
+    const double shp = DET ? par[o.a_la + q] + det_back(*as_u64(&pss[k]), g.det_sh) : par[o.a_la + q] + pss[k], rte = par[o.p_rte_pend + q];
     par[o.p_shp + q] = shp; par[o.p_rte + q] = rte;
     const double lg = digamma_pos(shp) - log(rte);
     par[o.E_la + q] = shp / rte; par[o.l_la + q] = lg; par[o.G_la + q] = exp(lg);
@@ -590,6 +691,17 @@ __global__ __launch_bounds__(64) void k_sample_gen(const double* __restrict__ rh
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
+template <bool DET>
+static int gen_launch_pass(vmr_ctx* h, const GenArgs& a, dim3 grid, dim3 blk, size_t sm) {
+  const Geo& g = h->g;
+  const void* fn = g.K <= 64 ? reinterpret_cast<const void*>(k_sweep_gen<1, DET>) : g.K <= 128 ? reinterpret_cast<const void*>(k_sweep_gen<2, DET>) : reinterpret_cast<const void*>(k_sweep_gen<4, DET>);
+  if (sm > 48 * 1024) HIPCHK(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
+  if (g.K <= 64) hipLaunchKernelGGL((k_sweep_gen<1, DET>), grid, blk, sm, h->stream, a, g);
+  else if (g.K <= 128) hipLaunchKernelGGL((k_sweep_gen<2, DET>), grid, blk, sm, h->stream, a, g);
+  else hipLaunchKernelGGL((k_sweep_gen<4, DET>), grid, blk, sm, h->stream, a, g);
+  HIPCHK(h, hipGetLastError());
+  return VMR_OK;
+}
 static int gen_pass(vmr_ctx* h, int update, int elbo, int hist, int sum_a) {
   const Geo& g = h->g;
   const long long NS = ((long long)g.N * g.N + 63) / 64;
@@ -616,13 +728,7 @@ static int gen_pass(vmr_ctx* h, int update, int elbo, int hist, int sum_a) {
     if (h->opt.gen_no_lds_h) a.YL = 0;
     sm += (size_t)a.YL * row;
   }
-  const void* fn = g.K <= 64 ? reinterpret_cast<const void*>(k_sweep_gen<1>) : g.K <= 128 ? reinterpret_cast<const void*>(k_sweep_gen<2>) : reinterpret_cast<const void*>(k_sweep_gen<4>);
-  if (sm > 48 * 1024) HIPCHK(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
-  if (g.K <= 64) hipLaunchKernelGGL(k_sweep_gen<1>, grid, blk, sm, h->stream, a, g);
-  else if (g.K <= 128) hipLaunchKernelGGL(k_sweep_gen<2>, grid, blk, sm, h->stream, a, g);
-  else hipLaunchKernelGGL(k_sweep_gen<4>, grid, blk, sm, h->stream, a, g);
-  HIPCHK(h, hipGetLastError());
-  return VMR_OK;
+  return g.det ? gen_launch_pass<true>(h, a, grid, blk, sm) : gen_launch_pass<false>(h, a, grid, blk, sm);   // (DET: the integer-sum variants)
 }
 static size_t gen_h_bytes(const Geo& g) { return (size_t)g.L * g.Y * g.Mp * g.K * 8; }
 
@@ -654,42 +760,54 @@ static int gen_hsum_blocks(const vmr_ctx* h) {
   return (int)std::max<size_t>(2, std::min<size_t>((rows + per - 1) / per, std::max<size_t>(2, (size_t)h->ncu * 2 / g.L)));
 }
 
-int gen_gamma(vmr_ctx* h, bool with_phi) {
+template <bool DET>
+static int gen_gamma_t(vmr_ctx* h, bool with_phi) {
   const Geo& g = h->g;
-  if (!h->h_valid || !h->f_valid || !h->a_valid) { int rc = gen_hist(h); if (rc) return rc; }
   {
     Prof p(h, VMR_KERNEL_FINALIZE);
     const int nb = gen_hsum_blocks(h), ext = nb > 1 ? 1 : 0;
     const int s1_lds = (!ext && (size_t)(5 * g.K + g.Mp) * 8 <= 48 * 1024) ? 1 : 0;   // (within the default dynamic-LDS limit, the K-sized arrays included)
     double* slotA = (h->n_partial > 0 || !h->a_zero) ? h->slotA : nullptr;
-    if (ext) hipLaunchKernelGGL(k_gen_hsum, dim3(g.L * nb), dim3(1024), (size_t)g.K * 8, h->stream, h->par, h->Hg, h->gen_s1, 0, 0, nb, g);
-    hipLaunchKernelGGL(k_fin_gamma_gen, dim3(g.L), dim3(1024), (size_t)5 * g.K * 8 + (s1_lds ? (size_t)g.Mp * 8 : 0), h->stream, h->par, h->Hg, slotA,
+    if (ext) hipLaunchKernelGGL(k_gen_hsum<DET>, dim3(g.L * nb), dim3(1024), (size_t)g.K * 8, h->stream, h->par, h->Hg, h->gen_s1, 0, 0, nb, g);
+    hipLaunchKernelGGL(k_fin_gamma_gen<DET>, dim3(g.L), dim3(1024), (size_t)5 * g.K * 8 + (s1_lds ? (size_t)g.Mp * 8 : 0), h->stream, h->par, h->Hg, slotA,
                        h->slotF, h->gen_s1, s1_lds, ext, with_phi ? 1 : 0, with_phi ? 1 : 0, g);
     if (ext && (with_phi || !g.mut)) {   // phi's sums with the new theta, then its commit (mutuality off: always, model.py:680)
       double* s2 = h->gen_s1 + (size_t)g.L * g.Mp;
-      hipLaunchKernelGGL(k_gen_hsum, dim3(g.L * nb), dim3(1024), (size_t)g.K * 8, h->stream, h->par, h->Hg, s2, 1, with_phi ? 1 : 0, nb, g);
-      hipLaunchKernelGGL(k_fin_phi_gen, dim3(g.L), dim3(1024), (size_t)2 * g.K * 8, h->stream, h->par, h->Hg, s2, g);
+      hipLaunchKernelGGL(k_gen_hsum<DET>, dim3(g.L * nb), dim3(1024), (size_t)g.K * 8, h->stream, h->par, h->Hg, s2, 1, with_phi ? 1 : 0, nb, g);
+      hipLaunchKernelGGL(k_fin_phi_gen<DET>, dim3(g.L), dim3(1024), (size_t)2 * g.K * 8, h->stream, h->par, h->Hg, s2, g);
     }
   }
   HIPCHK(h, hipGetLastError());
+  return VMR_OK;
+}
+int gen_gamma(vmr_ctx* h, bool with_phi) {
+  const Geo& g = h->g;
+  if (!h->h_valid || !h->f_valid || !h->a_valid) { int rc = gen_hist(h); if (rc) return rc; }
+  const int rc = g.det ? gen_gamma_t<true>(h, with_phi) : gen_gamma_t<false>(h, with_phi);
+  if (rc) return rc;
   h->a_valid = false; h->a_zero = true;
   if (with_phi) { h->h_valid = false; h->f_valid = false; h->h_zero = true; }
   return VMR_OK;
 }
 
-int gen_phi(vmr_ctx* h) {
+template <bool DET>
+static int gen_phi_t(vmr_ctx* h) {
   const Geo& g = h->g;
-  if (!g.mut) return VMR_OK;   // committed by k_fin_gamma_gen
-  if (!h->h_valid) { int rc = gen_hist(h); if (rc) return rc; }
   {
     Prof p(h, VMR_KERNEL_FINALIZE);
     const int nb = gen_hsum_blocks(h);
     double* s2 = nb > 1 ? h->gen_s1 + (size_t)g.L * g.Mp : nullptr;
-    if (s2) hipLaunchKernelGGL(k_gen_hsum, dim3(g.L * nb), dim3(1024), (size_t)g.K * 8, h->stream, h->par, h->Hg, s2, 1, 0, nb, g);
-    hipLaunchKernelGGL(k_fin_phi_gen, dim3(g.L), dim3(1024), (size_t)2 * g.K * 8, h->stream, h->par, h->Hg, s2, g);
+    if (s2) hipLaunchKernelGGL(k_gen_hsum<DET>, dim3(g.L * nb), dim3(1024), (size_t)g.K * 8, h->stream, h->par, h->Hg, s2, 1, 0, nb, g);
+    hipLaunchKernelGGL(k_fin_phi_gen<DET>, dim3(g.L), dim3(1024), (size_t)2 * g.K * 8, h->stream, h->par, h->Hg, s2, g);
   }
   HIPCHK(h, hipGetLastError());
   return VMR_OK;
+}
+int gen_phi(vmr_ctx* h) {
+  const Geo& g = h->g;
+  if (!g.mut) return VMR_OK;   // committed by k_fin_gamma_gen
+  if (!h->h_valid) { int rc = gen_hist(h); if (rc) return rc; }
+  return g.det ? gen_phi_t<true>(h) : gen_phi_t<false>(h);
 }
 
 int gen_rho(vmr_ctx* h, int mode, bool commit_nu, bool raw_nu, gen_fin_rho_fn fin_rho) {

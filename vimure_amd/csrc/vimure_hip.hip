@@ -1579,8 +1579,8 @@ __device__ __forceinline__ void fin_rho_body(double* par, double* Hg, const doub
           if (g.mut && y > 0) a0 += (z2 / (z1 + z2)) * hk[k];
         }
       } else if (g.mut && y > 0) {
-        for (int k = 0; k < g.K; ++k) {
-          const double hv = Hl[(size_t)it * g.K + k];
+        for (int k = 0; k < g.K; ++k) {   // (general kernels, deterministic mode: the cells hold integers, sweep_gen.hip)
+          const double hv = g.det ? det_back(reinterpret_cast<const unsigned long long*>(Hl)[(size_t)it * g.K + k], g.det_sh) : Hl[(size_t)it * g.K + k];
           if (hv != 0.0) a0 += (z2 / (gth * par[o.G_la + l * g.K + k] + z2)) * hv;
         }
       }
@@ -1612,7 +1612,23 @@ __device__ __forceinline__ void fin_rho_body(double* par, double* Hg, const doub
   __syncthreads();
   if (!last) return;
   double a1 = 0, a2 = 0, a3 = 0;
-  if (threadIdx.x < NSLOT) {
+  if (g.gen && g.det) {
+    // (the general kernels' deterministic pass added integers here, two words each: slots 0 .. NSLOT/2 - 1 at 2^-det_shr, the
+    // others at 2^-(det_shr + DET_SH2), sweep_gen.hip's gen_fx2.  How they split over the slots depends on which workgroup drew which
+    // step: summed as integers, then converted once -- a slot beyond 2^53 would round on its own)
+    if (threadIdx.x == 0) {
+      unsigned long long* pi = reinterpret_cast<unsigned long long*>(slotR);
+      unsigned long long s[6] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
+      for (int q = 0; q < NSLOT; ++q) {
+        const int w = q < NSLOT / 2 ? 0 : 3;
+        for (int i = 1; i <= 3; ++i) { s[w + i - 1] += pi[q * 4 + i]; pi[q * 4 + i] = 0ull; }
+        pi[q * 4] = 0ull;
+      }
+      a1 = det_back(s[0], g.det_shr) + det_back(s[3], g.det_shr + DET_SH2);
+      a2 = det_back(s[1], g.det_shr) + det_back(s[4], g.det_shr + DET_SH2);
+      a3 = det_back(s[2], g.det_shr) + det_back(s[5], g.det_shr + DET_SH2);
+    }
+  } else if (threadIdx.x < NSLOT) {
     double* ps = slotR + (size_t)threadIdx.x * 4;
     a1 = ps[1]; a2 = ps[2]; a3 = ps[3];
     ps[0] = ps[1] = ps[2] = ps[3] = 0.0;   // consume
@@ -2397,7 +2413,7 @@ static int create_ctx(vmr_ctx** out, hipDeviceProp_t* prop, int device, int L, i
   g.gen = K > KMAX ? 1 : 0; g.wide = 0;   // (wide entries: decided once the largest count is known)
   read_opts(h->opt);
   g.dbg = h->opt.debug;
-  g.det = h->opt.deterministic ? 1 : 0; g.det_sh = 0; g.det_shr = 0;   // sorted report lists unless the older step layout is asked for
+  g.det = h->opt.deterministic ? 1 : 0; g.det_sh = 0; g.det_shr = 0; g.det_sha = 0;   // sorted report lists unless the older step layout is asked for
   std::string err;
   if (choose_geo(g, prop->multiProcessorCount, err, lists_only) != VMR_OK) return fail(nullptr, VMR_EINVAL, err.c_str());
   memset(h->prof_ms, 0, sizeof h->prof_ms); memset(h->prof_n, 0, sizeof h->prof_n);
@@ -2608,6 +2624,23 @@ static int sl_finish(vmr_ctx* h) {
   return VMR_OK;
 }
 
+// VMR_DETERMINISTIC=1: the fixed-point scales (Geo::det_sh, det_shr) from the sum of all counts.  xbits: bits of the largest count
+// a single add into H can carry -- the sweep kernels convert such a term with the 1.5 * 2^52 trick, which holds |v| 2^sh < 2^51.
+static int det_scales(vmr_ctx* h, int xbits) {
+  Geo& g = h->g;
+  unsigned long long sx = 0;
+  CK(hipMemcpyAsync(&sx, h->sumx, 8, hipMemcpyDeviceToHost, h->stream));
+  CK(hipStreamSynchronize(h->stream));
+  int bits = 1;
+  while (bits < 62 && (sx >> bits) != 0ull) ++bits;
+  g.det_sh = std::max(0, std::min(51 - xbits, 61 - bits));   // (specialised kernels: counts of 11 bits, so <= 40)
+  const unsigned long long eb = 64ull * (sx + (unsigned long long)g.L * g.N * g.N * g.K);
+  int rbits = 1;
+  while (rbits < 62 && (eb >> rbits) != 0ull) ++rbits;
+  g.det_shr = std::min(34, std::max(0, 61 - rbits));   // (<= 34: ELBO terms up to 2047 * |log eps| < 2^17)
+  return VMR_OK;
+}
+
 // LDS shapes, the statistics / factor tables, scratch; for report lists the count-mode launch (constants C[l][y][m])
 static int create_tail(vmr_ctx* h, const hipDeviceProp_t& prop) {
   Geo& g = h->g;
@@ -2622,7 +2655,6 @@ static int create_tail(vmr_ctx* h, const hipDeviceProp_t& prop) {
   }
   if (g.gen) {
     // the general kernels: one copy of H with every category, nothing in LDS, no constants C (sweep_gen.h)
-    if (g.det) return fail(nullptr, VMR_EINVAL, "VMR_DETERMINISTIC=1 needs the specialised kernels: K <= 8, counts <= 2047, (largest count + 1) * M <= 2^20");
     g.ml = 0; g.hc = 0; g.yt = 0; g.two_pass = 0;
     const double hb = (double)L * g.Y * g.Mp * K * 8.0;
     size_t fr = 0, tot = 0;
@@ -2643,6 +2675,26 @@ static int create_tail(vmr_ctx* h, const hipDeviceProp_t& prop) {
     CK(hipMemsetAsync(h->nu_acc, 0, (size_t)(3 + L) * 8, h->stream));
     CK(hipMalloc(&h->lutg, (size_t)L * g.W * 256 * 8));
     CK(hipMemsetAsync(h->lutg, 0, (size_t)L * g.W * 256 * 8, h->stream));
+    if (g.det) {
+      // VMR_DETERMINISTIC=1: H, the slots and gen_s1 hold the integer sums themselves (sweep_gen.hip), no shadow; the fixed point
+      // of H leaves room for the sum of all counts and for the largest count in one add
+      if (!h->sparse) return fail(nullptr, VMR_EINVAL, "VMR_DETERMINISTIC=1 needs the report lists (a sparse tensor)");
+      unsigned xm = 0;
+      CK(hipMemcpyAsync(&xm, h->xmax, 4, hipMemcpyDeviceToHost, h->stream));
+      CK(hipStreamSynchronize(h->stream));
+      int xbits = 1;
+      while (xbits < 32 && (xm >> xbits) != 0u) ++xbits;
+      int rc = det_scales(h, xbits);
+      if (rc) return rc;
+      // sums of rho: a 64-bit cell (or a lane's sum) holds at most N^2 ties' worth; 2^-50 at most (the conversion trick, rho <= 1).
+      // (The specialised kernels' fixed 2^-30 moved a K = 12 fit with many nearly empty categories 5e-8 from the default mode.)
+      const unsigned long long T_ = (unsigned long long)g.N * g.N;
+      int tbits = 1;
+      while (tbits < 62 && (T_ >> tbits) != 0ull) ++tbits;
+      g.det_sha = std::min(50, 62 - tbits);
+      CK(hipMalloc(&h->fr_slots, (size_t)L * FR_G * 2 * 8));
+      CK(hipMemsetAsync(h->fr_slots, 0, (size_t)L * FR_G * 2 * 8, h->stream));
+    }
     CK(hipStreamSynchronize(h->stream));
     return VMR_OK;
   }
@@ -2785,16 +2837,8 @@ static int create_tail(vmr_ctx* h, const hipDeviceProp_t& prop) {
     // VMR_DETERMINISTIC=1 (sorted report lists only): see SlArgs::det.  The fixed point of the count-weighted sums leaves
     // room for the sum of all counts.
     if (!h->sparse) return fail(nullptr, VMR_EINVAL, "VMR_DETERMINISTIC=1 needs the report lists (a sparse tensor with M <= 8192, counts <= 2047)");
-    unsigned long long sx = 0;
-    CK(hipMemcpyAsync(&sx, h->sumx, 8, hipMemcpyDeviceToHost, h->stream));
-    CK(hipStreamSynchronize(h->stream));
-    int bits = 1;
-    while (bits < 62 && (sx >> bits) != 0ull) ++bits;
-    g.det_sh = std::min(40, std::max(0, 61 - bits));    // (<= 40: the conversion trick of the sweep kernel holds |v| 2^sh < 2^51, v up to 2047)
-    const unsigned long long eb = 64ull * (sx + (unsigned long long)L * g.N * g.N * K);
-    int rbits = 1;
-    while (rbits < 62 && (eb >> rbits) != 0ull) ++rbits;
-    g.det_shr = std::min(34, std::max(0, 61 - rbits));   // (<= 34: ELBO terms up to 2047 * |log eps| < 2^17)
+    int rc = det_scales(h, 11);   // (packed entries: counts up to 2047)
+    if (rc) return rc;
     const size_t nd = (size_t)L * g.Y * g.Mp * K + (size_t)L * g.W * 64 * K + (size_t)L * K + 5;
     CK(hipMalloc(&h->det_buf, nd * 8));
     CK(hipMemsetAsync(h->det_buf, 0, nd * 8, h->stream));

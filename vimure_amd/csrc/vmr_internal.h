@@ -68,9 +68,12 @@ struct Geo {
                 // (y >= hc = yt; a few per cent) are ALSO kept as a compact list (vmr_ctx::far_pos / far_ent); the pass takes their
                 // factors by formula and leaves their statistics to k_far_hist, which follows it
   int wide;     // entries in two words (vmr_ctx::EX): counts beyond 2047 or (max count + 1) * Mp beyond 2^20 table rows
+  int det_sha;  // VMR_DETERMINISTIC=1 on the general kernels: sums of rho over ties in 2^-det_sha (N^2 2^det_sha <= 2^62, at most 2^-50)
 };
-// fixed point of the deterministic mode: count-weighted sums 2^-g.det_sh; ELBO partials 2^-g.det_shr; sums of rho over ties (< 2^31 ties) 2^-30
+// fixed point of the deterministic mode: count-weighted sums 2^-g.det_sh; ELBO partials 2^-g.det_shr; sums of rho over ties (< 2^31 ties)
+// 2^-30 on the specialised kernels, 2^-g.det_sha on the general ones
 #define DET_SH_A 30
+#define DET_SH2 30   // general kernels: the ELBO partials' second word is 2^-(det_shr + DET_SH2) (sweep_gen.hip, gen_fx2)
 __device__ __forceinline__ unsigned long long det_fx(double v, int sh) { return (unsigned long long)__double2ll_rn(ldexp(v, sh)); }
 __device__ __forceinline__ double det_back(unsigned long long u, int sh) { return ldexp((double)(long long)u, -sh); }
 
