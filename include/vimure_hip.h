@@ -125,6 +125,18 @@ int vmr_set_state(vmr_handle h, const double* gamma_shp, const double* gamma_rte
                   const double* phi_shp, const double* phi_rte, double nu_shp, double nu_rte,
                   const double* pr_rho, int pr_rho_on_device);
 
+/* The initial rho prior of a realisation drawn on the device, bit for bit what `_set_rho_prior` (model.py:470-482, 509-559)
+ * draws from a RandomState without an informative prior: 1 + 0.01 * rand(L,N,N,K) (MT19937, genrand_res53), + bias0 on
+ * category 0, symmetrised when undirected != 0, normalised per tie in NumPy's summation order, one-hot (1, 0, .., 0) where the
+ * handle's coverage (vmr_data_stats) is 0.  The host only walks the generator: block b holds the ties [tie_cuts[b],
+ * tie_cuts[b + 1]) (2K 32-bit words each) and starts from the generator state mt_keys[b * 624 .. +624], mt_pos[b] (the key and
+ * position of RandomState.get_state(), pos in [0, 624]).  tie_cuts[nblk + 1] must rise strictly from 0 to L*N*N.
+ * out: [L,N,N,K] in natural order, device memory (out_on_device != 0) or host memory (filled through one copy).
+ * Runs on the handle's stream and synchronises it, so vmr_set_state(..., out, 1) takes out as it is.
+ * Invalid descriptors return VMR_EINVAL before anything is launched. */
+int vmr_draw_pr_rho(vmr_handle h, int nblk, const int64_t* tie_cuts, const uint32_t* mt_keys, const int32_t* mt_pos,
+                    double bias0, int undirected, double* out, int out_on_device);
+
 /* n_iters full sweeps of `_update_CAVI` (model.py:623-660): gamma -> phi -> rho -> nu, each
  * with the cache refresh of model.py:662-696 fused in.  Asynchronous on the handle's stream
  * unless elbo_out != NULL, in which case the ELBO (`__ELBO`, model.py:948-1019) is reduced

@@ -35,6 +35,8 @@ def _load_locked():
         lib.vmr_host_draw_pr_rho.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_int64, C.c_int, C.c_double, C.c_void_p, C.c_void_p]
         lib.vmr_host_mt_skip.restype = None
         lib.vmr_host_mt_skip.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_int64]
+        lib.vmr_host_mt_states.restype = None
+        lib.vmr_host_mt_states.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         return lib
     except Exception:   # no compiler on this host: the caller falls back to NumPy (same numbers, slower)
         return None
@@ -137,6 +139,41 @@ def mt_skip(prng, n_doubles):
     lib.vmr_host_mt_skip(key.ctypes.data, C.byref(pos), 2 * int(n_doubles))
     prng.set_state(("MT19937", key, pos.value, st[3], st[4]))
     return True
+
+
+BLOCK_WORDS = 1 << 15   # generator words per block of the device draw: 2000 blocks at BASELINE config 3
+MAX_BLOCKS = 8192       # (2.5 KB of state each: 20 MB at most, whatever the size of the prior)
+
+
+def block_count(L, N, K):
+    """How many blocks `mt_block_states` cuts an [L,N,N,K] draw into by default: blocks of about BLOCK_WORDS words (one
+    workgroup each, so that a few thousand cover the GPU), at most MAX_BLOCKS and at most one per tie."""
+    ties = L * N * N
+    return int(max(1, min(ties, MAX_BLOCKS, -(-2 * K * ties // BLOCK_WORDS))))
+
+
+def mt_block_states(prng, L, N, K, nblk=None):
+    """The block descriptors of a device draw of `prng.rand(L, N, N, K)` (vmr_draw_pr_rho): tie cut points cuts[nblk + 1]
+    (int64, whole ties of 2K words each), and the MT19937 state at the first word of every block, keys[nblk, 624] (uint32) and
+    pos[nblk] (int32).  The generator is walked once, without producing numbers (vmr_host_mt_states), and `prng` is left where
+    `prng.rand(L, N, N, K)` leaves it.  None when the helper is unavailable or `prng` is not an MT19937 RandomState."""
+    lib = load()
+    if lib is None:
+        return None
+    st = prng.get_state()
+    if st[0] != "MT19937":
+        return None
+    ties = L * N * N
+    nblk = block_count(L, N, K) if nblk is None else int(max(1, min(int(nblk), ties)))
+    cuts = np.array([ties * b // nblk for b in range(nblk + 1)], dtype=np.int64)
+    words = np.ascontiguousarray(2 * K * np.diff(cuts), dtype=np.int64)
+    key = np.ascontiguousarray(st[1], dtype=np.uint32).copy()
+    pos = C.c_int(int(st[2]))
+    keys = np.empty((nblk, 624), np.uint32)
+    starts = np.empty(nblk, np.int32)
+    lib.vmr_host_mt_states(key.ctypes.data, C.byref(pos), nblk, words.ctypes.data, keys.ctypes.data, starts.ctypes.data)
+    prng.set_state(("MT19937", key, pos.value, st[3], st[4]))
+    return cuts, keys, starts
 
 
 def draw_pr_rho_layers(prng, L_total, N, K, bias0, layers, coverage_local):

@@ -30,6 +30,7 @@ SIGNATURES = {
     "vmr_set_priors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double]),
     "vmr_set_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
                                 C.c_void_p, C.c_int]),
+    "vmr_draw_pr_rho": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_void_p, C.c_int]),
     "vmr_step": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "vmr_elbo": (C.c_int, [C.c_void_p, _dp]),
     "vmr_fit_loop": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p,

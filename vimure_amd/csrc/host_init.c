@@ -54,6 +54,17 @@ void vmr_host_mt_skip(uint32_t* key, int* pos, int64_t n) {
   }
 }
 
+/* the generator state (key[624], pos) at the first word of each of nblk consecutive blocks of words[b] 32-bit outputs, into
+ * out_keys[b * 624 ..] and out_pos[b]; key/pos are left at the end of the last block.  One walk of the recurrence, as
+ * vmr_host_mt_skip: the block starts of the device draw (vmr_draw_pr_rho). */
+void vmr_host_mt_states(uint32_t* key, int* pos, int nblk, const int64_t* words, uint32_t* out_keys, int32_t* out_pos) {
+  for (int b = 0; b < nblk; ++b) {
+    for (int i = 0; i < MT_N; ++i) out_keys[(size_t)b * MT_N + i] = key[i];
+    out_pos[b] = *pos;
+    vmr_host_mt_skip(key, pos, words[b]);
+  }
+}
+
 /* the next n tempered 32-bit outputs */
 FAST static void mt_words(uint32_t* restrict key, int* pos, uint32_t* restrict out, int64_t n) {
   while (n > 0) {

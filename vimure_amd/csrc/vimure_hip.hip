@@ -3335,7 +3335,7 @@ void vmr_destroy(vmr_handle h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   for (auto& e : h->evs) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
   for (auto& e : h->graphs) (void)hipGraphExecDestroy(e.ex);
-  void* ptrs[] = {h->x0p, h->h0s, h->far_pos, h->far_ent, h->far_base, h->EX, h->gen_s1, h->rm2, h->det_buf, h->fr_slots, h->nu_acc, h->fin_g, h->perm, h->sy, h->cls_p, h->Qt_p, h->nat, h->rho_snap, h->par_snap, h->rq, h->Rm, h->rbase, h->E, h->rs, h->Cg, h->Qt, h->ebase, h->rcls, h->X, h->Rb, h->cov, h->sumx, h->rho, h->logpr, h->par, h->slotA, h->slotR, h->elbo_dev, h->lutg, h->Hg, h->xmax, h->slotF, h->npartial};
+  void* ptrs[] = {h->drw, h->x0p, h->h0s, h->far_pos, h->far_ent, h->far_base, h->EX, h->gen_s1, h->rm2, h->det_buf, h->fr_slots, h->nu_acc, h->fin_g, h->perm, h->sy, h->cls_p, h->Qt_p, h->nat, h->rho_snap, h->par_snap, h->rq, h->Rm, h->rbase, h->E, h->rs, h->Cg, h->Qt, h->ebase, h->rcls, h->X, h->Rb, h->cov, h->sumx, h->rho, h->logpr, h->par, h->slotA, h->slotR, h->elbo_dev, h->lutg, h->Hg, h->xmax, h->slotF, h->npartial};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (h->stream2) { (void)hipStreamSynchronize(h->stream2); (void)hipStreamDestroy(h->stream2); }
   if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
@@ -3454,6 +3454,46 @@ int vmr_set_state(vmr_handle h, const double* gamma_shp, const double* gamma_rte
   h->h_zero = false; h->a_zero = false;   // (whatever an earlier, possibly failed, sweep left behind)
   if (h->h0s) HIPCHK(h, hipMemsetAsync(h->h0s, 0, (size_t)h->g.L * NSLOT * h->g.K * 8, h->stream));   // (the slots, not the constants behind them)
   if (h->gen_s1) HIPCHK(h, hipMemsetAsync(h->gen_s1, 0, (size_t)h->g.L * (h->g.Mp + h->g.K) * 8, h->stream));
+  return VMR_OK;
+}
+
+int vmr_draw_pr_rho(vmr_handle h, int nblk, const int64_t* tie_cuts, const uint32_t* mt_keys, const int32_t* mt_pos,
+                    double bias0, int undirected, double* out, int out_on_device) {
+  if (!h) return VMR_EINVAL;
+  if (!tie_cuts || !mt_keys || !mt_pos || !out) return fail(h, VMR_EINVAL, "vmr_draw_pr_rho: NULL argument");
+  if (nblk <= 0) return fail(h, VMR_EINVAL, "vmr_draw_pr_rho: nblk must be positive");
+  const Geo& g = h->g;
+  if (g.K > KGEN_MAX) return fail(h, VMR_EINVAL, "vmr_draw_pr_rho: K must be at most 256");
+  const int64_t ties = (int64_t)g.L * g.N * g.N;
+  for (int b = 0; b < nblk; ++b)
+    if (tie_cuts[b + 1] <= tie_cuts[b]) return fail(h, VMR_EINVAL, "vmr_draw_pr_rho: the tie cuts must be increasing");
+  if (tie_cuts[0] != 0 || tie_cuts[nblk] != ties) return fail(h, VMR_EINVAL, "vmr_draw_pr_rho: the tie cuts must span [0, L*N*N]");
+  for (int b = 0; b < nblk; ++b)
+    if (mt_pos[b] < 0 || mt_pos[b] > 624) return fail(h, VMR_EINVAL, "vmr_draw_pr_rho: a generator position outside [0, 624]");
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t cb = (size_t)(nblk + 1) * 8, kb = (size_t)nblk * 624 * 4, need = cb + kb + (size_t)nblk * 4;
+  if (h->drw_cap < need) {
+    if (h->drw) HIPCHK(h, hipFree(h->drw));
+    h->drw = nullptr;
+    h->drw_cap = 0;
+    HIPCHK(h, hipMalloc(&h->drw, need));
+    h->drw_cap = need;
+  }
+  char* base = static_cast<char*>(h->drw);
+  int rc;
+  if ((rc = h2d(h, base, tie_cuts, cb))) return rc;
+  if ((rc = h2d(h, base + cb, mt_keys, kb))) return rc;
+  if ((rc = h2d(h, base + cb + kb, mt_pos, (size_t)nblk * 4))) return rc;
+  const size_t n = (size_t)ties * g.K;
+  double* dst = out;
+  if (!out_on_device) HIPCHK(h, hipMalloc(&dst, n * 8));   // (the host form, for tests: the handle's own buffers may hold a state)
+  rc = draw_pr_rho_launch(h, nblk, reinterpret_cast<const int64_t*>(base), reinterpret_cast<const uint32_t*>(base + cb),
+                          reinterpret_cast<const int32_t*>(base + cb + kb), bias0, undirected, dst);
+  if (rc == VMR_OK && !out_on_device) rc = d2h(h, out, dst, n * 8);
+  hipError_t e = hipStreamSynchronize(h->stream);   // (the host arrays are only read during the call)
+  if (!out_on_device) (void)hipFree(dst);
+  if (rc != VMR_OK) return rc;
+  HIPCHK(h, e);
   return VMR_OK;
 }
 

@@ -110,6 +110,8 @@ struct vmr_ctx {
   uint8_t* X = nullptr;        // [L][N*N][Mp]
   uint64_t* Rb = nullptr;      // [L][N*N][W]
   uint8_t* cov = nullptr;      // [L][N*N]
+  void* drw = nullptr;         // vmr_draw_pr_rho's device copy of the block descriptors (tie cuts, MT19937 states), grown as needed
+  size_t drw_cap = 0;
   uint8_t* rcls = nullptr;     // [L][N*N] class of the mask row: 0 empty, 1 all ones, 2 partial
   // report lists (sparse format, see k_rho_sp); X is freed once they exist
   int sparse = 0;
@@ -481,6 +483,10 @@ static int grid_per_layer(vmr_ctx* h, Kern k, size_t smem, int* gl, long long ca
   *gl = (int)gl_;
   return VMR_OK;
 }
+
+// the initial rho prior from MT19937 block states, queued on the handle's stream; draw_prior.hip
+int draw_pr_rho_launch(vmr_ctx* h, int nblk, const int64_t* cuts, const uint32_t* keys, const int32_t* pos, double bias0,
+                       int undirected, double* out);
 
 // in-place exclusive scan of n u32 items on the handle's stream (bsum: scratch of ceil(n / 2048) items); vimure_hip.hip
 int scan_u32(vmr_ctx* h, unsigned* a, unsigned* bsum, size_t n);

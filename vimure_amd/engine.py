@@ -165,6 +165,7 @@ class CaviEngine:
         import torch
         if not hasattr(self, "_ahead"):
             self._ahead = [None, None]
+        if not hasattr(self, "_ahead_stream"):   # (draw_pr_rho may have made the slots without it)
             self._ahead_stream = torch.cuda.Stream(device=self.device)
         if self._ahead[slot] is None:
             self._ahead[slot] = torch.empty((self.L, self.N, self.N, self.K), dtype=torch.float64, device=f"cuda:{self.device}")
@@ -172,6 +173,38 @@ class CaviEngine:
             self._ahead[slot].view(-1).copy_(ten, non_blocking=True)
         self._ahead_stream.synchronize()
         return self._ahead[slot]
+
+    def draw_pr_rho(self, blocks, bias0, undirected, out=None):
+        """The initial rho prior drawn on the device (vmr_draw_pr_rho) from the block descriptors (cuts, keys, pos) of
+        `_hostlib.mt_block_states`, bit for bit the host draw, one-hot where this engine's coverage is 0.  out: a float64 CUDA
+        tensor [L,N,N,K], a C-contiguous float64 NumPy array (filled through one copy: for tests), or None: the engine's device
+        slot 0 of `upload_ahead`.  No host staging buffer is involved.  Returns out; the engine's stream has finished the draw,
+        so `set_state` takes a device tensor as it is."""
+        cuts, keys, pos = blocks
+        cuts = np.ascontiguousarray(cuts, dtype=np.int64)
+        keys = np.ascontiguousarray(keys, dtype=np.uint32)
+        pos = np.ascontiguousarray(pos, dtype=np.int32)
+        nblk = int(pos.shape[0])
+        if cuts.shape != (nblk + 1,) or keys.shape != (nblk, 624):
+            raise ValueError("blocks: cuts[nblk + 1], keys[nblk, 624] and pos[nblk] expected")
+        shape = (self.L, self.N, self.N, self.K)
+        if out is None:
+            import torch
+            if not hasattr(self, "_ahead"):
+                self._ahead = [None, None]
+            if self._ahead[0] is None:
+                self._ahead[0] = torch.empty(shape, dtype=torch.float64, device=f"cuda:{self.device}")
+            out = self._ahead[0]
+        if _is_torch(out):
+            import torch
+            assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float64 and tuple(out.shape) == shape
+            ptr, dev = out.data_ptr(), 1
+        else:
+            assert out.dtype == np.float64 and out.flags.c_contiguous and out.shape == shape
+            ptr, dev = out.ctypes.data, 0
+        self._check(self.lib.vmr_draw_pr_rho(self._h, nblk, cuts.ctypes.data, keys.ctypes.data, pos.ctypes.data, float(bias0),
+                                             int(bool(undirected)), ptr, dev))
+        return out
 
     def close(self):
         self._ahead = [None, None]

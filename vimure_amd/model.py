@@ -38,7 +38,7 @@ DEFAULT_NUM_REALISATIONS = 1
 
 _EXTRA = ["R", "EPS", "K", "bias0", "max_iter", "alpha_lambda", "beta_lambda", "alpha_teta", "beta_teta",
           "num_realisations"]  # the reference's whitelist, typos included (model.py:90-101)
-_OURS = ["device", "alpha_theta", "beta_theta", "engine", "keep_engine"]
+_OURS = ["device", "alpha_theta", "beta_theta", "engine", "keep_engine", "init_on_device"]
 
 
 def _is_torch(x):
@@ -233,6 +233,12 @@ class VimureModel(TransformerMixin, BaseEstimator):
             return out
         return pr
 
+    def _device_draw_possible(self):
+        """`fit(init_on_device=True)` draws on the GPU: no informative prior (scipy's Poisson pmf has no bit-exact device
+        counterpart), an MT19937 generator and the host helper that walks it."""
+        from . import _hostlib
+        return self.rho_prior is None and self.prng.get_state()[0] == "MT19937" and _hostlib.load() is not None
+
     def _draw_gammas(self, sumX, prng=None):
         """`_initialize_priors` (model.py:561-605): the draws that follow the rho prior, in the reference's order."""
         prng = self.prng if prng is None else prng
@@ -259,17 +265,26 @@ class VimureModel(TransformerMixin, BaseEstimator):
             return 0 if r == 0 else 1
         return r % 3
 
-    def _initial_states(self, eng, coverage):
+    def _initial_states(self, eng, coverage, on_device=False):
         """Initial state of every realisation, in order: (r, seed of r, state dict incl. pr_rho, seed after r).  CAVI
         consumes no randomness (reference model.py:386-437), so the whole seed chain is a function of the first seed
         and realisation r + 1 can be drawn while r runs on the GPU.  pr_rho lands in the engine's staging buffers
-        (three in rotation: one being uploaded, one queued, one being drawn)."""
+        (three in rotation: one being uploaded, one queued, one being drawn).  on_device: the generator is only walked
+        (`_hostlib.mt_block_states`); pr_rho is None and the state holds the block descriptors of the device draw
+        ("pr_rho_blocks", with its "bias0"), which `CaviEngine.draw_pr_rho` turns into the same prior."""
+        from . import _hostlib
         seed, prng = self.seed, self.prng
         for r in range(self.num_realisations):
             bias = DEFAULT_BIAS0 if r < 5 else (r - 4) * self.bias0
-            pr = self._draw_pr_rho(coverage, bias, prng=prng, out=eng.staging(self._staging_index(eng, r)))
+            if on_device:
+                blocks = _hostlib.mt_block_states(prng, self.L, self.N, self.K)
+                pr = None
+            else:
+                pr = self._draw_pr_rho(coverage, bias, prng=prng, out=eng.staging(self._staging_index(eng, r)))
             st = self._draw_gammas(self.sumX, prng=prng)
             st["pr_rho"] = pr
+            if on_device:
+                st["pr_rho_blocks"], st["bias0"] = blocks, bias
             step = prng.randint(1, 500)
             nxt = step if seed is None else seed + step
             yield r, seed, st, nxt
@@ -282,7 +297,10 @@ class VimureModel(TransformerMixin, BaseEstimator):
         device of a torch tensor X); `engine` reuses a `CaviEngine` already holding this X, R, K (many seeds
         of one dataset: the data is uploaded once, see vimure_amd/batch.py); `keep_engine=True` leaves the posteriors on
         the GPU after the fit: `get_inferred_model` / `predict` then run there (vmr_readout) and `rho_f` is only copied
-        to the host if something asks for it (`close()` frees the device memory).
+        to the host if something asks for it (`close()` frees the device memory).  `init_on_device=True` draws the initial rho
+        prior of every realisation on the GPU (vmr_draw_pr_rho), bit for bit the host draw: the host only walks the generator
+        and no L N^2 K array is built or uploaded.  An informative `rho_prior` keeps the host draw; `pr_rho_drawn_on` says
+        which one ran ("device" or "host").
 
         Host work per realisation is the RandomState draw of the initial state (bit-exact with the reference); with
         several realisations the next draw runs on a host thread while the GPU sweeps, the best realisation is kept on
@@ -308,8 +326,10 @@ class VimureModel(TransformerMixin, BaseEstimator):
                            self.alpha_mutuality, self.beta_mutuality)
             maxL, trace, best = -INF, [], None
             self.loop_seconds = 0.0   # wall time inside the CAVI loops of all realisations (device work included)
-            self.draw_seconds = 0.0   # host time the loops waited for an initial state
-            states = self._initial_states(eng, coverage)
+            self.draw_seconds = 0.0   # host time the loops waited for an initial state (with init_on_device: its GPU draw too)
+            on_dev = bool(extra_params.get("init_on_device", False)) and self._device_draw_possible()
+            self.pr_rho_drawn_on = "device" if on_dev else "host"
+            states = self._initial_states(eng, coverage, on_device=on_dev)
             if self.num_realisations > 1:   # draw realisation r + 1 while r runs
                 import queue
                 import threading
@@ -337,19 +357,20 @@ class VimureModel(TransformerMixin, BaseEstimator):
                                 return
                             r_ = item[0]
                             pr_ = item[2]["pr_rho"]
-                            si = self._staging_index(eng, r_)
-                            if r_ > 0 and getattr(eng, "can_upload_ahead", lambda: False)() and isinstance(pr_, np.ndarray) and np.shares_memory(pr_, eng.staging(si)):
-                                slot = r_ % 2
-                                while not slot_free[slot].wait(timeout=0.1):
-                                    if stop.is_set():
-                                        return
-                                slot_free[slot].clear()
-                                dev = eng.upload_ahead(si, slot)   # (realisation 0 is waited for: nothing to hide its upload behind)
-                                if dev is not None:
-                                    item[2]["pr_rho"] = dev
-                                    item[2]["_slot"] = slot
-                                else:
-                                    slot_free[slot].set()
+                            if pr_ is not None:   # (a host draw; the device draw runs in the consumer, from the block states)
+                                si = self._staging_index(eng, r_)
+                                if r_ > 0 and getattr(eng, "can_upload_ahead", lambda: False)() and isinstance(pr_, np.ndarray) and np.shares_memory(pr_, eng.staging(si)):
+                                    slot = r_ % 2
+                                    while not slot_free[slot].wait(timeout=0.1):
+                                        if stop.is_set():
+                                            return
+                                    slot_free[slot].clear()
+                                    dev = eng.upload_ahead(si, slot)   # (realisation 0 is waited for: nothing to hide its upload behind)
+                                    if dev is not None:
+                                        item[2]["pr_rho"] = dev
+                                        item[2]["_slot"] = slot
+                                    else:
+                                        slot_free[slot].set()
                             if not put(item):
                                 return
                         put(None)
@@ -370,6 +391,8 @@ class VimureModel(TransformerMixin, BaseEstimator):
             while True:
                 t_draw = time.perf_counter()
                 item = next_state()
+                if item is not None and item[2]["pr_rho"] is None:   # init_on_device: the prior of the block states, on the GPU
+                    item[2]["pr_rho"] = eng.draw_pr_rho(item[2]["pr_rho_blocks"], item[2]["bias0"], self.undirected)
                 self.draw_seconds += time.perf_counter() - t_draw
                 if item is None:
                     break
