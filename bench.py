@@ -14,10 +14,15 @@
 The timed region is exactly K steps, one block unless --repeats splits it into consecutive blocks (each block ends in a
 synchronize: their spread in `timing_blocks`); `value` is K over the summed time of the blocks.  Before the warm-up,
 --settle-sweeps untimed sweeps bring the GPU to its steady pace and the initial state is set again.  `--dump-outputs DIR`
-writes what the timed steps computed to DIR/*.npy.  After the timed region, under a time budget, the default run adds two
-blocks measured on the same GPU:
-`c5_layer` (one layer of configs[4] at its stated size: ms per sweep, per-kernel rates) and `small_fits` (the configs[3]
-workload of tools/bench_batch.py: fits/s from ONE process).
+writes what the timed steps computed to DIR/*.npy.  A plain run does only that: set-up, settle, warm-up, the timed steps, the
+dump, and the JSON line, whose roofline and per-kernel figures come from HIP events of the timed steps themselves.
+
+  python bench.py --gpus 1 --steps K --warmup W --full
+  adds, after the timed region and outside it, what the headline figure does not need: `time_to_converge` (fits until the
+  reference's stop rule fires), `cpu_baseline` / `cpu_baseline_sparse` (the C oracles on the host cores, with full-size parity
+  of the engine against them), and on config c3 with one GPU, under a time budget, two blocks measured on the same GPU:
+  `c5_layer` (one layer of configs[4] at its stated size: ms per sweep, per-kernel rates) and `small_fits` (the configs[3]
+  workload of tools/bench_batch.py: fits/s from ONE process).  --no-converge, --no-cpu-baseline and --no-extra leave parts out.
 
 A "step" is one full CAVI sweep (gamma, phi, rho, nu: reference model.py:623-660) with the ELBO
 evaluated at the reference cadence (iteration 1 and every 10th, model.py:1036).  Inputs are
@@ -89,16 +94,19 @@ def main():
                     help="after the timed sweeps, write what they computed (the posteriors get_state hands a caller; rho as a fixed "
                          "seeded sample of its ties) and the last ELBO to DIR/<name>.npy, float64")
     ap.add_argument("--no-kernel-events", action="store_true", help="diagnostic: no HIP events around the kernels in the timed region (roofline then has no live launch time)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the c5_layer / small_fits blocks after the timed region")
-    ap.add_argument("--extra-seconds", type=float, default=150.0, help="time budget of the extra blocks")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure what the headline figure does not need: time to convergence, the CPU "
+                         "baselines with full-size parity, and (config c3, one GPU) the c5_layer / small_fits blocks")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the c5_layer / small_fits blocks after the timed region")
+    ap.add_argument("--extra-seconds", type=float, default=150.0, help="--full: time budget of the extra blocks")
     ap.add_argument("--c5-nodes", type=int, default=8000, help="--config c5: nodes per layer (the stated configuration is 8000; smaller only to rehearse)")
     ap.add_argument("--villages", type=int, default=75, help="--config c4: villages of the Karnataka table (x 4 layers x --seeds fits); 75 = the stated workload")
     ap.add_argument("--seeds", type=int, default=10, help="--config c4: seeds per (village, layer); the reference's driver runs 10")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU baseline budget (bounded sample)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines and the full-size parity")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: CPU baseline budget (bounded sample)")
     ap.add_argument("--format", default="auto", choices=["auto", "dense", "sparse"],
                     help="engine data layout (VMR_FORMAT): report lists unless X is dense; 'dense' forces the tile path")
-    ap.add_argument("--no-converge", action="store_true", help="skip the time-to-ELBO-converge fit")
+    ap.add_argument("--no-converge", action="store_true", help="--full: skip the time-to-ELBO-converge fit")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -296,9 +304,9 @@ def main():
         out["sweep"] = {"canonical_bytes_per_iter": b_iter + b_elbo / 10.0,
                         "canonical_equiv_GBps": (b_iter + b_elbo / 10.0) / (dt / args.steps) / 1e9,
                         "iter_per_s_at_8TBps_canonical": HBM_PEAK_GBS * 1e9 / (b_iter + b_elbo / 10.0)}
-        if not args.no_converge:
+        if args.full and not args.no_converge:
             out["time_to_converge"] = time_to_converge(cfg, net, eng, seed)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"], out["parity_full_size"] = cpu_baseline(cfg, net, R, host, pr, args.cpu_seconds, eng)
             try:
                 out["cpu_baseline_sparse"] = cpu_baseline_sparse(cfg, net, host, pr, args.cpu_seconds, out["parity_full_size"])
@@ -307,7 +315,7 @@ def main():
         eng.close()
         del net, R
         torch.cuda.empty_cache()
-        if not args.no_extra and world == 1 and args.config == "c3":
+        if args.full and not args.no_extra and world == 1 and args.config == "c3":
             t_extra = time.perf_counter()
             try:
                 out["c5_layer"] = c5_layer_block(local)
