@@ -14,7 +14,8 @@
 //                                        bits 16..31 (Geo::farl): the step's reports of the levels beyond the LDS ones are its ties' FIRST
 //                                        ones -- rounds 0 .. nf - 1 -- and this is nf (k_far_first)
 // Padding only appears in the ~max-count steps per layer where the count changes.  Every per-tie array the sweeps touch is
-// stored BY POSITION (rho, log prior, mask-row class, the ELBO's mirror sums Qt), so all of a wave's accesses are contiguous;
+// stored BY POSITION (rho, log prior and, K = 2, its difference lpd, mask-row class, the ELBO's mirror sums Qt), so all of a
+// wave's accesses are contiguous;
 // the boundary functions (vmr_set_state, vmr_get_state, vmr_readout, vmr_sample) translate through perm.
 #ifndef VMR_SWEEP_SL_H
 #define VMR_SWEEP_SL_H
@@ -89,6 +90,14 @@ struct SlArgs {
               // as E log theta_m + E log lambda_k -- one table read per report instead of K
   const unsigned* Ez;   // 64 empty entries (the zeroed slack behind E): what the ring of a long step loads past the step's last round
   int elbo_cur;   // ELBO-only pass: the CURRENT G_nu, not the stale one -- nu was not committed since the rho it evaluates (split ELBO sweep of vmr_sweep_local)
+  // K = 2: rho depends on the log prior only through lp_1 - lp_0.  lpd [L][T] (by position, 64 rows of slack) holds that difference
+  // and lpb [L][2] the layer's bounds max_t |lp_k|: the update variants without ELBO read 8 bytes per tie instead of 16, and every
+  // K = 2 update variant (the ELBO ones from their own log prior, bit for bit the stored difference) takes
+  //   d = lpd + (U_1 - T E[lambda_1]) - (U_0 - T E[lambda_0])
+  // wherever |U_k - T E[lambda_k]| + lpb_k < 700 and |d| < 700; a wave that fails the test loads its step's log prior rows and takes
+  // the literal code.  (Kept by vmr_set_state, the one place the log prior is written.)  lpd null (VMR_NO_LPD): the log prior is
+  // read and the difference formed in registers, bit for bit the same.  lpb: required by every K = 2 handle of these kernels.
+  const double* lpd; const double* lpb;
 #ifdef SL_DEBUG
   unsigned long long* dbg_t;   // [waves][8]: a wave's start, end of prologue, end of step loop, end; first loads issued, tables' barrier, nu share done, flush done (100 MHz clock)
 #endif

@@ -68,7 +68,8 @@ template <int K> struct Batch { static constexpr int value = K <= 2 ? SL_BATCH2 
 // atomic lands first -- is an INTEGER sum in fixed point: the LDS statistics and mask sums (64-bit LDS adds), the per-lane sums over
 // ties (rho over all-ones rows, the ELBO partials), the cross-workgroup shadows.  Integer adds commute exactly, so the workgroups
 // keep their 16 waves and their tickets (rounds 2-3 ran this mode with ONE wave per workgroup: 4.5 times slower).
-template <int K, bool UPDATE, bool ELBO, bool ALLFULL, bool STORE = true, bool DET = false>
+// LPD (K = 2 update without ELBO, SlArgs::lpd non-null): the difference of the log prior is read instead of the log prior.
+template <int K, bool UPDATE, bool ELBO, bool ALLFULL, bool STORE = true, bool DET = false, bool LPD = false>
 __device__ __forceinline__ void sweep_body(const SlArgs& a, const Geo& g, const unsigned bx, const unsigned gx) {
   extern __shared__ __align__(16) unsigned char smem[];
   constexpr int PFK = sl_pf(K);   // rounds prefetched one step ahead
@@ -165,6 +166,11 @@ __device__ __forceinline__ void sweep_body(const SlArgs& a, const Geo& g, const 
   double* rl = a.rho + (size_t)l * T * K;
   double* rho_slack = a.rho + (size_t)g.L * T * K;   // 64 rows behind the last layer (vmr_create)
   const double* lpl = a.logpr + (size_t)l * T * K;
+  // (SlArgs::lpd) K = 2: the update variants without ELBO read the difference of the log prior, 8 bytes per tie; every K = 2 update
+  // variant tests against the layer's bounds
+  constexpr bool LPDV = LPD && K == 2 && UPDATE && !ELBO;
+  const double* lpdl = LPDV ? a.lpd + (size_t)l * T : nullptr;
+  const double lpb0 = (K == 2 && UPDATE) ? a.lpb[2 * l] : 0.0, lpb1 = (K == 2 && UPDATE) ? a.lpb[2 * l + 1] : 0.0;
   const unsigned* rql = a.rq ? a.rq + (size_t)l * (T + 1) : nullptr;
   const unsigned short* Rml = a.rq ? a.Rm + a.rbase[l] : nullptr;
   // a step is "far" when one of its reports lies in a level beyond the LDS copies this launch holds: it takes the general body,
@@ -219,7 +225,10 @@ __device__ __forceinline__ void sweep_body(const SlArgs& a, const Geo& g, const 
     if (LV0 && a.x0p) d.x0 = *at_bytes(a.x0p + (size_t)l * NS * 64 + row0, lane4);
 #pragma unroll
     for (int k = 0; k < K; ++k) { d.v[k] = 0.0; d.w[k] = 0.0; }
-    if (UPDATE || ELBO) {
+    if (LPDV) {   // v[0] = lp_1 - lp_0 (v[1] unused)
+      if (lp_const) d.v[0] = lp0_k - lp0_0;
+      else d.v[0] = *at_bytes(lpdl + row0, (unsigned)lane * 8u);
+    } else if (UPDATE || ELBO) {
       if (lp_const) {
 #pragma unroll
         for (int k = 0; k < K; ++k) d.v[k] = k == 0 ? lp0_0 : lp0_k;
@@ -536,20 +545,34 @@ __device__ __forceinline__ void sweep_body(const SlArgs& a, const Geo& g, const 
       }
       // ---- per-tie update from the finished sums
       double aa[K];
-#pragma unroll
-      for (int k = 0; k < K; ++k) aa[k] = (cur.v[k] + U[k]) - Tt * Ela[k];
       bool done = false;
       if (K == 2) {
-        // two categories: rho_0 = 1 / (1 + e^(a1-a0)) -- one exp, one reciprocal -- wherever the reference's raw exponentials
-        // neither overflow nor underflow (then equal to exp(a_k) / sum up to rounding); other ties below
-        const double d = aa[1] - aa[0];
-        const bool safe = fabs(aa[0]) < 700.0 && fabs(aa[1]) < 700.0 && fabs(d) < 700.0;
+        // two categories: rho_0 = 1 / (1 + e^d), d = a_1 - a_0 -- one exp, one reciprocal -- wherever the reference's raw exponentials
+        // neither overflow nor underflow (then equal to exp(a_k) / sum up to rounding); other ties below.  The a_k = lp_k + c_k are
+        // not formed: d comes from the difference of the log prior, and the layer's bounds of |lp_k| decide (SlArgs::lpd)
+        double c[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) c[k] = fma(-Tt, Ela[k], U[k]);
+        const double d = ((LPDV ? cur.v[0] : cur.v[K - 1] - cur.v[0]) + c[K - 1]) - c[0];
+        bool safe = fabs(c[0]) + lpb0 < 700.0 && fabs(c[K - 1]) + lpb1 < 700.0 && fabs(d) < 700.0;
+        if (!__all(safe)) {   // (rare) the step's log prior rows, the a_k and the test on them
+          double v[K];
+#pragma unroll
+          for (int k = 0; k < K; ++k) v[k] = cur.v[k];
+          if (LPDV) load_k<K>(at_bytes(lpl + row0 * K, laneK8), v);
+#pragma unroll
+          for (int k = 0; k < K; ++k) aa[k] = v[k] + c[k];
+          safe = fabs(aa[0]) < 700.0 && fabs(aa[K - 1]) < 700.0 && fabs(d) < 700.0;
+        }
         if (__all(safe)) {
           const double e = exp_tab(d, xt);   // (a table-free degree-13 polynomial was measured 17 % slower per launch)
           r[0] = rcp_nr2(1.0 + e);   // (1 + e in [1, e^700]: no scaling needed)
-          r[1] = e * r[0];
+          r[K - 1] = e * r[0];
           done = true;
         }
+      } else {
+#pragma unroll
+        for (int k = 0; k < K; ++k) aa[k] = (cur.v[k] + U[k]) - Tt * Ela[k];
       }
       if (!done) {
         double sum = 0.0;
@@ -925,28 +948,28 @@ __device__ __forceinline__ void sweep_body(const SlArgs& a, const Geo& g, const 
 
 #define SL_BOUNDS(K, UPDATE, ELBO, ALLFULL) \
   __launch_bounds__(sl_tpb_max(K, ELBO, ALLFULL, UPDATE), (K == 2 && !ELBO && ALLFULL) ? SL_WPE : sl_wpe(K, ELBO, ALLFULL, UPDATE))
-template <int K, bool UPDATE, bool ELBO, bool ALLFULL, bool STORE = true, bool DET = false>
+template <int K, bool UPDATE, bool ELBO, bool ALLFULL, bool STORE = true, bool DET = false, bool LPD = false>
 __global__ SL_BOUNDS(K, UPDATE, ELBO, ALLFULL) void k_sweep_sl(SlArgs a, Geo g) {
-  sweep_body<K, UPDATE, ELBO, ALLFULL, STORE, DET>(a, g, blockIdx.x, gridDim.x);
+  sweep_body<K, UPDATE, ELBO, ALLFULL, STORE, DET, LPD>(a, g, blockIdx.x, gridDim.x);
 }
 // One launch for many small handles in lockstep (vmr_fit_loop_batch): workgroup -> unit through `blk_unit`, the unit's
 // arguments from device memory.  A sweep of a Karnataka-sized layer is two dependent 20-40 us launches that leave the GPU
 // nearly empty; here every unit's sweep shares them.
-template <int K, bool UPDATE, bool ELBO, bool ALLFULL, bool STORE = true>
+template <int K, bool UPDATE, bool ELBO, bool ALLFULL, bool STORE = true, bool LPD = false>
 __global__ __launch_bounds__(sl_tpb_max_b(K, ELBO, ALLFULL), sl_wpe_b(K, ELBO, ALLFULL)) void k_sweep_sl_b(const SlUnit* __restrict__ units, const int* __restrict__ blk_unit) {
   const SlUnit& u = units[blk_unit[blockIdx.x]];
-  sweep_body<K, UPDATE, ELBO, ALLFULL, STORE>(u.a, u.g, blockIdx.x - (unsigned)u.blk0, (unsigned)u.nblk);
+  sweep_body<K, UPDATE, ELBO, ALLFULL, STORE, false, LPD>(u.a, u.g, blockIdx.x - (unsigned)u.blk0, (unsigned)u.nblk);
 }
 
 // ------------------------------------------------------------------------------------------
 // launcher of this object's K
 // ------------------------------------------------------------------------------------------
-template <bool UPDATE, bool ELBO, bool ALLFULL, bool STORE = true, bool DET = false>
-static int sl_launch_one(vmr_ctx* h, const SlShape& sh, SlArgs& a) {
+template <bool UPDATE, bool ELBO, bool ALLFULL, bool STORE = true, bool DET = false, bool LPD = false>
+static int sl_launch_one_(vmr_ctx* h, const SlShape& sh, SlArgs& a) {
   constexpr int K = VMR_K;
   const Geo& g = h->g;
   const long long NS = ((long long)g.N * g.N + 63) / 64, nw = sh.tpb / 64;
-  int rc = grid_per_layer(h, k_sweep_sl<K, UPDATE, ELBO, ALLFULL, STORE, DET>, sh.smem, &a.Gl, (NS + nw - 1) / nw, sh.tpb);
+  int rc = grid_per_layer(h, k_sweep_sl<K, UPDATE, ELBO, ALLFULL, STORE, DET, LPD>, sh.smem, &a.Gl, (NS + nw - 1) / nw, sh.tpb);
   if (rc) return rc;
 #ifdef SL_DEBUG
   // VMR_DEBUG_TIMES=<file>: every launch appends "<update><elbo> <waves>" and one line of four clock readings per wave
@@ -959,7 +982,7 @@ static int sl_launch_one(vmr_ctx* h, const SlShape& sh, SlArgs& a) {
     if (nwv * 64 <= ((size_t)1 << 22)) a.dbg_t = dbg_buf;
   }
 #endif
-  hipLaunchKernelGGL((k_sweep_sl<K, UPDATE, ELBO, ALLFULL, STORE, DET>), dim3(g.L * a.Gl), dim3(sh.tpb), sh.smem, h->stream, a, g);
+  hipLaunchKernelGGL((k_sweep_sl<K, UPDATE, ELBO, ALLFULL, STORE, DET, LPD>), dim3(g.L * a.Gl), dim3(sh.tpb), sh.smem, h->stream, a, g);
 #ifdef SL_DEBUG
   if (a.dbg_t) {
     std::vector<unsigned long long> t(nwv * 8);
@@ -973,6 +996,13 @@ static int sl_launch_one(vmr_ctx* h, const SlShape& sh, SlArgs& a) {
   }
 #endif
   return VMR_OK;
+}
+
+// (the update variants without ELBO of K = 2 read the difference of the log prior where the handle keeps it: SlArgs::lpd)
+template <bool UPDATE, bool ELBO, bool ALLFULL, bool STORE = true, bool DET = false>
+static int sl_launch_one(vmr_ctx* h, const SlShape& sh, SlArgs& a) {
+  if (VMR_K == 2 && UPDATE && !ELBO && a.lpd) return sl_launch_one_<UPDATE, ELBO, ALLFULL, STORE, DET, VMR_K == 2 && UPDATE && !ELBO>(h, sh, a);
+  return sl_launch_one_<UPDATE, ELBO, ALLFULL, STORE, DET>(h, sh, a);
 }
 
 #define SL_CAT2(a, b) a##b
@@ -1016,24 +1046,32 @@ int SL_CAT(vmr_sl_launch_k, VMR_K)(vmr_ctx* h, int mode, const SlShape& sh, SlAr
 
 // the rho update (mode 0), rho update + ELBO data terms (mode 1) or the statistics of the current rho (mode 3: a realisation's
 // first sweep) of `nblocks` workgroups' worth of units in one launch
-template <bool UPDATE, bool ELBO, bool ALLFULL, bool STORE = true>
-static int sl_launch_batch_one(vmr_ctx* h, hipStream_t st, const SlUnit* units, const int* blk_unit, int nblocks, int tpb, size_t smem) {
+template <bool UPDATE, bool ELBO, bool ALLFULL, bool STORE = true, bool LPD = false>
+static int sl_launch_batch_one_(vmr_ctx* h, hipStream_t st, const SlUnit* units, const int* blk_unit, int nblocks, int tpb, size_t smem) {
   constexpr int K = VMR_K;
   // (the leave for > 48 KB of dynamic LDS is per device and this may be any thread's first launch there: asked for every time --
   // a call that costs nothing beside a batch's launches -- instead of remembered in a process-wide static)
   if (smem > 48 * 1024)
-    HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_sweep_sl_b<K, UPDATE, ELBO, ALLFULL, STORE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-  hipLaunchKernelGGL((k_sweep_sl_b<K, UPDATE, ELBO, ALLFULL, STORE>), dim3(nblocks), dim3(tpb), smem, st, units, blk_unit);
+    HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_sweep_sl_b<K, UPDATE, ELBO, ALLFULL, STORE, LPD>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+  hipLaunchKernelGGL((k_sweep_sl_b<K, UPDATE, ELBO, ALLFULL, STORE, LPD>), dim3(nblocks), dim3(tpb), smem, st, units, blk_unit);
   return VMR_OK;
+}
+// (lpd: every unit keeps the difference of the log prior -- the units of one launch come from handles of one build and one
+// environment, so they all do or none does)
+template <bool UPDATE, bool ELBO, bool ALLFULL, bool STORE = true>
+static int sl_launch_batch_one(vmr_ctx* h, hipStream_t st, bool lpd, const SlUnit* units, const int* blk_unit, int nblocks, int tpb, size_t smem) {
+  if (VMR_K == 2 && UPDATE && !ELBO && lpd) return sl_launch_batch_one_<UPDATE, ELBO, ALLFULL, STORE, VMR_K == 2 && UPDATE && !ELBO>(h, st, units, blk_unit, nblocks, tpb, smem);
+  return sl_launch_batch_one_<UPDATE, ELBO, ALLFULL, STORE>(h, st, units, blk_unit, nblocks, tpb, smem);
 }
 int SL_CAT(vmr_sl_launch_batch_k, VMR_K)(vmr_ctx* h, hipStream_t st, int mode, int allfull, const SlUnit* units, const int* blk_unit, int nblocks,
                                           int tpb, size_t smem) {
-  if (mode == 3) return allfull ? sl_launch_batch_one<false, false, true>(h, st, units, blk_unit, nblocks, tpb, smem)
-                                : sl_launch_batch_one<false, false, false>(h, st, units, blk_unit, nblocks, tpb, smem);
-  if (mode == 4) return allfull ? sl_launch_batch_one<true, false, true, false>(h, st, units, blk_unit, nblocks, tpb, smem)
-                                : sl_launch_batch_one<true, false, false, false>(h, st, units, blk_unit, nblocks, tpb, smem);
-  if (allfull) return mode ? sl_launch_batch_one<true, true, true>(h, st, units, blk_unit, nblocks, tpb, smem)
-                           : sl_launch_batch_one<true, false, true>(h, st, units, blk_unit, nblocks, tpb, smem);
-  return mode ? sl_launch_batch_one<true, true, false>(h, st, units, blk_unit, nblocks, tpb, smem)
-              : sl_launch_batch_one<true, false, false>(h, st, units, blk_unit, nblocks, tpb, smem);
+  const bool lpd = h->lpd != nullptr;
+  if (mode == 3) return allfull ? sl_launch_batch_one<false, false, true>(h, st, lpd, units, blk_unit, nblocks, tpb, smem)
+                                : sl_launch_batch_one<false, false, false>(h, st, lpd, units, blk_unit, nblocks, tpb, smem);
+  if (mode == 4) return allfull ? sl_launch_batch_one<true, false, true, false>(h, st, lpd, units, blk_unit, nblocks, tpb, smem)
+                                : sl_launch_batch_one<true, false, false, false>(h, st, lpd, units, blk_unit, nblocks, tpb, smem);
+  if (allfull) return mode ? sl_launch_batch_one<true, true, true>(h, st, lpd, units, blk_unit, nblocks, tpb, smem)
+                           : sl_launch_batch_one<true, false, true>(h, st, lpd, units, blk_unit, nblocks, tpb, smem);
+  return mode ? sl_launch_batch_one<true, true, false>(h, st, lpd, units, blk_unit, nblocks, tpb, smem)
+              : sl_launch_batch_one<true, false, false>(h, st, lpd, units, blk_unit, nblocks, tpb, smem);
 }

@@ -435,6 +435,27 @@ __global__ void k_init_rho_pos(const double* __restrict__ pr, double* __restrict
   if (bad) atomicOr(not_onehot, 1);
 }
 
+// K = 2 (SlArgs::lpd): lpd[row] = logpr[row][1] - logpr[row][0] over the L T rows by position (lpd null: VMR_NO_LPD), and the layers' bounds
+// lpb[l][k] = max |logpr[l][.][k]| (non-negative doubles order as their bit patterns: an integer max; a NaN bound fails every test)
+__global__ __launch_bounds__(256) void k_lpd(const double* __restrict__ logpr, double* __restrict__ lpd, unsigned long long* __restrict__ lpb, size_t T, int L) {
+  for (int l = 0; l < L; ++l) {
+    unsigned long long m0 = 0ull, m1 = 0ull;
+    for (size_t q = blockIdx.x * (size_t)blockDim.x + threadIdx.x; q < T; q += (size_t)gridDim.x * blockDim.x) {
+      const size_t row = (size_t)l * T + q;
+      const double v0 = logpr[row * 2], v1 = logpr[row * 2 + 1];
+      if (lpd) lpd[row] = v1 - v0;
+      m0 = max(m0, (unsigned long long)__double_as_longlong(fabs(v0)));
+      m1 = max(m1, (unsigned long long)__double_as_longlong(fabs(v1)));
+    }
+#pragma unroll
+    for (int o2 = 32; o2 > 0; o2 >>= 1) {
+      m0 = max(m0, (unsigned long long)__shfl_xor((long long)m0, o2, 64));
+      m1 = max(m1, (unsigned long long)__shfl_xor((long long)m1, o2, 64));
+    }
+    if ((threadIdx.x & 63) == 0) { atomicMax(&lpb[2 * l], m0); atomicMax(&lpb[2 * l + 1], m1); }
+  }
+}
+
 // nibble LUT of E[theta] for wide masks: lut[l][n][e] = sum of E[theta_m] over the set bits e of reporters 4n..4n+3
 __global__ void k_build_lut(const double* __restrict__ par, double* __restrict__ lutg, Geo g) {
   const ParOff o = par_off(g.L, g.Mp, g.K);
@@ -1777,7 +1798,7 @@ static SlShape sl_shape(const vmr_ctx* h, bool update, bool elbo, bool hist) {
 static SlArgs sl_args(const vmr_ctx* h, const SlShape& sh, int do_hist, int sum_a = 0) {
   return SlArgs{h->E, h->rs, h->ebase, h->perm, h->sy, h->cls_p, h->Qt_p, h->Rb, h->rq, h->Rm, h->rbase, h->rm2, h->rho, h->logpr, h->par, h->slotR,
                 h->lutg, h->Hg, h->slotF, h->slotA, 1, do_hist, sh.yt, sh.hc, sum_a, nullptr, nullptr, 0, 0, nullptr, h->lp0 ? 1 : 0, h->g.farl, (do_hist == 1 && h->g.two_pass && sh.hc >= 1) ? h->h0s : nullptr, (do_hist == 1 && h->g.two_pass && sh.hc >= 1 && h->h0s) ? h->x0p : nullptr,
-                (h->h0s && h->g.two_pass && !h->opt.no_lv0r) ? 1 : 0, h->E + h->n_slots, 0};   // (level 0 must be among the LDS levels: its deficits go there)
+                (h->h0s && h->g.two_pass && !h->opt.no_lv0r) ? 1 : 0, h->E + h->n_slots, 0, h->lpd, h->lpb};   // (level 0 must be among the LDS levels: its deficits go there)
 }
 static int sl_launch(vmr_ctx* h, int mode, const SlShape& sh, SlArgs& a) {
   sl_launch_fn fn = vmr_sl_launcher(h->g.K);
@@ -2387,6 +2408,7 @@ static void read_opts(VmrOpts& o) {
   o.no_rlists = set("VMR_NO_RLISTS");
   o.no_rm2 = set("VMR_NO_RM2");
   o.no_lp0 = set("VMR_NO_LP0");
+  o.no_lpd = set("VMR_NO_LPD");
   o.always_store_rho = set("VMR_ALWAYS_STORE_RHO");
   o.debug_lazy_rho = set("VMR_DEBUG_LAZY_RHO");
   o.gen_hsum = num("VMR_GEN_HSUM", 0);
@@ -3335,7 +3357,7 @@ void vmr_destroy(vmr_handle h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   for (auto& e : h->evs) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
   for (auto& e : h->graphs) (void)hipGraphExecDestroy(e.ex);
-  void* ptrs[] = {h->drw, h->x0p, h->h0s, h->far_pos, h->far_ent, h->far_base, h->EX, h->gen_s1, h->rm2, h->det_buf, h->fr_slots, h->nu_acc, h->fin_g, h->perm, h->sy, h->cls_p, h->Qt_p, h->nat, h->rho_snap, h->par_snap, h->rq, h->Rm, h->rbase, h->E, h->rs, h->Cg, h->Qt, h->ebase, h->rcls, h->X, h->Rb, h->cov, h->sumx, h->rho, h->logpr, h->par, h->slotA, h->slotR, h->elbo_dev, h->lutg, h->Hg, h->xmax, h->slotF, h->npartial};
+  void* ptrs[] = {h->drw, h->x0p, h->h0s, h->far_pos, h->far_ent, h->far_base, h->EX, h->gen_s1, h->rm2, h->det_buf, h->fr_slots, h->nu_acc, h->fin_g, h->perm, h->sy, h->cls_p, h->Qt_p, h->nat, h->rho_snap, h->par_snap, h->rq, h->Rm, h->rbase, h->E, h->rs, h->Cg, h->Qt, h->ebase, h->rcls, h->X, h->Rb, h->cov, h->sumx, h->rho, h->logpr, h->lpd, h->lpb, h->par, h->slotA, h->slotR, h->elbo_dev, h->lutg, h->Hg, h->xmax, h->slotF, h->npartial};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (h->stream2) { (void)hipStreamSynchronize(h->stream2); (void)hipStreamDestroy(h->stream2); }
   if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
@@ -3427,6 +3449,16 @@ int vmr_set_state(vmr_handle h, const double* gamma_shp, const double* gamma_rte
     HIPCHK(h, hipMemcpyAsync(&nf, flag, 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->lp0 = nf == 0 && !h->opt.no_lp0;
+    if (g.K == 2 && !g.gen) {   // the bounds of the log prior and (unless VMR_NO_LPD) its difference (SlArgs::lpd)
+      if (!h->lpb) HIPCHK(h, hipMalloc(&h->lpb, (size_t)g.L * 2 * 8));
+      if (!h->lpd && !h->opt.no_lpd) {
+        HIPCHK(h, hipMalloc(&h->lpd, ((size_t)g.L * T_ + 64) * 8));
+        HIPCHK(h, hipMemsetAsync(h->lpd + (size_t)g.L * T_, 0, (size_t)64 * 8, h->stream));
+      }
+      HIPCHK(h, hipMemsetAsync(h->lpb, 0, (size_t)g.L * 2 * 8, h->stream));
+      hipLaunchKernelGGL(k_lpd, dim3(1024), dim3(256), 0, h->stream, h->logpr, h->lpd, reinterpret_cast<unsigned long long*>(h->lpb), T_, g.L);
+      HIPCHK(h, hipGetLastError());
+    }
   } else {
     if (!pr_rho_on_device) {
       // stage through logpr (overwritten by k_init_rho element-wise after being read)
@@ -4200,13 +4232,14 @@ int vmr_kernel_bytes(vmr_handle h, int kernel_class, double* bytes) {
     const double E = (g.wide ? 8.0 : 4.0) * (double)h->nnz, RP = 4.0 * (ties / 64.0 + g.L);   // (two-word entries: 8 B per report)
     const double mask = h->all_full ? 0.0 : ties + (h->rq ? 4.0 * ties + 2.0 * (double)h->n_rm : (double)h->n_partial * g.W * 8.0);
     const double Q = g.mut ? 4.0 * ties : 0.0;
+    const double Slp = h->lpd ? 8.0 * ties : Srho;   // log prior of the update passes without ELBO: K = 2, its difference (SlArgs::lpd)
     switch (kernel_class) {
       case VMR_KERNEL_GAMMA_MASK: *bytes = ties + (h->rq ? 4.0 * ties + 2.0 * (double)h->n_rm : (double)h->n_partial * g.W * 8.0) + Srho; break;
       case VMR_KERNEL_GAMMA_COUNTS:   // (x0p: the rounds of level 0 only are not read -- a count per tie instead)
         *bytes = ((h->x0p && g.two_pass) ? 4.0 * (double)h->stat_slots + 4.0 * ties : E) + RP + Srho;
         break;
-      case VMR_KERNEL_RHO: *bytes = E + RP + mask + 2.0 * Srho; break;
-      case VMR_KERNEL_RHO_NOSTORE: *bytes = E + RP + mask + Srho; break;   // (the log prior is read, rho is not written)
+      case VMR_KERNEL_RHO: *bytes = E + RP + mask + Slp + Srho; break;
+      case VMR_KERNEL_RHO_NOSTORE: *bytes = E + RP + mask + Slp; break;   // (the log prior is read, rho is not written)
       case VMR_KERNEL_ELBO: *bytes = E + RP + mask + Q + 2.0 * Srho; break;
       case VMR_KERNEL_RHO_ELBO: *bytes = E + RP + mask + Q + 2.0 * Srho; break;
       default: *bytes = 0.0; break;

@@ -89,7 +89,7 @@ struct VmrOpts {
   int two_pass, farl;          // VMR_TWO_PASS, VMR_FARL
   int yt, hc;                  // VMR_YT, VMR_HC: max(0, atoi), -1 when unset
   int tpb, st_tpb;             // VMR_TPB, VMR_ST_TPB: taken when a multiple of 64 in [64, 1024]
-  bool no_level0, no_x0, no_lv0r, no_level_sort, no_rlists, no_rm2, no_lp0;   // VMR_NO_*
+  bool no_level0, no_x0, no_lv0r, no_level_sort, no_rlists, no_rm2, no_lp0, no_lpd;   // VMR_NO_*
   bool always_store_rho, debug_lazy_rho;   // VMR_ALWAYS_STORE_RHO, VMR_DEBUG_LAZY_RHO
   int gen_hsum;                // VMR_GEN_HSUM: taken when > 0
   bool gen_no_lds_h;           // VMR_GEN_NO_LDS_H
@@ -155,6 +155,7 @@ struct vmr_ctx {
   unsigned long long* sumx = nullptr;
   // state
   double *rho = nullptr, *logpr = nullptr;
+  double *lpd = nullptr, *lpb = nullptr;   // K = 2 sorted lists: lp_1 - lp_0 by position [L][T] + 64 rows of slack, the layers' bounds [L][2] (SlArgs::lpd)
   double* par = nullptr;       // parameter block, see P_* offsets
   // Steady-state sweeps as hipGraphs (vmr_step and the fit loop: up to 9 plain sweeps per launch; env VMR_GRAPH=1).  Off by default:
   // measured at BASELINE config 3 (round 4, with the unwritten rho inside the graphs) 5797-5959 iterations/s replayed against
