@@ -222,6 +222,29 @@ int vmr_readout(vmr_handle h, int method, double threshold, void* out, int out_o
  * out_on_device != 0: `out` is a device pointer.  Synchronises. */
 int vmr_sample(vmr_handle h, uint64_t seed, int n_trials, uint8_t* out, int out_on_device);
 
+/* Posterior expected reports on the device -- `_calculate_mean_poisson` (model.py:1220-1293; its `pd.merge` of R.subs with data_T
+ * at :1272-1285) -- over the support S = {(l,i,j,m) : R[l,i,j,m] != 0} (every (l,i,j,m), the diagonal included, without R):
+ *   mp[l,i,j,m] = sum_k rho[l,i,j,k] (G_theta[l,m] G_lambda[l,k] + G_nu XT[l,i,j,m]),  k ascending,
+ *   XT[l,i,j,m] = X[l,j,i,m] with mutuality, else 0 (model.py:141-145, 164-170),
+ * from the CURRENT rho (after vmr_restore: the snapshot's) and the G_* that vmr_get_geometric returns as g_theta, g_lambda, g_nu.
+ * Order: lexicographic in (l,i,j,m), np.nonzero's -- also for handles made by vmr_create_coo, where the reference keeps the
+ * order of R.subs.  layer < 0: every layer; else that one (sl then holds it).  vmr_mean_poisson_size gives |S|; n is the
+ * capacity of the outputs (VMR_EINVAL below |S|); subscripts (int32) and vals: any subscript pointer may be NULL; device
+ * pointers when out_on_device != 0.  Each value is one lane's sum: bit-identical from run to run.  VMR_ENAN when a value is NaN.
+ * Synchronise; temporaries (a tie-major index of the reports, 24 B per report slot of a layer; support offsets, 16 B per tie)
+ * are freed before return, and one that does not fit in the free device memory is refused with VMR_EINVAL. */
+int vmr_mean_poisson_size(vmr_handle h, int layer, uint64_t* n);
+int vmr_mean_poisson(vmr_handle h, int layer, uint64_t n, int32_t* sl, int32_t* si, int32_t* sj, int32_t* sm,
+                     double* vals, int out_on_device);
+
+/* AUC of the expected reports against the observed ones over the support -- `utils.calculate_AUC(mp, X, mask=R)`
+ * (utils.py:40-66, i.e. sklearn's roc_curve + auc) -- of one layer, or of all (layer < 0):
+ *   P = #{S : X > 0}, Q = |S| - P,  AUC = (#{(p,n) : mp_p > mp_n} + #{(p,n) : mp_p = mp_n} / 2) / (P Q).
+ * The pair counts are exact 64-bit integer sums (bit-identical from run to run); VMR_EINVAL when 2 P Q reaches 2^63 or P 2^31.
+ * P = 0 or Q = 0: *auc = NaN (sklearn's answer, with its warning left to the caller).  n_pos / n_neg may be NULL.  Rules of
+ * vmr_mean_poisson otherwise. */
+int vmr_report_auc(vmr_handle h, int layer, double* auc, uint64_t* n_pos, uint64_t* n_neg);
+
 /* exp(E[log .]) of theta [L,M], lambda [L,K], nu from the current shape/rate parameters
  * (model.py:676-684), plus g_nu_cache = the G_exp_nu the last cache refresh held, i.e. the
  * value computed BEFORE the last nu update -- what `model.G_exp_nu` reads after `fit` and what

@@ -48,6 +48,10 @@ SIGNATURES = {
     "vmr_get_geometric": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vmr_sync": (C.c_int, [C.c_void_p]),
     "vmr_readout": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_int]),
+    "vmr_mean_poisson_size": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]),
+    "vmr_mean_poisson": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_int]),
+    "vmr_report_auc": (C.c_int, [C.c_void_p, C.c_int, _dp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "vmr_snapshot": (C.c_int, [C.c_void_p]),
     "vmr_restore": (C.c_int, [C.c_void_p]),
     "vmr_profile": (C.c_int, [C.c_void_p, C.c_int]),

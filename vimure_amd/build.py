@@ -28,7 +28,8 @@ def units(dev=False):
          ("sorted_lists", os.path.join(CSRC, "sorted_lists.hip"), extra),
          ("sweep_gen", os.path.join(CSRC, "sweep_gen.hip"), extra),   # the general kernels: any K, wide entries
          ("generate", os.path.join(CSRC, "generate.hip"), extra),     # the synthetic generators on the device
-         ("draw_prior", os.path.join(CSRC, "draw_prior.hip"), extra)]  # the initial rho prior on the device
+         ("draw_prior", os.path.join(CSRC, "draw_prior.hip"), extra),  # the initial rho prior on the device
+         ("ppc", os.path.join(CSRC, "ppc.hip"), extra)]                # expected reports and report AUC
     dev_ks = tuple(int(k) for k in os.environ.get("VMR_DEV_KS", "2").split(","))   # (VMR_DEV_KS=2,3: also the K = 3 sweep kernels)
     for k in (dev_ks if dev else KS):
         u.append((f"sweep_sl_k{k}", os.path.join(CSRC, "sweep_sl.hip"), extra + [f"-DVMR_K={k}"]))

@@ -2132,6 +2132,8 @@ static int ensure_rho(vmr_ctx* h) {
   return VMR_OK;
 }
 
+int ensure_rho_ext(vmr_ctx* h) { return ensure_rho(h); }
+
 // nu: -1 = the pass leaves nu alone; 0 = it leaves the raw sum in elbo_dev[1]; 1 = it also commits nu (sorted lists, see SlArgs::nu_acc)
 static int launch_hist(vmr_ctx* h, int nu = -1) {
   const Geo& g = h->g;

@@ -492,6 +492,9 @@ int draw_pr_rho_launch(vmr_ctx* h, int nblk, const int64_t* cuts, const uint32_t
 // in-place exclusive scan of n u32 items on the handle's stream (bsum: scratch of ceil(n / 2048) items); vimure_hip.hip
 int scan_u32(vmr_ctx* h, unsigned* a, unsigned* bsum, size_t n);
 
+// re-writes rho where the last sweep left it unwritten, before anything reads it (vmr_readout and its kin); vimure_hip.hip
+int ensure_rho_ext(vmr_ctx* h);
+
 #define CK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { g_create_err = std::string(#call) + ": " + hipGetErrorString(e_); (void)hipGetLastError(); return VMR_EHIP; } } while (0)
 
 #endif  // VMR_INTERNAL_H

@@ -355,6 +355,48 @@ class CaviEngine:
         self._check(self.lib.vmr_readout(self._h, code, float(threshold), out.ctypes.data, 0))
         return out
 
+    def _layer_arg(self, layer):
+        if layer is None:
+            return -1
+        layer = int(layer)
+        if not 0 <= layer < self.L:
+            raise ValueError(f"layer {layer} out of range [0, {self.L})")
+        return layer
+
+    def mean_poisson_size(self, layer=None):
+        """|S|: the number of (l,i,j,m) with R != 0 (every one without R), of one layer or of all."""
+        n = C.c_uint64()
+        self._check(self.lib.vmr_mean_poisson_size(self._h, self._layer_arg(layer), C.byref(n)))
+        return int(n.value)
+
+    def mean_poisson(self, layer=None, device=False):
+        """Expected reports of the current state over the support of R (`_calculate_mean_poisson`, reference
+        model.py:1220-1293): (subs, vals) with subs = 4 int32 arrays (l, i, j, m) in lexicographic order, the real layer index
+        in l.  device=True: torch tensors on the engine's GPU (vmr_mean_poisson writes them there)."""
+        la = self._layer_arg(layer)
+        n = self.mean_poisson_size(layer)
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            subs = [torch.empty(n, dtype=torch.int32, device=dev) for _ in range(4)]
+            vals = torch.empty(n, dtype=torch.float64, device=dev)
+            torch.cuda.synchronize(dev)
+            ptrs, vp = [t.data_ptr() for t in subs], vals.data_ptr()
+        else:
+            subs = [np.empty(n, np.int32) for _ in range(4)]
+            vals = np.empty(n, np.float64)
+            ptrs, vp = [a.ctypes.data for a in subs], vals.ctypes.data
+        if n:
+            self._check(self.lib.vmr_mean_poisson(self._h, la, n, *ptrs, vp, int(bool(device))))
+        return tuple(subs), vals
+
+    def report_auc(self, layer=None):
+        """(auc, n_pos, n_neg): AUC of the expected reports against X > 0 over the support of R (`utils.calculate_AUC` with
+        mask = R, reference utils.py:40-66), exact; NaN when either class is empty."""
+        a, p, q = C.c_double(), C.c_uint64(), C.c_uint64()
+        self._check(self.lib.vmr_report_auc(self._h, self._layer_arg(layer), C.byref(a), C.byref(p), C.byref(q)))
+        return a.value, int(p.value), int(q.value)
+
     def snapshot(self):
         """Keep the current posteriors on the device (`_update_optimal_parameters`, reference model.py:925-942)."""
         self._check(self.lib.vmr_snapshot(self._h))

@@ -578,6 +578,94 @@ class VimureModel(TransformerMixin, BaseEstimator):
         Y[Y >= threshold] = 1
         return Y if method == "fixed_threshold" else Y.astype("int")
 
+    # ------------------------------------------------------------------ posterior-predictive check (model.py:1220-1293)
+    def _ppc_engine(self, X, R):
+        """(engine, temporary): the engine kept by fit(keep_engine=True) when X is None, else a temporary one holding X and R
+        (routed as `fit` routes them) set to the model's best state (`*_f`, rho_f as the prior)."""
+        if not hasattr(self, "gamma_shp_f"):
+            raise ValueError("the model has not been fitted: call fit(..., keep_engine=True) first, or fit it and pass X=")
+        if X is None:
+            eng = getattr(self, "_engine", None)
+            if eng is None:
+                raise ValueError("no device state to read: fit(..., keep_engine=True) keeps one; otherwise pass the data as X= "
+                                 "(and R=)")
+            if R is not None:
+                raise ValueError("R= is taken with X= only: the kept engine holds the R of the fit")
+            return eng, False
+        if isinstance(X, pd.DataFrame) or type(X).__name__ == "Graph":
+            from ._io import read_from_edgelist, read_from_igraph
+            net = read_from_edgelist(X) if isinstance(X, pd.DataFrame) else read_from_igraph(X)
+            X = net.X
+            if R is None:
+                R = net.R
+        if R is None:
+            R = getattr(self, "R", None)
+        Xd = X if _is_torch(X) else engine_data(X, "X")
+        shape = tuple(int(s) for s in Xd.shape)
+        if shape != (self.L, self.N, self.N, self.M):
+            raise ValueError(f"X has shape {shape}, the fitted model {(self.L, self.N, self.N, self.M)}")
+        if R is not None and tuple(int(s) for s in R.shape) != shape:
+            raise ValueError("Dimensions of reporter mask (R) do not match L x N x N x M")
+        coo = is_sparse_like(Xd)
+        Rd = R
+        if R is None or _is_torch(R):
+            pass
+        elif coo:
+            Rd = R if is_sparse_like(R) else SparseTensor.fromarray(np.asarray(R) != 0)
+        else:
+            Rd = to_dense_u8(R, "R")
+            if Rd.dtype != np.uint8 or Rd.max(initial=0) > 1:
+                Rd = (Rd != 0).astype(np.uint8)
+        if coo:
+            eng = CaviEngine.from_coo(Xd.subs, Xd.vals, shape, R=None if Rd is None else Rd.subs, K=self.K,
+                                      mutuality=self.mutuality, eps=self.EPS)
+        else:
+            eng = CaviEngine(Xd, Rd, K=self.K, mutuality=self.mutuality, eps=self.EPS)
+        try:
+            eng.set_priors(self.alpha_theta, self.beta_theta, self.alpha_lambda, self.beta_lambda,
+                           self.alpha_mutuality, self.beta_mutuality)
+            eng.set_state(self.gamma_shp_f, self.gamma_rte_f, self.phi_shp_f, self.phi_rte_f, self.nu_shp_f, self.nu_rte_f,
+                          self.rho_f)
+        except BaseException:
+            eng.close()
+            raise
+        return eng, True
+
+    def calculate_mean_poisson(self, X=None, R=None, layer=None, device=False):
+        """Expected reports of the best realisation over the support of R -- the reference's `_calculate_mean_poisson`
+        (model.py:1220-1293) computed on the GPU (vmr_mean_poisson): a SparseTensor of shape (L, N, N, M) whose subs are the
+        (l, i, j, m) with R != 0 (every one without R) in lexicographic order -- np.nonzero's; for a coordinate-list R the
+        reference keeps R.subs' order instead -- and vals = sum_k rho_f (G_exp_theta_f G_exp_lambda_f + G_exp_nu_f X^T).
+        X None: the engine kept by fit(keep_engine=True); else X (and R, default the fit's) go to a temporary engine, as in
+        `fit`.  layer: that layer only.  device=True: subs and vals are torch tensors on the GPU."""
+        eng, tmp = self._ppc_engine(X, R)
+        try:
+            subs, vals = eng.mean_poisson(layer=layer, device=device)
+        finally:
+            if tmp:
+                eng.close()
+        shape = (self.L, self.N, self.N, self.M)
+        if not device:
+            return SparseTensor(subs, vals, shape=shape)
+        st = SparseTensor.__new__(SparseTensor)   # (tensors stay on the device: no conversion)
+        st.subs, st.vals, st.shape, st.ndim, st.dtype = tuple(subs), vals, shape, 4, vals.dtype
+        return st
+
+    def report_auc(self, X=None, R=None, layer=None):
+        """AUC of the expected reports against the observed ones (X > 0) over the support of R: `utils.calculate_AUC(mp, X,
+        mask=R)` (reference utils.py:40-66), exact, on the GPU (vmr_report_auc); of one layer or of the whole tensor.  NaN with
+        a warning when the support holds no positive or no negative.  Engine as in `calculate_mean_poisson`."""
+        eng, tmp = self._ppc_engine(X, R)
+        try:
+            auc, n_pos, n_neg = eng.report_auc(layer=layer)
+        finally:
+            if tmp:
+                eng.close()
+        if n_pos == 0 or n_neg == 0:
+            warnings.warn("No %s reports in the support: the AUC is undefined" % ("positive" if n_pos == 0 else "negative"),
+                          UserWarning)
+        return float(auc)
+
     def predict(self, X=None, method="rho_max", threshold=None):
         """Alias of `get_inferred_model` (the reference's experiment wrapper calls it predict)."""
         return self.get_inferred_model(method=method, threshold=threshold)
