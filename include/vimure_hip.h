@@ -245,6 +245,31 @@ int vmr_mean_poisson(vmr_handle h, int layer, uint64_t n, int32_t* sl, int32_t* 
  * vmr_mean_poisson otherwise. */
 int vmr_report_auc(vmr_handle h, int layer, double* auc, uint64_t* n_pos, uint64_t* n_neg);
 
+/* Network statistics of n_samples posterior samples of Y, computed where rho lives: sample s is exactly what
+ * vmr_sample(h, seed + s, n_trials, ..) writes (seed + s mod 2^64; the same Philox draw), and only the statistics come back.
+ * counts: host uint64 [n_samples][L][4], over ALL (i, j) of a layer, the diagonal included:
+ *   0 edges   #{Y > 0}                          (Y > 0).sum()
+ *   1 weight  sum Y                             Y.sum()
+ *   2 mutual  #{(i,j) : Y_ij > 0 and Y_ji > 0}  np.logical_and(Y > 0, Y.T > 0).sum()  -- mutual / weight is the reference's
+ *                                               utils.calculate_overall_reciprocity (utils.py:69-70)
+ *   3 tp      #{Y > 0 and y_ref > 0}            0 without y_ref
+ * y_ref: uint8 [L,N,N] (a device pointer when y_ref_on_device != 0) or NULL.  deg_out / deg_in: host int32 [n_samples][L][N],
+ * deg_out[s][l][i] = #{j : Y_ij > 0}, deg_in[s][l][j] = #{i : Y_ij > 0}; either may be NULL.
+ * Reads the CURRENT rho (after vmr_restore: the snapshot's), once per chunk of samples; any K, any n_trials >= 1, both data
+ * formats.  All sums are integer sums: bit-identical from run to run.  The chunk's temporaries (L N^2 bytes per sample, half
+ * of the free device memory at most, 256 samples at most) are freed before return; a single sample that does not fit is
+ * refused with VMR_EINVAL.  n_samples < 1, n_trials < 1 or counts NULL: VMR_EINVAL; before vmr_set_state: VMR_ESTATE.
+ * Synchronises. */
+int vmr_sample_stats(vmr_handle h, uint64_t seed, int n_samples, int n_trials, const uint8_t* y_ref, int y_ref_on_device,
+                     uint64_t* counts, int32_t* deg_out, int32_t* deg_in);
+
+/* The same quantities in expectation under q(Y) = prod rho, no sampling: with p_ij = sum_{k>=1} rho_ijk (k ascending),
+ *   out[l] = (sum p_ij, sum_ij sum_k k rho_ijk, sum_ij p_ij p_ji, sum p_ij (1 - p_ij))        host double [L][4]
+ * -- expected edges, expected weight, the numerator of the expected reciprocity (all ordered pairs: the diagonal enters as
+ * p_ii^2; out[2] / out[0] is the quotient for K = 2) and the variance of `edges`.  Doubles summed by a fixed two-stage tree
+ * (no atomics): bit-identical from run to run.  Temporary: 8 L N^2 bytes (VMR_EINVAL when that does not fit).  Synchronises. */
+int vmr_expected_stats(vmr_handle h, double* out);
+
 /* exp(E[log .]) of theta [L,M], lambda [L,K], nu from the current shape/rate parameters
  * (model.py:676-684), plus g_nu_cache = the G_exp_nu the last cache refresh held, i.e. the
  * value computed BEFORE the last nu update -- what `model.G_exp_nu` reads after `fit` and what

@@ -44,6 +44,8 @@ SIGNATURES = {
     "vmr_commit_nu_dev": (C.c_int, [C.c_void_p, C.c_void_p]),
     "vmr_stream": (C.c_void_p, [C.c_void_p]),
     "vmr_sample": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_int]),
+    "vmr_sample_stats": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vmr_expected_stats": (C.c_int, [C.c_void_p, C.c_void_p]),
     "vmr_get_state": (C.c_int, [C.c_void_p] + [C.c_void_p] * 7),
     "vmr_get_geometric": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vmr_sync": (C.c_int, [C.c_void_p]),

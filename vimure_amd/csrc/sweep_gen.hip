@@ -17,6 +17,7 @@
 // hold 64-bit integers in this mode, and gen_s1 does between the finalize kernels.  The readers convert them (det_back).  Sums of
 // one thread over a fixed share, and the shuffle / block trees, are already the same every run.
 #include "sweep_gen.h"
+#include "sample_draw.h"
 
 // v 2^sh rounded to nearest as a 64-bit integer through the 1.5 * 2^52 trick: |v| scale < 2^51 (the host caps det_sh by the largest count)
 __device__ __forceinline__ unsigned long long gen_fxm(double v, double scale) {
@@ -668,22 +669,7 @@ __global__ __launch_bounds__(64) void k_sample_gen(const double* __restrict__ rh
     const double* r = rho + q * K;
     size_t t = q;
     if (perm) { const size_t l = q / T, pos = q - l * T; t = l * T + perm[l * NS * 64 + pos]; }
-    for (int k = 0; k < K; ++k) cnt[k * 64] = 0u;
-    for (int n = 0; n < n_trials; n += 2) {
-      unsigned c[4] = {(unsigned)t, (unsigned)((unsigned long long)t >> 32), (unsigned)(n >> 1), 0u};
-      philox4x32_10(c, (unsigned)seed, (unsigned)(seed >> 32));
-      for (int i = 0; i < 2; ++i) {
-        if (n + i < n_trials) {
-          const double u = ((double)(c[2 * i] >> 5) * 67108864.0 + (double)(c[2 * i + 1] >> 6)) * (1.0 / 9007199254740992.0);
-          int sel = 0;
-          double acc = r[0];
-          for (int k = 1; k < K; ++k) { if (u >= acc) sel = k; acc += r[k]; }
-          cnt[sel * 64] += 1u;
-        }
-      }
-    }
-    int best = 0;
-    for (int k = 1; k < K; ++k) if (cnt[k * 64] > cnt[best * 64]) best = k;
+    const int best = draw_tie<true>(r, K, n_trials, seed, t, cnt);   // (sample_draw.h)
     out[t] = (uint8_t)best;
   }
 }

@@ -18,6 +18,7 @@
 #include "vmr_internal.h"
 #include "sweep_sl.h"
 #include "sweep_gen.h"
+#include "sample_draw.h"
 
 thread_local std::string g_create_err;
 
@@ -1741,27 +1742,7 @@ __global__ __launch_bounds__(256) void k_sample(const double* __restrict__ rho, 
     const double* r = rho + q * K;
     size_t t = q;
     if (perm) { const size_t l = q / T, pos = q - l * T; t = l * T + perm[l * NS * 64 + pos]; }
-    unsigned cnt[KMAX];
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k) cnt[k] = 0u;
-    for (int n = 0; n < n_trials; n += 2) {
-      unsigned c[4] = {(unsigned)t, (unsigned)((unsigned long long)t >> 32), (unsigned)(n >> 1), 0u};
-      philox4x32_10(c, (unsigned)seed, (unsigned)(seed >> 32));
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        if (n + i < n_trials) {
-          const double u = ((double)(c[2 * i] >> 5) * 67108864.0 + (double)(c[2 * i + 1] >> 6)) * (1.0 / 9007199254740992.0);
-          int sel = 0;
-          double acc = r[0];
-          for (int k = 1; k < K; ++k) { if (u >= acc) sel = k; acc += r[k]; }   // first k with u < cumulative sum; the last one catches the rest
-#pragma unroll
-          for (int k = 0; k < KMAX; ++k) cnt[k] += (sel == k) ? 1u : 0u;
-        }
-      }
-    }
-    int best = 0;
-#pragma unroll
-    for (int k = 1; k < KMAX; ++k) if (k < K && cnt[k] > cnt[best]) best = k;
+    const int best = draw_tie<false>(r, K, n_trials, seed, t, nullptr);   // (sample_draw.h)
     out[t] = (uint8_t)best;
   }
 }
@@ -2416,6 +2397,7 @@ static void read_opts(VmrOpts& o) {
   o.gen_hsum = num("VMR_GEN_HSUM", 0);
   o.gen_no_lds_h = set("VMR_GEN_NO_LDS_H");
   o.gen_dbg = num("VMR_GEN_DBG", 0);
+  o.netstats_chunk = std::max(0, num("VMR_NETSTATS_CHUNK", 0));
   o.batch_fg = set("VMR_BATCH_FG") ? std::max(1, std::min(FG_G, num("VMR_BATCH_FG", 0))) : 0;
   if (const char* t = getenv("VMR_DEBUG_TIMES")) snprintf(o.debug_times, sizeof o.debug_times, "%s", t);
 }

@@ -95,6 +95,7 @@ struct VmrOpts {
   bool gen_no_lds_h;           // VMR_GEN_NO_LDS_H
   int gen_dbg;                 // VMR_GEN_DBG (-DGEN_DEBUG builds)
   int batch_fg;                // VMR_BATCH_FG: clamped to [1, FG_G], 0 when unset
+  int netstats_chunk;          // VMR_NETSTATS_CHUNK: samples per chunk of vmr_sample_stats at most (tests: several chunks); 0: sized from free memory
   char debug_times[256];       // VMR_DEBUG_TIMES (-DSL_DEBUG builds): "" when unset
 };
 

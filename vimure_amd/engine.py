@@ -342,6 +342,49 @@ class CaviEngine:
         self._check(self.lib.vmr_sample(self._h, int(seed) & (2 ** 64 - 1), int(n_trials), y.ctypes.data, 0))
         return y
 
+    def sample_stats(self, seed, n_samples, n_trials=1, Y_ref=None, degrees=False):
+        """Network statistics of n_samples posterior samples, computed on the device (vmr_sample_stats): sample s is
+        `self.sample(seed + s, n_trials)`, and only the counts come back.  Returns a dict of NumPy arrays: `edges` #{Y > 0},
+        `weight` sum Y, `mutual` #{Y_ij > 0 and Y_ji > 0}, `tp` #{Y > 0 and Y_ref > 0} (zeros without Y_ref), each int64 [S, L]
+        over all (i, j) of a layer; with degrees=True also `deg_out`, `deg_in` int32 [S, L, N].  Y_ref: [L,N,N], a NumPy array
+        (compared with 0) or a uint8 CUDA tensor."""
+        S = int(n_samples)
+        shape = (self.L, self.N, self.N)
+        yp, ydev, keep = None, 0, None
+        if Y_ref is not None:
+            if _is_torch(Y_ref):
+                import torch
+                if (not Y_ref.is_cuda or Y_ref.dtype != torch.uint8 or not Y_ref.is_contiguous()
+                        or tuple(Y_ref.shape) != shape):
+                    raise ValueError(f"device Y_ref must be a contiguous torch.uint8 GPU tensor of shape {shape}")
+                torch.cuda.synchronize(Y_ref.device)
+                yp, ydev, keep = Y_ref.data_ptr(), 1, Y_ref
+            else:
+                Y_ref = np.asarray(Y_ref)
+                if Y_ref.shape != shape:
+                    raise ValueError(f"Y_ref has shape {Y_ref.shape}, the engine's networks {shape}")
+                keep = np.ascontiguousarray(Y_ref > 0, dtype=np.uint8)
+                yp = keep.ctypes.data
+        counts = np.zeros((max(S, 0), self.L, 4), np.uint64)
+        dout = np.zeros((max(S, 0), self.L, self.N), np.int32) if degrees else None
+        din = np.zeros((max(S, 0), self.L, self.N), np.int32) if degrees else None
+        self._check(self.lib.vmr_sample_stats(self._h, int(seed) & (2 ** 64 - 1), S, int(n_trials), yp, ydev, counts.ctypes.data,
+                                              dout.ctypes.data if degrees else None, din.ctypes.data if degrees else None))
+        del keep
+        c = counts.astype(np.int64)
+        out = {"edges": c[..., 0], "weight": c[..., 1], "mutual": c[..., 2], "tp": c[..., 3]}
+        if degrees:
+            out["deg_out"], out["deg_in"] = dout, din
+        return out
+
+    def expected_stats(self):
+        """The statistics of `sample_stats` in expectation under q(Y) = prod rho (vmr_expected_stats), with p_ij = sum_{k>=1}
+        rho_ijk: dict of float64 [L] arrays `edges` sum p, `weight` sum_ij sum_k k rho_ijk, `mutual` sum_ij p_ij p_ji (all ordered
+        pairs: the diagonal enters as p_ii^2) and `edges_var` sum p (1 - p)."""
+        out = np.zeros((self.L, 4), np.float64)
+        self._check(self.lib.vmr_expected_stats(self._h, out.ctypes.data))
+        return {"edges": out[:, 0].copy(), "weight": out[:, 1].copy(), "mutual": out[:, 2].copy(), "edges_var": out[:, 3].copy()}
+
     def sub_step(self, which):
         self._check(self.lib.vmr_sub_step(self._h, int(which)))
 

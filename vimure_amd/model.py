@@ -666,6 +666,33 @@ class VimureModel(TransformerMixin, BaseEstimator):
                           UserWarning)
         return float(auc)
 
+    def posterior_network_stats(self, n_samples=100, seed=None, n_trials=1, Y_true=None, degrees=False, X=None, R=None):
+        """Posterior distribution of the network's summary statistics, computed on the GPU (vmr_sample_stats,
+        vmr_expected_stats): n_samples draws of Y from q(Y) -- sample s is `sample_inferred_model(N=n_trials, seed=seed + s,
+        device=True)[0]` -- reduced where rho lives to edges, weight, mutual pairs and, with Y_true [L,N,N], true positives (and
+        the degrees when asked); only those counts cross PCIe.  Returns a `netstats.NetworkStats`: the counts, reciprocity
+        (`utils.calculate_overall_reciprocity` per sample), density, precision / recall / F1 against Y_true, the analytic
+        expectations (`expected`) and `summary()`.  seed None: the fit's.  Engine as in `calculate_mean_poisson`."""
+        from .netstats import NetworkStats
+        if seed is None:
+            seed = self.seed
+        ref_edges = None
+        if Y_true is not None and not _is_torch(Y_true):
+            Y_true = np.asarray(Y_true)
+            if Y_true.shape != (self.L, self.N, self.N):
+                raise ValueError(f"Y_true has shape {Y_true.shape}, the fitted model's networks {(self.L, self.N, self.N)}")
+            ref_edges = (Y_true > 0).sum(axis=(1, 2))
+        eng, tmp = self._ppc_engine(X, R)
+        try:
+            counts = eng.sample_stats(seed, n_samples, n_trials=n_trials, Y_ref=Y_true, degrees=degrees)
+            expected = eng.expected_stats()
+        finally:
+            if tmp:
+                eng.close()
+        if Y_true is not None and ref_edges is None:
+            ref_edges = (Y_true > 0).sum(dim=(1, 2)).cpu().numpy()
+        return NetworkStats(self.N, counts, expected=expected, ref_edges=ref_edges, seed=seed, n_trials=n_trials)
+
     def predict(self, X=None, method="rho_max", threshold=None):
         """Alias of `get_inferred_model` (the reference's experiment wrapper calls it predict)."""
         return self.get_inferred_model(method=method, threshold=threshold)
