@@ -270,6 +270,34 @@ int vmr_sample_stats(vmr_handle h, uint64_t seed, int n_samples, int n_trials, c
  * (no atomics): bit-identical from run to run.  Temporary: 8 L N^2 bytes (VMR_EINVAL when that does not fit).  Synchronises. */
 int vmr_expected_stats(vmr_handle h, double* out);
 
+/* Posterior predictive checks: n_rep replicated datasets drawn from the fitted model over the support of the handle's own R and
+ * reduced where they are drawn -- no replicate is ever written -- and the same reduction of the observed data.
+ * Replicate r: Y_r is exactly what vmr_sample(h, seed_y + r, n_trials, ..) writes (mod 2^64; the CURRENT rho, after vmr_restore
+ * the snapshot's); lam[l,i,j] = lambda[r][l][Y_r[l,i,j]] (the table as given, per layer); for every unordered pair i < j, layer l
+ * and reporter m with R[l,i,j,m] != 0 or R[l,j,i,m] != 0 the pair draw of vmr_generate_x with seed seed_x + r, rates
+ * lam[l,i,j] theta[r][l][m] and lam[l,j,i] theta[r][l][m], and eta[r]: the numbers vmr_generate_x(lam_dev = lam, theta[r], eta[r],
+ * seed_x + r) puts at (l,i,j,m) and (l,j,i,m), not clamped.  A direction whose own R entry is 0 is dropped; a draw depends on
+ * (seed, l, i, j, m) only.  Diagonal ties hold no replicated report.  S and "without R" as for vmr_mean_poisson.
+ * counts: host uint64 [n_rep][L][VMR_PPC_NSTAT], exact integer sums over S of a layer (x: the count at a support element):
+ *   0 n_pos          #{S : x > 0}
+ *   1 total          sum x
+ *   2 sumsq          sum x^2
+ *   3 mutual         #{(i,j,m) in S, i != j : x_ijm > 0, (j,i,m) in S and x_jim > 0}   (ordered: a reciprocated pair counts twice)
+ *   4 ties_reported  #{(i,j) : some m in S with x > 0}                                  (the union baseline)
+ *   5 ties_agreed    #{(i,j) : at least two m in S with x > 0}                          (the intersection of the self-reporter setting)
+ * by_reporter: host uint64 [n_rep][L][M][2], (n_pos, total) of every reporter, or NULL.  theta [n_rep][L][M], lambda [n_rep][L][K],
+ * eta [n_rep] are host arrays.  Any K, any n_trials >= 1, both data formats, every mask layout, handles of vmr_create_coo.
+ * A chunk of replicates keeps L N^2 bytes of Y per replicate on the device (half of the free memory at most, 256 replicates at
+ * most; freed before return; VMR_EINVAL when one does not fit).  VMR_EINVAL before any launch: n_rep < 1, n_trials < 1, a NULL
+ * theta / lambda / eta / counts, an eta outside [0, 1), a negative or non-finite theta or lambda.  VMR_ESTATE before
+ * vmr_set_state.  Bit-identical from run to run.  Synchronises.
+ * vmr_ppc_observed: the same statistics of the handle's own X over S (counts [L][VMR_PPC_NSTAT], by_reporter [L][M][2] or NULL);
+ * observed diagonal counts enter where S holds the diagonal.  Report-list handles: the temporaries of vmr_mean_poisson. */
+#define VMR_PPC_NSTAT 6
+int vmr_ppc_replicates(vmr_handle h, int n_rep, uint64_t seed_y, uint64_t seed_x, int n_trials, const double* theta,
+                       const double* lambda, const double* eta, uint64_t* counts, uint64_t* by_reporter);
+int vmr_ppc_observed(vmr_handle h, uint64_t* counts, uint64_t* by_reporter);
+
 /* exp(E[log .]) of theta [L,M], lambda [L,K], nu from the current shape/rate parameters
  * (model.py:676-684), plus g_nu_cache = the G_exp_nu the last cache refresh held, i.e. the
  * value computed BEFORE the last nu update -- what `model.G_exp_nu` reads after `fit` and what

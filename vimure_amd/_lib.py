@@ -12,6 +12,8 @@ VMR_OK, VMR_EINVAL, VMR_EHIP, VMR_ENAN, VMR_ESTATE = 0, -1, -2, -3, -4
 STEP_GAMMA, STEP_PHI, STEP_RHO, STEP_NU = 0, 1, 2, 3
 KERNEL_GAMMA_MASK, KERNEL_GAMMA_COUNTS, KERNEL_PHI, KERNEL_RHO, KERNEL_ELBO, KERNEL_FINALIZE, KERNEL_RHO_ELBO, KERNEL_RHO_NOSTORE = range(8)
 READ_RHO_MAX, READ_RHO_MEAN, READ_THRESHOLD = 0, 1, 2
+PPC_NSTAT = 6
+PPC_STAT_NAMES = ["n_pos", "total", "sumsq", "mutual", "ties_reported", "ties_agreed"]
 KERNEL_NAMES = ["gamma_mask", "gamma_counts", "phi", "rho", "elbo", "finalize", "rho_elbo", "rho_nostore"]
 
 _dp = C.POINTER(C.c_double)
@@ -46,6 +48,9 @@ SIGNATURES = {
     "vmr_sample": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_int]),
     "vmr_sample_stats": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vmr_expected_stats": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "vmr_ppc_replicates": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]),
+    "vmr_ppc_observed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "vmr_get_state": (C.c_int, [C.c_void_p] + [C.c_void_p] * 7),
     "vmr_get_geometric": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vmr_sync": (C.c_int, [C.c_void_p]),

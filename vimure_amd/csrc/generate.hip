@@ -10,49 +10,9 @@
 // Not the reference's RandomState stream (a GPU cannot follow MT19937 draw by draw): the host classes keep that exact mode
 // (vimure_amd/synthetic.py, pinned bit for bit by tests/golden/K_generators.npz); this one is held to it by moments.
 #include "vmr_internal.h"
+#include "report_draw.h"
 
 namespace {
-
-struct Rng {   // a stream of uniforms for one (layer, pair, reporter): Philox calls as needed
-  unsigned k0, k1, c0, c1, c2, n, have;
-  unsigned w[4];
-  __device__ Rng(unsigned long long seed, unsigned l, unsigned long long pair, unsigned m)
-      : k0((unsigned)seed), k1((unsigned)(seed >> 32)), c0((unsigned)pair), c1((unsigned)(pair >> 32)), c2(m ^ (l << 20)), n(0), have(0) {}
-  __device__ double uniform() {   // (0, 1): 53 bits, never 0
-    if (have < 2) {
-      unsigned c[4] = {c0, c1, c2, n++};
-      philox4x32_10(c, k0, k1);
-      w[0] = c[0]; w[1] = c[1]; w[2] = c[2]; w[3] = c[3];
-      have = 4;
-    }
-    const unsigned a = w[have - 1], b = w[have - 2];
-    have -= 2;
-    return ((double)(a >> 5) * 67108864.0 + (double)(b >> 6) + 0.5) * (1.0 / 9007199254740992.0);
-  }
-};
-
-// Poisson(rate): inversion by sequential search below 30 (one uniform, about `rate` steps), Hoermann's transformed rejection (PTRS,
-// 1993) above -- the algorithm NumPy's legacy generator uses for rate >= 10 -- both exact.
-__device__ unsigned poisson_draw(double rate, Rng& g) {
-  if (!(rate > 0.0)) return 0u;
-  if (rate < 30.0) {
-    const double u = g.uniform();
-    double p = exp(-rate), cdf = p;
-    unsigned k = 0;
-    while (u > cdf && k < 1000u) { ++k; p *= rate / (double)k; cdf += p; }
-    return k;
-  }
-  const double slam = sqrt(rate), loglam = log(rate), b = 0.931 + 2.53 * slam, a = -0.059 + 0.02483 * b;
-  const double invalpha = 1.1239 + 1.1328 / (b - 3.4), vr = 0.9277 - 3.6224 / (b - 2.0);
-  for (int it = 0; it < 64; ++it) {
-    const double U = g.uniform() - 0.5, V = g.uniform(), us = 0.5 - fabs(U);
-    const double kf = floor((2.0 * a / us + b) * U + rate + 0.43);
-    if (us >= 0.07 && V <= vr) return (unsigned)kf;
-    if (kf < 0.0 || (us < 0.013 && V > us)) continue;
-    if (log(V) + log(invalpha) - log(a / (us * us) + b) <= -rate + kf * loglam - lgamma(kf + 1.0)) return (unsigned)kf;
-  }
-  return (unsigned)(rate + 0.5);   // (not reached in practice: acceptance is > 0.9 per trial)
-}
 
 // Y[l,i,j] ~ Poisson(w[grp_i][grp_j]) clipped to K - 1, zero diagonal (synthetic.py:548-571, 639-667)
 __global__ __launch_bounds__(256) void k_gen_y(uint8_t* __restrict__ Y, const double* __restrict__ w, const int* __restrict__ grp, int L, int N, int C, int K,
@@ -81,7 +41,7 @@ __global__ __launch_bounds__(256) void k_gen_x(uint8_t* __restrict__ X, const ui
                                                const double* __restrict__ theta, int L, int N, int M, double eta, double lambda_diff,
                                                unsigned long long seed, int self_rep) {
   const unsigned long long T = (unsigned long long)N * N, npair = (unsigned long long)L * T;
-  const double inv = 1.0 / (1.0 - eta * eta);
+  const double inv = pair_inv(eta);
   for (unsigned long long q = blockIdx.x; q < npair; q += gridDim.x) {
     const unsigned long long l = q / T, t = q - l * T, i = t / N, j = t - i * N;
     if (j <= i) continue;   // every unordered pair once
@@ -91,17 +51,8 @@ __global__ __launch_bounds__(256) void k_gen_x(uint8_t* __restrict__ X, const ui
     uint8_t* xb = X + tji * M;
     for (int m = threadIdx.x; m < M; m += 256) {
       if (self_rep && (unsigned long long)m != i && (unsigned long long)m != j) continue;   // (the tensor was zeroed by the caller)
-      const double th = theta[l * M + m], a = la * th, b = lb * th;
-      Rng g(seed, (unsigned)l, t, (unsigned)m);
-      const bool ij_first = g.uniform() < 0.5;
       unsigned xij, xji;
-      if (ij_first) {
-        xij = poisson_draw((a + eta * b) * inv, g);
-        xji = poisson_draw(b + eta * (double)xij, g);
-      } else {
-        xji = poisson_draw((b + eta * a) * inv, g);
-        xij = poisson_draw(a + eta * (double)xji, g);
-      }
+      pair_draw(seed, (unsigned)l, t, (unsigned)m, la, lb, theta[l * M + m], eta, inv, xij, xji);   // report_draw.h
       xa[m] = (uint8_t)(xij > 255u ? 255u : xij);
       xb[m] = (uint8_t)(xji > 255u ? 255u : xji);
     }

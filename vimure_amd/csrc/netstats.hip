@@ -28,7 +28,6 @@ namespace {
 
 #define NS_TILE 64
 #define NS_BSTRIDE 68   // bytes per row of the transposed tile in LDS: 17 words, odd, so a wave's column reads spread over the banks
-#define NS_CHUNK_MAX 256
 
 // A chunk of C samples drawn from one read of rho: Y[s][q's tie] = the draw of (seed0 + s, tie), s in [0, C).
 // LDS_CNT: K > KMAX, the trial counts in LDS (64 threads, [K][64] words); KC > 0: K = KC, the row is held in registers.
@@ -184,7 +183,10 @@ struct Tmp {
   }
 };
 
-static int launch_draw(vmr_ctx* h, uint8_t* Y, unsigned long long seed0, int C, int n_trials) {
+}  // namespace
+
+// declared in vmr_internal.h: the replicates of the posterior predictive check (ppc_rep.hip) draw their Y with it too
+int ns_draw_chunk(vmr_ctx* h, uint8_t* Y, unsigned long long seed0, int C, int n_trials) {
   const Geo& g = h->g;
   const size_t T = (size_t)g.N * g.N, ties = (size_t)g.L * T, NS = (T + 63) / 64;
   if (g.K > KMAX) {
@@ -200,8 +202,6 @@ static int launch_draw(vmr_ctx* h, uint8_t* Y, unsigned long long seed0, int C, 
   HIPCHK(h, hipGetLastError());
   return VMR_OK;
 }
-
-}  // namespace
 
 extern "C" int vmr_sample_stats(vmr_handle h, uint64_t seed, int n_samples, int n_trials, const uint8_t* y_ref, int y_ref_on_device,
                                 uint64_t* counts, int32_t* deg_out, int32_t* deg_in) {
@@ -246,7 +246,7 @@ extern "C" int vmr_sample_stats(vmr_handle h, uint64_t seed, int n_samples, int 
   for (size_t s0 = 0; s0 < (size_t)n_samples; s0 += C) {
     const int c = (int)std::min<size_t>(C, (size_t)n_samples - s0);
     HIPCHK(h, hipMemsetAsync(cd, 0, (size_t)c * cnt_b, h->stream));
-    if ((rc = launch_draw(h, Y, (unsigned long long)seed + (unsigned long long)s0, c, n_trials))) return rc;   // (mod 2^64)
+    if ((rc = ns_draw_chunk(h, Y, (unsigned long long)seed + (unsigned long long)s0, c, n_trials))) return rc;   // (mod 2^64)
     hipLaunchKernelGGL(k_ns_reduce, dim3(nstrip, (unsigned)g.L, (unsigned)c), dim3(256), 0, h->stream, Y, yref_dev, g.N, g.L, cd, dout, din);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(counts + s0 * g.L * 4, cd, (size_t)c * cnt_b, hipMemcpyDeviceToHost, h->stream));

@@ -20,6 +20,7 @@
 // wave's binary searches then share cache lines) and every negative adds 2 #(pos > s) + #(pos = s), summed in uint64 -- exact,
 // order-free, the same from run to run.
 #include "vmr_internal.h"
+#include "ppc_layer.h"
 
 namespace {
 
@@ -27,37 +28,6 @@ namespace {
 #define PPC_MODE_WRITE 0
 #define PPC_MODE_POS 1
 #define PPC_MODE_NEG 2
-
-// one layer of a handle, as the kernels see it
-struct PpcLayer {
-  int l, N, M, Mp, K, W, mut, mb;
-  size_t T;
-  const uint8_t* X;                 // dense tiles: [T][Mp] of the layer, else null
-  const uint64_t* Rb;               // [T][W] mask words of the layer, or null
-  const uint8_t* cls;               // [T] class of the mask row: 0 empty, 1 all ones, 2 partial
-  const unsigned* rq;               // mask lists: [T + 1] first listed reporter of a row (relative to Rm), or null
-  const unsigned short* Rm;
-  const unsigned long long* ik;     // report lists: tie-major index, keys tie << mb | m (sorted) ...
-  const unsigned* iv;               // ... values x << 1 | R ...
-  const unsigned* ip;               // ... row starts [T + 1]
-  const unsigned* inv;              // tie -> sorted position (rho by position), or null (rho by tie)
-  const double* rho;                // [T][K] of the layer
-  const double* gth;                // G_theta [Mp] of the layer, G_lambda [K], G_nu (the current parameters, vmr_get_geometric)
-  const double* gla;
-  const double* gnu;
-};
-
-// count X[t, m] of the layer: the dense row, or the tie's row of the index
-__device__ __forceinline__ unsigned ppc_x(const PpcLayer& p, size_t t, unsigned m) {
-  if (p.X) return p.X[t * p.Mp + m];
-  unsigned a = p.ip[t], b = p.ip[t + 1];
-  const unsigned long long key = ((unsigned long long)t << p.mb) | m;
-  while (a < b) {
-    const unsigned c = a + ((b - a) >> 1);
-    if (p.ik[c] < key) a = c + 1; else b = c;
-  }
-  return (a < p.ip[t + 1] && p.ik[a] == key) ? (p.iv[a] >> 1) : 0u;
-}
 
 // the score in the reference's order and roundings: PoissonMean_k = theta_m lambda_k + nu XT, then sum_k rho_k PoissonMean_k,
 // k ascending, every product and sum rounded on its own (no contraction to FMA: the AUC counts exact ties, and a value one ulp
@@ -233,51 +203,13 @@ __global__ __launch_bounds__(256) void k_ppc_rank(const unsigned long long* __re
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
-// temporaries of one call: freed on every exit path; an allocation that does not fit in the free device memory is refused
-struct Tmp {
-  vmr_ctx* h;
-  std::vector<void*> ptrs;
-  explicit Tmp(vmr_ctx* h_) : h(h_) {}
-  ~Tmp() { for (void* q : ptrs) (void)hipFree(q); }
-  Tmp(const Tmp&) = delete;
-  Tmp& operator=(const Tmp&) = delete;
-  template <class T_>
-  int get(T_** out, size_t bytes, const char* what) {
-    *out = nullptr;
-    size_t fr = 0, tot = 0;
-    HIPCHK(h, hipMemGetInfo(&fr, &tot));
-    if (bytes + (64u << 20) > fr) {
-      char msg[256];
-      snprintf(msg, sizeof msg, "%s needs %.2f GB of device memory, %.2f GB are free", what, bytes / 1e9, fr / 1e9);
-      return fail(h, VMR_EINVAL, msg);
-    }
-    void* q = nullptr;
-    HIPCHK(h, hipMalloc(&q, bytes ? bytes : 8));
-    ptrs.push_back(q);
-    *out = reinterpret_cast<T_*>(q);
-    return VMR_OK;
-  }
-  void release(void* q) {
-    for (auto& e : ptrs) if (e == q) { (void)hipFree(e); e = nullptr; }
-  }
-};
-
 static unsigned grid_for(size_t n, size_t per = 256, size_t cap = 16384) { return (unsigned)std::max<size_t>(1, std::min<size_t>(cap, (n + per - 1) / per)); }
 
-// One layer prepared for the walks: the index (report lists), tie -> position, the support offsets off [T + 1] and, with
-// positives, poff [T + 1].  Its temporaries live in `tmp`; release() gives the layer's memory back before the next one.
-struct LayerPrep {
-  PpcLayer p;
-  unsigned long long *off = nullptr, *poff = nullptr;
-  unsigned long long nsup = 0, npos = 0;
-  std::vector<void*> mine;
-};
+}  // namespace
 
-static int prep_layer(vmr_ctx* h, Tmp& tm, int l, bool positives, bool walk, LayerPrep& lp) {
+int ppc_layer_mask(vmr_ctx* h, int l, PpcLayer& p) {
   const Geo& g = h->g;
-  const size_t T = (size_t)g.N * g.N, NS = (T + 63) / 64;
-  const ParOff o = par_off(g.L, g.Mp, g.K);
-  PpcLayer& p = lp.p;
+  const size_t T = (size_t)g.N * g.N;
   memset(&p, 0, sizeof p);
   p.l = l; p.N = g.N; p.M = g.M; p.Mp = g.Mp; p.K = g.K; p.W = g.W; p.mut = g.mut; p.T = T;
   p.mb = 1;
@@ -290,13 +222,22 @@ static int prep_layer(vmr_ctx* h, Tmp& tm, int l, bool positives, bool walk, Lay
     HIPCHK(h, hipMemcpy(&rb, h->rbase + l, 8, hipMemcpyDeviceToHost));
     p.Rm = h->Rm + rb;
   }
+  return VMR_OK;
+}
+
+int ppc_prep_layer(vmr_ctx* h, Tmp& tm, int l, bool positives, bool walk, LayerPrep& lp, bool want_index) {
+  const Geo& g = h->g;
+  const size_t T = (size_t)g.N * g.N, NS = (T + 63) / 64;
+  const ParOff o = par_off(g.L, g.Mp, g.K);
+  PpcLayer& p = lp.p;
+  int rc;
+  if ((rc = ppc_layer_mask(h, l, p))) return rc;
   p.rho = h->rho + (size_t)l * T * g.K;
   p.gth = h->par + o.G_th + (size_t)l * g.Mp;
   p.gla = h->par + o.G_la + (size_t)l * g.K;
   p.gnu = h->par + o.sc + SC_G_NU;
   auto take = [&](auto** q, size_t bytes, const char* what) { const int rc = tm.get(q, bytes, what); if (!rc) lp.mine.push_back(*q); return rc; };
-  int rc;
-  const bool index = h->sparse && (positives || (walk && g.mut));   // the counts are needed: positives, or XT
+  const bool index = h->sparse && (want_index || positives || (walk && g.mut));   // the counts are needed: positives, or XT
   if (h->sparse) {
     if (walk) {
       unsigned* inv = nullptr;
@@ -355,10 +296,12 @@ static int prep_layer(vmr_ctx* h, Tmp& tm, int l, bool positives, bool walk, Lay
   return VMR_OK;
 }
 
-static void release_layer(Tmp& tm, LayerPrep& lp) {
+void ppc_release_layer(Tmp& tm, LayerPrep& lp) {
   for (void* q : lp.mine) tm.release(q);
   lp.mine.clear();
 }
+
+namespace {
 
 // lanes per tie: a support row holds up to M reporters
 static int group_lanes(const vmr_ctx* h) {
@@ -417,9 +360,9 @@ extern "C" int vmr_mean_poisson_size(vmr_handle h, int layer, uint64_t* n) {
   unsigned long long tot = 0;
   for (int l = (layer < 0 ? 0 : layer); l < (layer < 0 ? h->g.L : layer + 1); ++l) {
     LayerPrep lp;
-    if ((rc = prep_layer(h, tm, l, false, false, lp))) return rc;
+    if ((rc = ppc_prep_layer(h, tm, l, false, false, lp))) return rc;
     tot += lp.nsup;
-    release_layer(tm, lp);
+    ppc_release_layer(tm, lp);
   }
   *n = tot;
   return VMR_OK;
@@ -447,7 +390,7 @@ extern "C" int vmr_mean_poisson(vmr_handle h, int layer, uint64_t n, int32_t* sl
   unsigned long long base = 0;   // output index of the layer's first value
   for (int l = l0; l < l1; ++l) {
     LayerPrep lp;
-    if ((rc = prep_layer(h, tm, l, false, true, lp))) return rc;
+    if ((rc = ppc_prep_layer(h, tm, l, false, true, lp))) return rc;
     if (out_on_device) {
       hipLaunchKernelGGL(k_ppc_walk<PPC_MODE_WRITE>, dim3(grid_for(T * G, 256, 65536)), dim3(256), 0, h->stream, lp.p, G, (size_t)0, T, lp.off,
                          (const unsigned long long*)nullptr, 0ull, lp.nsup, sl ? sl + base : nullptr, si ? si + base : nullptr, sj ? sj + base : nullptr,
@@ -485,7 +428,7 @@ extern "C" int vmr_mean_poisson(vmr_handle h, int layer, uint64_t n, int32_t* sl
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     base += lp.nsup;
-    release_layer(tm, lp);
+    ppc_release_layer(tm, lp);
   }
   return bad_check(h, bad, "vmr_mean_poisson");
 }
@@ -503,10 +446,10 @@ extern "C" int vmr_report_auc(vmr_handle h, int layer, double* auc, uint64_t* n_
   unsigned long long P = 0, S = 0;
   for (int l = l0; l < l1; ++l) {
     LayerPrep lp;
-    if ((rc = prep_layer(h, tm, l, true, false, lp))) return rc;
+    if ((rc = ppc_prep_layer(h, tm, l, true, false, lp))) return rc;
     P_l[l] = lp.npos; S_l[l] = lp.nsup;
     P += lp.npos; S += lp.nsup;
-    release_layer(tm, lp);
+    ppc_release_layer(tm, lp);
   }
   const unsigned long long Q = S - P;
   if (n_pos) *n_pos = P;
@@ -526,13 +469,13 @@ extern "C" int vmr_report_auc(vmr_handle h, int layer, double* auc, uint64_t* n_
   for (int l = l0; l < l1; ++l) {
     if (!P_l[l]) continue;
     LayerPrep lp;
-    if ((rc = prep_layer(h, tm, l, true, true, lp))) return rc;
+    if ((rc = ppc_prep_layer(h, tm, l, true, true, lp))) return rc;
     hipLaunchKernelGGL(k_ppc_walk<PPC_MODE_POS>, dim3(grid_for(T * G, 256, 65536)), dim3(256), 0, h->stream, lp.p, G, (size_t)0, T, lp.off, lp.poff,
                        0ull, P_l[l], (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, (double*)nullptr, pk + pb, bad);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));
     pb += P_l[l];
-    release_layer(tm, lp);
+    ppc_release_layer(tm, lp);
   }
   {
     hipcub::DoubleBuffer<unsigned long long> db(pk, pk2);
@@ -551,7 +494,7 @@ extern "C" int vmr_report_auc(vmr_handle h, int layer, double* auc, uint64_t* n_
     const unsigned long long Ql = S_l[l] - P_l[l];
     if (!Ql) continue;
     LayerPrep lp;
-    if ((rc = prep_layer(h, tm, l, true, true, lp))) return rc;
+    if ((rc = ppc_prep_layer(h, tm, l, true, true, lp))) return rc;
     size_t fr = 0, tot = 0;
     HIPCHK(h, hipMemGetInfo(&fr, &tot));
     // 16 B per negative (keys and the sort's second buffer) plus the sort's scratch: a third of the free memory at most
@@ -589,7 +532,7 @@ extern "C" int vmr_report_auc(vmr_handle h, int layer, double* auc, uint64_t* n_
       t0 = t1;
     }
     tm.release(ts); tm.release(nk); tm.release(nk2);
-    release_layer(tm, lp);
+    ppc_release_layer(tm, lp);
   }
   if ((rc = bad_check(h, bad, "vmr_report_auc"))) return rc;
   unsigned long long U2 = 0;

@@ -496,6 +496,11 @@ int scan_u32(vmr_ctx* h, unsigned* a, unsigned* bsum, size_t n);
 // re-writes rho where the last sweep left it unwritten, before anything reads it (vmr_readout and its kin); vimure_hip.hip
 int ensure_rho_ext(vmr_ctx* h);
 
+// C posterior samples of Y queued on the handle's stream: Y[s] (uint8 [L][N][N], natural order) is what vmr_sample(h, seed0 + s,
+// n_trials) writes, s in [0, C); rho is read once.  The caller has run ensure_rho_ext.  netstats.hip
+int ns_draw_chunk(vmr_ctx* h, uint8_t* Y, unsigned long long seed0, int C, int n_trials);
+#define NS_CHUNK_MAX 256   // samples per chunk at most (vmr_sample_stats, vmr_ppc_replicates)
+
 #define CK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { g_create_err = std::string(#call) + ": " + hipGetErrorString(e_); (void)hipGetLastError(); return VMR_EHIP; } } while (0)
 
 #endif  // VMR_INTERNAL_H

@@ -440,6 +440,36 @@ class CaviEngine:
         self._check(self.lib.vmr_report_auc(self._h, self._layer_arg(layer), C.byref(a), C.byref(p), C.byref(q)))
         return a.value, int(p.value), int(q.value)
 
+    def ppc_replicates(self, theta, lam, eta, seed_y, seed_x, n_trials=1, by_reporter=False):
+        """Discrepancy statistics of posterior predictive replicates, drawn and reduced on the device (vmr_ppc_replicates): no
+        replicate is written.  theta [n_rep, L, M], lam [n_rep, L, K], eta [n_rep] (each in [0, 1)): the parameters of every
+        replicate.  Replicate r: Y = `self.sample(seed_y + r, n_trials)`, lambda of a tie = lam[r, l, Y], and over the support of
+        this engine's R the counts `synthetic.device_build_x(None, theta[r], eta[r], seed_x + r, lam=...)` would hold, unclamped.
+        Returns counts int64 [n_rep, L, 6] -- `_lib.PPC_STAT_NAMES`: n_pos, total, sumsq, mutual, ties_reported, ties_agreed --
+        and, with by_reporter=True, also int64 [n_rep, L, M, 2]: (n_pos, total) of every reporter."""
+        theta, lam = _f64(theta), _f64(lam)
+        eta = _f64(np.atleast_1d(eta))
+        n_rep = int(eta.shape[0])
+        if theta.shape != (n_rep, self.L, self.M) or lam.shape != (n_rep, self.L, self.K) or eta.ndim != 1:
+            raise ValueError(f"theta {theta.shape}, lam {lam.shape}, eta {eta.shape}: expected (n_rep, {self.L}, {self.M}), "
+                             f"(n_rep, {self.L}, {self.K}), (n_rep,)")
+        counts = np.zeros((n_rep, self.L, _lib.PPC_NSTAT), np.uint64)
+        rep = np.zeros((n_rep, self.L, self.M, 2), np.uint64) if by_reporter else None
+        self._check(self.lib.vmr_ppc_replicates(self._h, n_rep, int(seed_y) & (2 ** 64 - 1), int(seed_x) & (2 ** 64 - 1), int(n_trials),
+                                                theta.ctypes.data, lam.ctypes.data, eta.ctypes.data, counts.ctypes.data,
+                                                rep.ctypes.data if by_reporter else None))
+        counts = counts.astype(np.int64)
+        return (counts, rep.astype(np.int64)) if by_reporter else counts
+
+    def ppc_observed(self, by_reporter=False):
+        """The statistics of `ppc_replicates` of this engine's own X over the support of R (vmr_ppc_observed): int64 [L, 6], and
+        with by_reporter=True also int64 [L, M, 2]."""
+        counts = np.zeros((self.L, _lib.PPC_NSTAT), np.uint64)
+        rep = np.zeros((self.L, self.M, 2), np.uint64) if by_reporter else None
+        self._check(self.lib.vmr_ppc_observed(self._h, counts.ctypes.data, rep.ctypes.data if by_reporter else None))
+        counts = counts.astype(np.int64)
+        return (counts, rep.astype(np.int64)) if by_reporter else counts
+
     def snapshot(self):
         """Keep the current posteriors on the device (`_update_optimal_parameters`, reference model.py:925-942)."""
         self._check(self.lib.vmr_snapshot(self._h))

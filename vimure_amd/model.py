@@ -693,6 +693,38 @@ class VimureModel(TransformerMixin, BaseEstimator):
             ref_edges = (Y_true > 0).sum(dim=(1, 2)).cpu().numpy()
         return NetworkStats(self.N, counts, expected=expected, ref_edges=ref_edges, seed=seed, n_trials=n_trials)
 
+    def posterior_predictive_check(self, n_rep=100, seed=None, params="draw", n_trials=1, by_reporter=False, X=None, R=None):
+        """Does data drawn from the fitted model look like the data it was fitted to?  n_rep replicated datasets are drawn on the
+        GPU over the support of R and reduced there (vmr_ppc_replicates; no replicate is written) to the integers of
+        `predictive.PredictiveCheck` -- positive reports, their sum and sum of squares, reciprocated reports, ties reported by
+        anyone and by at least two -- and the observed data is reduced the same way (vmr_ppc_observed).
+        Replicate r: Y from rho with seed + r (`sample_inferred_model(N=n_trials, seed=seed + r, device=True)`), the reports with
+        seed + 2^32 + r.  params="draw": theta, lambda, eta of every replicate from their Gamma posteriors with
+        `np.random.RandomState(seed)` (`PosteriorSyntheticNetwork.build_X`'s draw; an eta >= 1 is drawn again); "mean": the
+        posterior means.  by_reporter=True: also (n_pos, total) of every reporter.  seed None: the fit's.  Returns the
+        `PredictiveCheck`: `p_values()`, `summary()`.  Engine as in `calculate_mean_poisson`."""
+        from .predictive import PredictiveCheck, draw_parameters
+        if seed is None:
+            seed = self.seed
+        seed = int(seed)
+        if not hasattr(self, "gamma_shp_f"):
+            raise ValueError("the model has not been fitted: call fit(..., keep_engine=True) first, or fit it and pass X=")
+        theta, lam, eta, redraws = draw_parameters(self.gamma_shp_f, self.gamma_rte_f, self.phi_shp_f, self.phi_rte_f, self.nu_shp_f,
+                                                   self.nu_rte_f, n_rep, seed, params=params)
+        seed_y, seed_x = seed, seed + 2 ** 32
+        eng, tmp = self._ppc_engine(X, R)
+        try:
+            rep = eng.ppc_replicates(theta, lam, eta, seed_y, seed_x, n_trials=n_trials, by_reporter=by_reporter)
+            obs = eng.ppc_observed(by_reporter=by_reporter)
+            support = [eng.mean_poisson_size(layer=l) for l in range(self.L)]
+        finally:
+            if tmp:
+                eng.close()
+        rep, rep_m = rep if by_reporter else (rep, None)
+        obs, obs_m = obs if by_reporter else (obs, None)
+        return PredictiveCheck(obs, rep, observed_by_reporter=obs_m, replicated_by_reporter=rep_m, support=support, seed_y=seed_y,
+                               seed_x=seed_x, n_trials=n_trials, theta=theta, lam=lam, eta=eta, eta_redraws=redraws, params=params)
+
     def predict(self, X=None, method="rho_max", threshold=None):
         """Alias of `get_inferred_model` (the reference's experiment wrapper calls it predict)."""
         return self.get_inferred_model(method=method, threshold=threshold)
