@@ -298,6 +298,37 @@ int vmr_ppc_replicates(vmr_handle h, int n_rep, uint64_t seed_y, uint64_t seed_x
                        const double* lambda, const double* eta, uint64_t* counts, uint64_t* by_reporter);
 int vmr_ppc_observed(vmr_handle h, uint64_t* counts, uint64_t* by_reporter);
 
+/* The inferred network as an edge table, built on the device -- the edge list of the reference's experiment driver
+ * (notebooks/python/experiments/karnataka.py:200-318: the thresholded posterior beside the union and intersection baselines) for
+ * any K and any mask, instead of `get_inferred_model`'s dense [L,N,N] array (model.py:1099-1188) and the 8 L N^2 K bytes of rho.
+ * Per tie t = (l,i,j), from the handle's own X and R and the CURRENT rho (after vmr_restore: the snapshot's):
+ *   y        the byte vmr_readout(h, method, threshold, ..) writes for the tie; method VMR_READ_RHO_MAX or VMR_READ_THRESHOLD
+ *            (VMR_READ_RHO_MEAN: VMR_EINVAL)
+ *   prob     sum_{k>=1} rho_k, added in ascending k as in vmr_expected_stats (K = 2: the double rho_1, bit for bit)
+ *   mean     sum_k k rho_k, k ascending, every product and every sum rounded on its own (NumPy's loop; VMR_READ_RHO_MEAN's value up
+ *            to the rounding of a fused multiply-add)
+ *   n_rep    #{m : X[l,i,j,m] > 0}              total    sum_m X[l,i,j,m]
+ *   n_mask   #{m : R[l,i,j,m] != 0} (M without R)
+ *   ego      X[l,i,j,i], 0 where i >= M          alter    X[l,i,j,j], 0 where j >= M
+ *   y_T, n_rep_T, total_T   y, n_rep, total of the mirror tie (l,j,i); a diagonal tie is its own mirror
+ * n_rep, total, ego and alter are over ALL reporters, R ignored -- the driver's np.sum(X, axis=3) -- unlike the statistics of
+ * vmr_ppc_observed, which are over the support of R.
+ * A tie is a row iff (select & VMR_EDGE_REPORTED and n_rep > 0) or (select & VMR_EDGE_INFERRED and y > 0); select is 1, 2 or 3.
+ * Rows come in lexicographic (l,i,j) order, np.nonzero's; layer < 0: every layer, else that one.  vmr_edge_table_size gives the
+ * row count; n is the capacity of the outputs (VMR_EINVAL below the row count, before anything is written); any output pointer
+ * may be NULL; device pointers when out_on_device != 0.  Any K, both data formats, every mask layout, handles of vmr_create_coo;
+ * fewer than 2^31 ties per layer.  Integer reductions and per-lane sums only: bit-identical from run to run.  VMR_ESTATE before
+ * vmr_set_state.  Synchronise; temporaries (report-list handles: the tie-major index of vmr_mean_poisson and the tie -> position
+ * table; 20 B per tie of a layer; host outputs: a layer's rows) are freed before return, and one that does not fit in the free
+ * device memory is refused with VMR_EINVAL. */
+enum { VMR_EDGE_REPORTED = 1, VMR_EDGE_INFERRED = 2 };
+int vmr_edge_table_size(vmr_handle h, int method, double threshold, int select, int layer, uint64_t* n);
+int vmr_edge_table(vmr_handle h, int method, double threshold, int select, int layer, uint64_t n,
+                   int32_t* sl, int32_t* si, int32_t* sj,
+                   uint8_t* y, double* prob, double* mean,
+                   uint32_t* n_rep, uint64_t* total, uint32_t* n_mask, uint32_t* ego, uint32_t* alter,
+                   uint8_t* y_T, uint32_t* n_rep_T, uint64_t* total_T, int out_on_device);
+
 /* exp(E[log .]) of theta [L,M], lambda [L,K], nu from the current shape/rate parameters
  * (model.py:676-684), plus g_nu_cache = the G_exp_nu the last cache refresh held, i.e. the
  * value computed BEFORE the last nu update -- what `model.G_exp_nu` reads after `fit` and what

@@ -13,6 +13,7 @@ STEP_GAMMA, STEP_PHI, STEP_RHO, STEP_NU = 0, 1, 2, 3
 KERNEL_GAMMA_MASK, KERNEL_GAMMA_COUNTS, KERNEL_PHI, KERNEL_RHO, KERNEL_ELBO, KERNEL_FINALIZE, KERNEL_RHO_ELBO, KERNEL_RHO_NOSTORE = range(8)
 READ_RHO_MAX, READ_RHO_MEAN, READ_THRESHOLD = 0, 1, 2
 PPC_NSTAT = 6
+EDGE_REPORTED, EDGE_INFERRED = 1, 2
 PPC_STAT_NAMES = ["n_pos", "total", "sumsq", "mutual", "ties_reported", "ties_agreed"]
 KERNEL_NAMES = ["gamma_mask", "gamma_counts", "phi", "rho", "elbo", "finalize", "rho_elbo", "rho_nostore"]
 
@@ -59,6 +60,8 @@ SIGNATURES = {
     "vmr_mean_poisson": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_int]),
     "vmr_report_auc": (C.c_int, [C.c_void_p, C.c_int, _dp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "vmr_edge_table_size": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_uint64)]),
+    "vmr_edge_table": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_uint64] + [C.c_void_p] * 14 + [C.c_int]),
     "vmr_snapshot": (C.c_int, [C.c_void_p]),
     "vmr_restore": (C.c_int, [C.c_void_p]),
     "vmr_profile": (C.c_int, [C.c_void_p, C.c_int]),

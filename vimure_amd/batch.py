@@ -501,6 +501,28 @@ def karnataka_tables(model, X, R, village, layer, seed, running_time) -> Dict[st
     return {"summary": summary, "trace": trace, "edgelist": edgelist, "reliability": reliability}
 
 
+def karnataka_edgelist(model, village, layer, seed, X=None, R=None) -> pd.DataFrame:
+    """The `edgelist` table of `karnataka_tables` -- same columns, dtypes and row order -- from the edge table the GPU builds
+    (`VimureModel.get_inferred_edgelist`, method "heuristic_threshold"): no dense [L,N,N] array is made on the host and rho_f
+    is not fetched.  The model is a K = 2 fit (the driver's setting) with its engine kept (`fit(..., keep_engine=True)`), or its
+    data come as X= (and R=), as in `calculate_mean_poisson`.  A tie is in the union when anyone reported it, in the
+    intersection when its reports sum to 2, and source_report / target_report say whether the ego's / alter's own count is 1."""
+    if int(model.K) != 2:
+        raise ValueError("karnataka_edgelist: the driver's tables are those of a K = 2 fit (vimure_posterior_probability is rho_1)")
+    t = model.get_inferred_edgelist(method="heuristic_threshold", select=("reported", "inferred"), X=X, R=R)
+    ii, jj = t["source"].to_numpy(), t["target"].to_numpy()
+    return pd.DataFrame({
+        "village": village, "layer": layer, "initial_seed": seed, "source": ii, "target": jj,
+        "dyad_ID": [f"{i}_{j}" for i, j in zip(ii, jj)],
+        "source_report": t["source_report"].to_numpy() == 1, "target_report": t["target_report"].to_numpy() == 1,
+        "vimure_posterior_probability": t["probability"].to_numpy(),
+        "in_union": t["n_reports"].to_numpy() > 0, "in_intersection": t["total_reports"].to_numpy() == 2,
+        "in_vimure": t["y"].to_numpy() == 1,
+        "reciprocated_in_union": t["reciprocated_n_reports"].to_numpy() > 0,
+        "reciprocated_in_intersection": t["reciprocated_total"].to_numpy() == 2,
+        "reciprocated_in_vimure": t["reciprocated_y"].to_numpy() == 1})
+
+
 def run_karnataka(villages: Dict[str, tuple], seeds: Iterable[int] = range(1, 11), out_dir: str = None, K=2, mutuality=True,
                   num_realisations=5, max_iter=101, device=None, workers=DEFAULT_WORKERS, lockstep=True, **fit_kwargs) -> Dict[str, pd.DataFrame]:
     """`karnataka.main` over many villages: villages = name -> (X [L,N,N,N], R, layer names); every layer is fitted on its own

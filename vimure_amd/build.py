@@ -31,7 +31,8 @@ def units(dev=False):
          ("draw_prior", os.path.join(CSRC, "draw_prior.hip"), extra),  # the initial rho prior on the device
          ("ppc", os.path.join(CSRC, "ppc.hip"), extra),                # expected reports and report AUC
          ("netstats", os.path.join(CSRC, "netstats.hip"), extra),      # network statistics of posterior samples
-         ("ppc_rep", os.path.join(CSRC, "ppc_rep.hip"), extra)]        # posterior predictive replicates, reduced
+         ("ppc_rep", os.path.join(CSRC, "ppc_rep.hip"), extra),        # posterior predictive replicates, reduced
+         ("edge_table", os.path.join(CSRC, "edge_table.hip"), extra)]  # the inferred network as an edge table
     dev_ks = tuple(int(k) for k in os.environ.get("VMR_DEV_KS", "2").split(","))   # (VMR_DEV_KS=2,3: also the K = 3 sweep kernels)
     for k in (dev_ks if dev else KS):
         u.append((f"sweep_sl_k{k}", os.path.join(CSRC, "sweep_sl.hip"), extra + [f"-DVMR_K={k}"]))

@@ -225,7 +225,7 @@ int ppc_layer_mask(vmr_ctx* h, int l, PpcLayer& p) {
   return VMR_OK;
 }
 
-int ppc_prep_layer(vmr_ctx* h, Tmp& tm, int l, bool positives, bool walk, LayerPrep& lp, bool want_index) {
+int ppc_prep_layer(vmr_ctx* h, Tmp& tm, int l, bool positives, bool walk, LayerPrep& lp, bool want_index, bool offsets) {
   const Geo& g = h->g;
   const size_t T = (size_t)g.N * g.N, NS = (T + 63) / 64;
   const ParOff o = par_off(g.L, g.Mp, g.K);
@@ -277,6 +277,7 @@ int ppc_prep_layer(vmr_ctx* h, Tmp& tm, int l, bool positives, bool walk, LayerP
   } else {
     p.X = h->X + (size_t)l * T * g.Mp;
   }
+  if (!offsets) return VMR_OK;
   unsigned long long *sup = nullptr, *pc = nullptr;
   if ((rc = take(&sup, (T + 1) * 8, "the support sizes")) || (rc = take(&lp.off, (T + 1) * 8, "the support offsets"))) return rc;
   if (positives && ((rc = take(&pc, (T + 1) * 8, "the positives' counts")) || (rc = take(&lp.poff, (T + 1) * 8, "the positives' offsets")))) return rc;

@@ -79,8 +79,9 @@ struct LayerPrep {
 int ppc_layer_mask(vmr_ctx* h, int l, PpcLayer& p);
 
 // positives: the counts are needed (the index of report-list handles is built) and poff is filled; walk: rho is read by tie (the
-// tie -> position table) and, with mutuality, the mirror counts; index: build the index of a report-list handle in any case.
-int ppc_prep_layer(vmr_ctx* h, Tmp& tm, int l, bool positives, bool walk, LayerPrep& lp, bool index = false);
+// tie -> position table) and, with mutuality, the mirror counts; index: build the index of a report-list handle in any case;
+// offsets = false: no support offsets (off stays null, nsup 0) for a caller that walks ties, not the support (edge_table.hip).
+int ppc_prep_layer(vmr_ctx* h, Tmp& tm, int l, bool positives, bool walk, LayerPrep& lp, bool index = false, bool offsets = true);
 void ppc_release_layer(Tmp& tm, LayerPrep& lp);
 
 #endif  // VMR_PPC_LAYER_H

@@ -15,6 +15,19 @@ class EngineError(RuntimeError):
     pass
 
 
+class EdgeTableArgumentError(EngineError, ValueError):
+    """An argument `edge_table` / `edge_table_size` refuse (VMR_EINVAL): a method that gives no categories, an empty or
+    unknown selection, outputs shorter than the table."""
+
+
+# columns of `CaviEngine.edge_table`, in the order of vmr_edge_table's output pointers (device=True: the unsigned 32 / 64-bit columns
+# are torch.int32 / torch.int64 tensors holding the same bits -- every value is below 2^31 / 2^63)
+EDGE_COLUMNS = (("l", np.int32), ("i", np.int32), ("j", np.int32), ("y", np.uint8), ("prob", np.float64), ("mean", np.float64),
+                ("n_rep", np.uint32), ("total", np.uint64), ("n_mask", np.uint32), ("ego", np.uint32), ("alter", np.uint32),
+                ("y_T", np.uint8), ("n_rep_T", np.uint32), ("total_T", np.uint64))
+_TORCH_NAME = {"uint32": "int32", "uint64": "int64"}
+
+
 def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
@@ -469,6 +482,80 @@ class CaviEngine:
         self._check(self.lib.vmr_ppc_observed(self._h, counts.ctypes.data, rep.ctypes.data if by_reporter else None))
         counts = counts.astype(np.int64)
         return (counts, rep.astype(np.int64)) if by_reporter else counts
+
+    def _edge_args(self, method, threshold, select, layer):
+        codes = {"rho_max": _lib.READ_RHO_MAX, "rho_mean": _lib.READ_RHO_MEAN, "threshold": _lib.READ_THRESHOLD}
+        if method not in codes:
+            raise ValueError("'method' should be one of \"rho_max\", \"threshold\".")
+        if isinstance(select, str):
+            select = (select,)
+        if isinstance(select, (int, np.integer)):
+            sel = int(select)
+        else:
+            bits = {"reported": _lib.EDGE_REPORTED, "inferred": _lib.EDGE_INFERRED}
+            sel = 0
+            for s in select:
+                if s not in bits:
+                    raise ValueError("'select' holds \"reported\", \"inferred\" or both.")
+                sel |= bits[s]
+        return codes[method], float(threshold), sel, self._layer_arg(layer)
+
+    def _check_edge(self, rc):
+        """A refused argument of the edge table is an EngineError AND a ValueError (EdgeTableArgumentError)."""
+        if rc == _lib.VMR_EINVAL:
+            raise EdgeTableArgumentError(self.lib.vmr_last_error(self._h).decode())
+        self._check(rc)
+
+    def edge_table_size(self, method="rho_max", threshold=0.0, select=("reported", "inferred"), layer=None):
+        """Rows of `edge_table` for the same arguments (vmr_edge_table_size)."""
+        code, thr, sel, la = self._edge_args(method, threshold, select, layer)
+        n = C.c_uint64()
+        self._check_edge(self.lib.vmr_edge_table_size(self._h, code, thr, sel, la, C.byref(n)))
+        return int(n.value)
+
+    def edge_table(self, method="rho_max", threshold=0.0, select=("reported", "inferred"), layer=None, device=False, out=None):
+        """The inferred network of the current rho as an edge table built on the device (vmr_edge_table): a row per tie (l,i,j)
+        that someone reported (`n_rep > 0`; select "reported") and / or that the read-out infers (`y > 0`; "inferred"), in
+        lexicographic order.  method "rho_max" or "threshold" (`rho_1 >= threshold`), as `readout`.  Returns a dict of arrays, one
+        entry per `EDGE_COLUMNS`: l, i, j (int32), y (uint8, `readout`'s byte), prob (sum_{k>=1} rho_k), mean (sum_k k rho_k),
+        n_rep #{m : X > 0}, total sum_m X, n_mask #{m : R != 0}, ego X[l,i,j,i], alter X[l,i,j,j] and y_T, n_rep_T, total_T of
+        the mirror tie (l,j,i); counts over all reporters, R ignored.  select may also be the bit mask 1 | 2; layer: that layer
+        only.  device=True: torch tensors on the engine's GPU.  out: a dict of preallocated arrays (all of one length, the
+        capacity; any column may be missing) to fill instead; a capacity below the row count is refused before anything is
+        written."""
+        code, thr, sel, la = self._edge_args(method, threshold, select, layer)
+        if out is not None:
+            cap = {int(a.shape[0]) for a in out.values()}
+            if len(cap) != 1:
+                raise ValueError("out: arrays of one length expected")
+            n, cols = cap.pop(), out
+        else:
+            n = self.edge_table_size(method, threshold, sel, layer)
+            if device:
+                import torch
+                dev = torch.device("cuda", self.device)
+                cols = {c: torch.empty(n, dtype=getattr(torch, _TORCH_NAME.get(np.dtype(t).name, np.dtype(t).name)), device=dev)
+                        for c, t in EDGE_COLUMNS}
+            else:
+                cols = {c: np.empty(n, t) for c, t in EDGE_COLUMNS}
+        ptrs = []
+        for c, t in EDGE_COLUMNS:
+            a = cols.get(c)
+            if a is None:
+                ptrs.append(None)
+            elif _is_torch(a):
+                assert a.is_cuda and a.is_contiguous() and a.element_size() == np.dtype(t).itemsize
+                ptrs.append(a.data_ptr())
+            else:
+                assert a.dtype == np.dtype(t) and a.flags.c_contiguous
+                ptrs.append(a.ctypes.data)
+        on_dev = any(_is_torch(a) for a in cols.values())
+        if on_dev:
+            import torch
+            torch.cuda.synchronize(torch.device("cuda", self.device))
+        if n or out is not None:
+            self._check_edge(self.lib.vmr_edge_table(self._h, code, thr, sel, la, n, *ptrs, int(on_dev)))
+        return cols
 
     def snapshot(self):
         """Keep the current posteriors on the device (`_update_optimal_parameters`, reference model.py:925-942)."""

@@ -578,6 +578,57 @@ class VimureModel(TransformerMixin, BaseEstimator):
         Y[Y >= threshold] = 1
         return Y if method == "fixed_threshold" else Y.astype("int")
 
+    def _edge_method(self, method, threshold):
+        """(engine method, threshold) of an edge table: `get_inferred_model`'s resolution of method and threshold, warning and
+        errors included; "rho_mean" gives no categories and is refused."""
+        options = ["rho_max", "rho_mean", "fixed_threshold", "heuristic_threshold"]
+        if method not in options:
+            raise ValueError("'method' should be one of {}.".format(", ".join(['"' + x + '"' for x in options])))
+        if (not self.mutuality and method != "rho_max") or (self.K > 2 and "threshold" in method):
+            msg = ('threshold methods is incompatible with VIMuRe\'s mutuality=False '
+                   'or for data with more than 2 categories. Using "rho_max" method.')
+            warnings.warn(msg, UserWarning)
+            method = "rho_max"
+        if method == "rho_mean":
+            raise ValueError('method="rho_mean" gives expected weights, not categories: an edge list needs "rho_max", '
+                             '"fixed_threshold" or "heuristic_threshold" (the table\'s `mean` column holds the expected weight).')
+        if method == "rho_max":
+            return "rho_max", 0.0
+        if method == "fixed_threshold":
+            if threshold is None or threshold > 1 or threshold < 0:
+                raise ValueError('For method="fixed_threshold", you must set the threshold to a value in [0,1].')
+        else:  # heuristic threshold, reference utils.py:200-217
+            threshold = 0.54 * self.G_exp_nu - 0.01
+        return "threshold", float(threshold)
+
+    def get_inferred_edgelist(self, method="rho_max", threshold=None, select=("reported", "inferred"), layer=None, X=None, R=None):
+        """The inferred network as an edge list built on the GPU (vmr_edge_table) -- what the reference's experiment driver
+        assembles from dense arrays (karnataka.py:200-318) -- instead of `get_inferred_model`'s [L,N,N] array: a row per tie that
+        someone reported (select "reported") and / or that the read-out infers (`y > 0`; "inferred"), in (layer, source, target)
+        order; neither rho nor a dense read-out crosses PCIe.  method and threshold as `get_inferred_model` takes them (same
+        warning and fall-back, same errors); "rho_mean" is a ValueError.  Columns: layer, source, target, y (the category
+        `get_inferred_model` gives the tie), probability (sum_{k>=1} rho_k), mean (sum_k k rho_k), n_reports #{m : X > 0},
+        total_reports sum_m X, n_mask #{m : R != 0}, source_report X[l,i,j,i], target_report X[l,i,j,j] (counts over all
+        reporters, R ignored) and reciprocated_y, reciprocated_n_reports, reciprocated_total of the tie (l,j,i).  layer: that
+        layer only.  Engine as in `calculate_mean_poisson`."""
+        if not hasattr(self, "gamma_shp_f"):
+            raise ValueError("the model has not been fitted: call fit(..., keep_engine=True) first, or fit it and pass X=")
+        code, thr = self._edge_method(method, threshold)
+        eng, tmp = self._ppc_engine(X, R)
+        try:
+            t = eng.edge_table(method=code, threshold=thr, select=select, layer=layer)
+        finally:
+            if tmp:
+                eng.close()
+        return pd.DataFrame({
+            "layer": np.asarray(t["l"], np.int64), "source": np.asarray(t["i"], np.int64), "target": np.asarray(t["j"], np.int64),
+            "y": np.asarray(t["y"], np.int64), "probability": np.asarray(t["prob"], np.float64),
+            "mean": np.asarray(t["mean"], np.float64), "n_reports": np.asarray(t["n_rep"], np.int64),
+            "total_reports": np.asarray(t["total"], np.int64), "n_mask": np.asarray(t["n_mask"], np.int64),
+            "source_report": np.asarray(t["ego"], np.int64), "target_report": np.asarray(t["alter"], np.int64),
+            "reciprocated_y": np.asarray(t["y_T"], np.int64), "reciprocated_n_reports": np.asarray(t["n_rep_T"], np.int64),
+            "reciprocated_total": np.asarray(t["total_T"], np.int64)})
+
     # ------------------------------------------------------------------ posterior-predictive check (model.py:1220-1293)
     def _ppc_engine(self, X, R):
         """(engine, temporary): the engine kept by fit(keep_engine=True) when X is None, else a temporary one holding X and R
