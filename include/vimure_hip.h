@@ -329,6 +329,47 @@ int vmr_edge_table(vmr_handle h, int method, double threshold, int select, int l
                    uint32_t* n_rep, uint64_t* total, uint32_t* n_mask, uint32_t* ego, uint32_t* alter,
                    uint8_t* y_T, uint32_t* n_rep_T, uint64_t* total_T, int out_on_device);
 
+/* The posterior scored against a ground-truth network, where rho lives -- the `f1_score` / `GridSearchCV` scoring of the
+ * reference's synthetic experiments (notebooks/python/experiments/unreliable_reporters.py:189-200, 358-361), the F1 of its
+ * known-answer tests (test/test_model.py:117-334) and `utils.get_optimal_threshold` -- instead of one dense read-out per
+ * threshold (L N^2 bytes each) plus, for an AUC or a calibration curve, the 8 L N^2 K bytes of rho.
+ * y_true: uint8 [L,N,N] in natural order, a device pointer when y_true_on_device != 0; every output is a host array and may be
+ * NULL (not all of them).  Reads the CURRENT rho (after vmr_restore: the snapshot's).  Per tie t = (l,i,j), over all ordered
+ * pairs of a layer, the diagonal included unless skip_diagonal != 0:
+ *   b     y_true > 0
+ *   s     the score: VMR_SCORE_RHO1 rho[t][1], what vmr_readout(VMR_READ_THRESHOLD) compares; VMR_SCORE_PROB sum_{k>=1} rho_k
+ *         added in ascending k, `prob` of vmr_edge_table (K = 2: the same double)
+ *   a     the first maximum of rho[t][.], the byte of vmr_readout(VMR_READ_RHO_MAX)
+ *   mean  sum_k k rho_k, every product and sum rounded on its own: `mean` of vmr_edge_table
+ * hist  [L][n_thr + 1][2]: hist[l][c][b] = #{ties with c = #{tau : thresholds[tau] <= s}}; thresholds finite and non-decreasing
+ *       (duplicates allowed), n_thr in [0, VMR_SCORE_MAX_THR].  tp(tau) = sum_{c > tau} hist[l][c][1], fp(tau) likewise with
+ *       [0]: the suffix sums are the caller's.  With VMR_SCORE_RHO1, tp(tau) + fp(tau) is the number of ones
+ *       vmr_readout(h, VMR_READ_THRESHOLD, thresholds[tau], ..) writes.  Without hist the thresholds are not read.
+ * conf  [L][VMR_SCORE_NCONF]: #{a > 0 and b}, #{a > 0 and not b}, #{a = 0 and b}, #{a = y_true}, P = #{b}
+ * sums  [L][VMR_SCORE_NSUM]: sum s, sum_{b} s, sum (s - [b])^2 (the Brier numerator), sum (mean - y_true)^2 (the experiment's MSE
+ *       numerator); doubles summed by a fixed two-stage tree whose grid depends on N only, no floating-point atomics
+ * auc_pairs [L][2]: (U2, Q), U2 = 2 #{(p,n) : s_p > s_n} + #{(p,n) : s_p = s_n} over ties p with b and n without, Q = #{not b};
+ * auc [L] = U2 / (2 P Q), NaN when P = 0 or Q = 0 (vmr_report_auc's rule).  Exact 64-bit integer counts; the positives' scores
+ * are sorted (8 B per positive, twice, plus the sort's scratch) and every negative tie searches them; nothing of this runs
+ * when auc and auc_pairs are both NULL.
+ * Any K, both data formats, every mask layout, handles of vmr_create_coo.  All results are bit-identical from run to run.
+ * VMR_EINVAL with a message, before any launch: NULL y_true, every output NULL, score not 0 / 1, n_thr out of range, hist with
+ * n_thr > 0 and thresholds NULL, a non-finite or decreasing threshold, a temporary that does not fit in the free device
+ * memory (L N^2 bytes for a host y_true; 8 (n_thr + 1) 2 L bytes; 32 B per workgroup); for the AUC, once P is counted,
+ * P >= 2^31 or 2 P Q >= 2^63.  VMR_ESTATE before vmr_set_state.  VMR_ENAN if any s is NaN (the outputs are then unspecified).
+ * Synchronises; temporaries are freed on every exit path. */
+enum { VMR_SCORE_RHO1 = 0, VMR_SCORE_PROB = 1 };
+#define VMR_SCORE_NCONF 5
+#define VMR_SCORE_NSUM 4
+#define VMR_SCORE_MAX_THR 4096
+int vmr_score_truth(vmr_handle h, const uint8_t* y_true, int y_true_on_device, int score, int skip_diagonal,
+                    int n_thr, const double* thresholds,
+                    uint64_t* hist,       /* [L][n_thr + 1][2] or NULL */
+                    uint64_t* conf,       /* [L][VMR_SCORE_NCONF] or NULL */
+                    double*   sums,       /* [L][VMR_SCORE_NSUM] or NULL */
+                    double*   auc,        /* [L] or NULL */
+                    uint64_t* auc_pairs   /* [L][2] or NULL */);
+
 /* exp(E[log .]) of theta [L,M], lambda [L,K], nu from the current shape/rate parameters
  * (model.py:676-684), plus g_nu_cache = the G_exp_nu the last cache refresh held, i.e. the
  * value computed BEFORE the last nu update -- what `model.G_exp_nu` reads after `fit` and what

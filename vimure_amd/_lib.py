@@ -14,6 +14,8 @@ KERNEL_GAMMA_MASK, KERNEL_GAMMA_COUNTS, KERNEL_PHI, KERNEL_RHO, KERNEL_ELBO, KER
 READ_RHO_MAX, READ_RHO_MEAN, READ_THRESHOLD = 0, 1, 2
 PPC_NSTAT = 6
 EDGE_REPORTED, EDGE_INFERRED = 1, 2
+SCORE_RHO1, SCORE_PROB = 0, 1
+SCORE_NCONF, SCORE_NSUM, SCORE_MAX_THR = 5, 4, 4096
 PPC_STAT_NAMES = ["n_pos", "total", "sumsq", "mutual", "ties_reported", "ties_agreed"]
 KERNEL_NAMES = ["gamma_mask", "gamma_counts", "phi", "rho", "elbo", "finalize", "rho_elbo", "rho_nostore"]
 
@@ -62,6 +64,7 @@ SIGNATURES = {
     "vmr_report_auc": (C.c_int, [C.c_void_p, C.c_int, _dp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "vmr_edge_table_size": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_uint64)]),
     "vmr_edge_table": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_uint64] + [C.c_void_p] * 14 + [C.c_int]),
+    "vmr_score_truth": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p] + [C.c_void_p] * 5),
     "vmr_snapshot": (C.c_int, [C.c_void_p]),
     "vmr_restore": (C.c_int, [C.c_void_p]),
     "vmr_profile": (C.c_int, [C.c_void_p, C.c_int]),

@@ -16,7 +16,8 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 HOST_SRC = os.path.join(CSRC, "host_init.c")
 HOST_LIB = os.path.join(HERE, "libvimure_host.so")
 HEADERS = [os.path.join(CSRC, "vmr_internal.h"), os.path.join(CSRC, "sweep_sl.h"), os.path.join(CSRC, "sweep_gen.h"),
-           os.path.join(CSRC, "sample_draw.h"), os.path.join(CSRC, "report_draw.h"), os.path.join(CSRC, "ppc_layer.h"), os.path.join(ROOT, "include", "vimure_hip.h")]
+           os.path.join(CSRC, "sample_draw.h"), os.path.join(CSRC, "report_draw.h"), os.path.join(CSRC, "ppc_layer.h"), os.path.join(CSRC, "rho_row.h"),
+           os.path.join(ROOT, "include", "vimure_hip.h")]
 KS = (2, 3, 4, 5, 6, 7, 8)
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
 
@@ -32,7 +33,8 @@ def units(dev=False):
          ("ppc", os.path.join(CSRC, "ppc.hip"), extra),                # expected reports and report AUC
          ("netstats", os.path.join(CSRC, "netstats.hip"), extra),      # network statistics of posterior samples
          ("ppc_rep", os.path.join(CSRC, "ppc_rep.hip"), extra),        # posterior predictive replicates, reduced
-         ("edge_table", os.path.join(CSRC, "edge_table.hip"), extra)]  # the inferred network as an edge table
+         ("edge_table", os.path.join(CSRC, "edge_table.hip"), extra),  # the inferred network as an edge table
+         ("score_truth", os.path.join(CSRC, "score_truth.hip"), extra)]  # the posterior scored against a ground truth
     dev_ks = tuple(int(k) for k in os.environ.get("VMR_DEV_KS", "2").split(","))   # (VMR_DEV_KS=2,3: also the K = 3 sweep kernels)
     for k in (dev_ks if dev else KS):
         u.append((f"sweep_sl_k{k}", os.path.join(CSRC, "sweep_sl.hip"), extra + [f"-DVMR_K={k}"]))

@@ -13,6 +13,7 @@
 // an atomic: the table is bit-identical from run to run.
 #include "vmr_internal.h"
 #include "ppc_layer.h"
+#include "rho_row.h"
 
 namespace {
 
@@ -46,24 +47,7 @@ static const size_t et_width[ET_NOUT] = {4, 4, 4, 1, 8, 8, 4, 8, 4, 4, 4, 1, 4, 
 // the byte vmr_readout writes for a tie (k_readout, vimure_hip.hip)
 __device__ __forceinline__ unsigned et_y(const double* __restrict__ r, int K, int method, double threshold) {
   if (method == VMR_READ_THRESHOLD) return r[1] >= threshold ? 1u : 0u;
-  int best = 0;
-  double bv = r[0];
-  for (int k = 1; k < K; ++k) if (r[k] > bv) { bv = r[k]; best = k; }   // first maximum, as np.argmax
-  return (unsigned)best;
-}
-
-// prob = sum_{k>=1} rho_k and mean = sum_k k rho_k, k ascending, every product and every sum rounded on its own: the compiler may
-// not contract k * rho_k + mean to a fused multiply-add here (__dmul_rn / __dadd_rn are inlined header code and do not stop it)
-__device__ __forceinline__ void et_prob_mean(const double* __restrict__ q, int K, double& prob, double& mean) {
-#pragma clang fp contract(off)
-  double pr = 0.0, mn = 0.0;
-  for (int k = 1; k < K; ++k) {
-    const double v = q[k];
-    const double kv = (double)k * v;
-    pr = pr + v;
-    mn = mn + kv;
-  }
-  prob = pr; mean = mn;
+  return rho_row_argmax(r, K);   // first maximum, as np.argmax
 }
 
 __device__ __forceinline__ const double* et_rho(const PpcLayer& p, size_t t) { return p.rho + (p.inv ? (size_t)p.inv[t] : t) * p.K; }
@@ -146,7 +130,7 @@ __global__ __launch_bounds__(256) void k_et_rows(PpcLayer p, const EtRec* __rest
     if (o.prob || o.mean) {
       // prob: the adds of vmr_expected_stats (k ascending); mean: every product and sum rounded on its own, k ascending
       double pr, mn;
-      et_prob_mean(et_rho(p, t), p.K, pr, mn);
+      rho_row_prob_mean(et_rho(p, t), p.K, pr, mn);
       if (o.prob) o.prob[at] = pr;
       if (o.mean) o.mean[at] = mn;
     }

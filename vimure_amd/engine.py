@@ -20,6 +20,13 @@ class EdgeTableArgumentError(EngineError, ValueError):
     unknown selection, outputs shorter than the table."""
 
 
+class ScoreArgumentError(EngineError, ValueError):
+    """An argument `score_truth` refuses (VMR_EINVAL): an unknown score, thresholds that are not finite, that decrease or that
+    are too many, a ground truth of another shape, no output asked for."""
+
+
+SCORE_OUTPUTS = ("hist", "conf", "sums", "auc", "auc_pairs")
+
 # columns of `CaviEngine.edge_table`, in the order of vmr_edge_table's output pointers (device=True: the unsigned 32 / 64-bit columns
 # are torch.int32 / torch.int64 tensors holding the same bits -- every value is below 2^31 / 2^63)
 EDGE_COLUMNS = (("l", np.int32), ("i", np.int32), ("j", np.int32), ("y", np.uint8), ("prob", np.float64), ("mean", np.float64),
@@ -556,6 +563,62 @@ class CaviEngine:
         if n or out is not None:
             self._check_edge(self.lib.vmr_edge_table(self._h, code, thr, sel, la, n, *ptrs, int(on_dev)))
         return cols
+
+    def score_truth(self, Y_true, thresholds=None, score="rho1", skip_diagonal=False, auc=True, outputs=None):
+        """The current rho scored against a ground-truth network on the device (vmr_score_truth): one pass over rho and one byte
+        of truth per tie; neither rho nor a read-out crosses PCIe.  Y_true: [L,N,N], a NumPy array of categories (clipped to 255;
+        only `> 0` and equality with the arg-max matter) or a uint8 CUDA tensor.  thresholds: finite, non-decreasing, at most
+        `_lib.SCORE_MAX_THR` (None: np.linspace(0, 1, 101)).  score: "rho1" (rho[..., 1], what `readout("threshold", t)` compares)
+        or "prob" (sum_{k>=1} rho_k).  Returns a dict of NumPy arrays: hist int64 [L, n_thr + 1, 2] (hist[l, c, b]: ties with
+        exactly c thresholds <= s, by truth), conf int64 [L, 5], sums float64 [L, 4], auc float64 [L] and auc_pairs int64 [L, 2]
+        = (U2, Q) (both None with auc=False: the sort of the positives' scores is skipped), n_ties int64 [L], thresholds --
+        what `scoring.TruthScore` takes.  outputs: the subset of `SCORE_OUTPUTS` to ask the device for (the others are None)."""
+        from .scoring import SCORES
+        if score not in SCORES:
+            raise ScoreArgumentError("score must be \"rho1\" or \"prob\"")
+        try:
+            thr = np.ascontiguousarray(np.atleast_1d(np.linspace(0, 1, 101) if thresholds is None else thresholds), dtype=np.float64)
+        except (TypeError, ValueError) as e:
+            raise ScoreArgumentError(f"thresholds: {e}") from None
+        if thr.ndim != 1:
+            raise ScoreArgumentError("thresholds: a 1-D sequence expected")
+        if outputs is None:
+            outputs = SCORE_OUTPUTS if auc else SCORE_OUTPUTS[:3]
+        outputs = tuple(outputs)
+        if any(o not in SCORE_OUTPUTS for o in outputs):
+            raise ScoreArgumentError(f"outputs: a subset of {SCORE_OUTPUTS} expected")
+        shape = (self.L, self.N, self.N)
+        if Y_true is None:
+            raise ScoreArgumentError("Y_true is None")
+        if _is_torch(Y_true):
+            import torch
+            if not Y_true.is_cuda or Y_true.dtype != torch.uint8 or not Y_true.is_contiguous() or tuple(Y_true.shape) != shape:
+                raise ScoreArgumentError(f"device Y_true must be a contiguous torch.uint8 GPU tensor of shape {shape}")
+            torch.cuda.synchronize(Y_true.device)
+            yp, ydev, keep = Y_true.data_ptr(), 1, Y_true
+        else:
+            Y_true = np.asarray(Y_true)
+            if Y_true.shape != shape:
+                raise ScoreArgumentError(f"Y_true has shape {Y_true.shape}, the engine's networks {shape}")
+            if Y_true.size and Y_true.min() < 0:
+                raise ScoreArgumentError("Y_true holds a negative category")
+            keep = np.ascontiguousarray(np.minimum(Y_true, 255), dtype=np.uint8)
+            yp, ydev = keep.ctypes.data, 0
+        n_thr = int(thr.shape[0])
+        bufs = {"hist": np.zeros((self.L, n_thr + 1, 2), np.uint64), "conf": np.zeros((self.L, _lib.SCORE_NCONF), np.uint64),
+                "sums": np.zeros((self.L, _lib.SCORE_NSUM), np.float64), "auc": np.full(self.L, np.nan),
+                "auc_pairs": np.zeros((self.L, 2), np.uint64)}
+        ptrs = [bufs[o].ctypes.data if o in outputs else None for o in SCORE_OUTPUTS]
+        rc = self.lib.vmr_score_truth(self._h, yp, ydev, SCORES.index(score), int(bool(skip_diagonal)), n_thr,
+                                      thr.ctypes.data if n_thr else None, *ptrs)
+        del keep
+        if rc == _lib.VMR_EINVAL:
+            raise ScoreArgumentError(self.lib.vmr_last_error(self._h).decode())
+        self._check(rc)
+        out = {o: (bufs[o].astype(np.int64) if bufs[o].dtype == np.uint64 else bufs[o]) if o in outputs else None for o in SCORE_OUTPUTS}
+        out["n_ties"] = np.full(self.L, self.N * self.N - (self.N if skip_diagonal else 0), np.int64)
+        out["thresholds"] = thr
+        return out
 
     def snapshot(self):
         """Keep the current posteriors on the device (`_update_optimal_parameters`, reference model.py:925-942)."""

@@ -776,6 +776,48 @@ class VimureModel(TransformerMixin, BaseEstimator):
         return PredictiveCheck(obs, rep, observed_by_reporter=obs_m, replicated_by_reporter=rep_m, support=support, seed_y=seed_y,
                                seed_x=seed_x, n_trials=n_trials, theta=theta, lam=lam, eta=eta, eta_redraws=redraws, params=params)
 
+    def score_truth(self, Y_true, thresholds=None, score="rho1", skip_diagonal=False, auc=True, X=None, R=None):
+        """How well does rho recover a known network?  The scores of the reference's synthetic experiments -- F1 of `rho_1 >=
+        threshold` at every threshold (unreliable_reporters.py:189-200; `utils.get_optimal_threshold`), of the arg-max
+        read-out, AUC, Brier score, calibration -- as a `scoring.TruthScore`.  While rho is still on the GPU
+        (fit(keep_engine=True) and nothing has read rho_f: `get_inferred_model`'s rule), or with X= (a temporary engine, as in
+        `calculate_mean_poisson`), one pass on the device (vmr_score_truth) returns a few integers per layer and threshold;
+        otherwise `scoring.score_truth_np` runs on rho_f.  Y_true [L,N,N]: an array, a COO container or a uint8 GPU tensor.
+        thresholds None: np.linspace(0, 1, 101).  score "rho1" or "prob" (sum_{k>=1} rho_k).  The reference's heuristic
+        threshold 0.54 G_exp_nu - 0.01 (utils.py:200-217) is scored too and reported by `summary()`."""
+        from .scoring import TruthScore, check_thresholds, score_truth_np, SCORES
+        if getattr(self, "_rho_f", None) is None and getattr(self, "_engine", None) is None:
+            raise ValueError("the model has not been fitted: call fit first")
+        if score not in SCORES:
+            raise ValueError("score must be \"rho1\" or \"prob\"")
+        thr = check_thresholds(thresholds)
+        if Y_true is None:
+            raise ValueError("Y_true is None")
+        if not _is_torch(Y_true):
+            Y_true = Y_true.toarray() if hasattr(Y_true, "toarray") else np.asarray(Y_true)
+        if tuple(int(q) for q in Y_true.shape) != (self.L, self.N, self.N):
+            raise ValueError(f"Y_true has shape {tuple(Y_true.shape)}, the fitted model's networks {(self.L, self.N, self.N)}")
+        heur = np.array([0.54 * float(self.G_exp_nu) - 0.01]) if np.isfinite(getattr(self, "G_exp_nu", np.nan)) else None
+        dev = getattr(self, "_engine", None) if getattr(self, "_rho_f", None) is None else None
+        if X is not None or dev is not None:
+            eng, tmp = self._ppc_engine(X, R)
+            try:
+                res = eng.score_truth(Y_true, thresholds=thr, score=score, skip_diagonal=skip_diagonal, auc=auc)
+                hh = None if heur is None else eng.score_truth(Y_true, thresholds=heur, score=score, skip_diagonal=skip_diagonal,
+                                                               auc=False, outputs=("hist",))
+            finally:
+                if tmp:
+                    eng.close()
+        else:
+            if R is not None:
+                raise ValueError("R= is taken with X= only")
+            Yh = Y_true.cpu().numpy() if _is_torch(Y_true) else Y_true
+            res = score_truth_np(self.rho_f, Yh, thr, score, skip_diagonal)
+            hh = None if heur is None else score_truth_np(self.rho_f, Yh, heur, score, skip_diagonal)
+            if not auc:
+                res["auc"], res["auc_pairs"] = None, None
+        return TruthScore(res, thr, heuristic=None if hh is None else (heur[0], hh["hist"]), score=score, skip_diagonal=bool(skip_diagonal))
+
     def predict(self, X=None, method="rho_max", threshold=None):
         """Alias of `get_inferred_model` (the reference's experiment wrapper calls it predict)."""
         return self.get_inferred_model(method=method, threshold=threshold)
