@@ -370,6 +370,42 @@ int vmr_score_truth(vmr_handle h, const uint8_t* y_true, int y_true_on_device, i
                     double*   auc,        /* [L] or NULL */
                     uint64_t* auc_pairs   /* [L][2] or NULL */);
 
+/* The reporter table: each reporter's reports against the posterior, computed where rho lives -- the per-reporter counterpart of
+ * vmr_edge_table and vmr_ppc_observed(by_reporter), without the 8 L N^2 K bytes of rho crossing PCIe and without writing the
+ * support (vmr_mean_poisson: |S| elements of 24 B).  From the CURRENT rho (after vmr_restore: the snapshot's), the handle's own X
+ * and R, and the g_theta, g_lambda, g_nu of vmr_get_geometric.  With S_m = {(i,j) : R[l,i,j,m] != 0} (without R every (i,j), the
+ * diagonal included: vmr_mean_poisson's support), x = X[l,i,j,m], y the byte vmr_readout(h, method, threshold, ..) writes for the
+ * tie (method VMR_READ_RHO_MAX or VMR_READ_THRESHOLD; VMR_READ_RHO_MEAN: VMR_EINVAL), prob = sum_{k>=1} rho_k (k ascending, `prob`
+ * of vmr_edge_table) and mp the value vmr_mean_poisson defines for (l,i,j,m):
+ * counts [L'][M][VMR_RT_NCOUNT], exact integer sums:
+ *   0 n_scope     #S_m                                 1 n_rep   #{S_m : x > 0}             2 total  sum_{S_m} x
+ *   3 n_inferred  #{S_m : y > 0}                       4 hits    #{S_m : x > 0 and y > 0}
+ *   5 mutual      #{(i,j) in S_m, i != j : x_ijm > 0, (j,i) in S_m, x_jim > 0}   (ordered; statistic 3 of vmr_ppc_observed, per reporter)
+ *   6 n_out       #{(i,j) not in S_m : x > 0}          (reports the mask discards; 0 without R)
+ * sums [L'][M][VMR_RT_NSUM]:
+ *   0 exp_ties    sum_{S_m} prob                       1 exp_hits  sum_{S_m, x > 0} prob     2 exp_total  sum_{S_m} mp
+ * L' = L for layer < 0, else 1 (that layer's rows at index 0).  Host arrays; either may be NULL, not both.
+ * Cost: one pass over rho plus the reports (and the mask entries of partial rows) -- a tie whose mask row is all ones is added
+ * once, not once per reporter -- so O(ties + reports), not O(|S|).
+ * Determinism: every accumulator is a 64-bit integer; the sums are accumulated in FIXED POINT (no floating-point atomics, no
+ * order-dependent sum), so all outputs are bit-identical from run to run.  With b = ceil(log2 N^2), e_l the exponent with
+ * max G_lambda < 2^e_l (frexp; over the layers asked for) and e_x the exponent with sum X < 2^e_x (vmr_data_stats' sum_x + 1, frexp):
+ *   exp_ties, exp_hits   every prob (<= 1) is rounded to a multiple of q = 2^-(61 - b)
+ *   exp_total            = g_theta[l,m] Q + g_nu U:  Q = sum_{S_m} sum_k rho_k g_lambda_k, terms (<= max G_lambda) rounded to
+ *                        2^-(61 - b - e_l);  U = sum_{S_m} (sum_k rho_k) X[l,j,i,m], terms rounded to 2^-(61 - e_x); per term
+ *                        q = g_theta[l,m] 2^-(61 - b - e_l) + g_nu 2^-(61 - e_x)   (mp <= g_theta max G_lambda + g_nu max X)
+ * A sum of n terms is therefore within n q / 2 of the exact sum of its terms (n <= n_scope).  A row of rho that sums to more than
+ * 2 does not fit this fixed point: VMR_EINVAL.
+ * Any K, both data formats, every mask layout, handles of vmr_create_coo, mutuality on or off; fewer than 2^31 ties per layer.
+ * VMR_EINVAL with a message, before any launch: counts and sums both NULL, a bad method, layer >= L, a temporary that does not fit
+ * in the free device memory (88 B per reporter and layer; report-list handles: the tie-major index of vmr_mean_poisson and the
+ * tie -> position table).  NULL handle: VMR_EINVAL.  VMR_ESTATE before vmr_set_state.  VMR_ENAN if a sum is NaN.  Synchronises;
+ * temporaries are freed on every exit path. */
+#define VMR_RT_NCOUNT 7
+#define VMR_RT_NSUM 3
+int vmr_reporter_table(vmr_handle h, int method, double threshold, int layer,
+                       uint64_t* counts /* [L'][M][VMR_RT_NCOUNT] */, double* sums /* [L'][M][VMR_RT_NSUM] */);
+
 /* exp(E[log .]) of theta [L,M], lambda [L,K], nu from the current shape/rate parameters
  * (model.py:676-684), plus g_nu_cache = the G_exp_nu the last cache refresh held, i.e. the
  * value computed BEFORE the last nu update -- what `model.G_exp_nu` reads after `fit` and what

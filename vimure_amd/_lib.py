@@ -16,6 +16,9 @@ PPC_NSTAT = 6
 EDGE_REPORTED, EDGE_INFERRED = 1, 2
 SCORE_RHO1, SCORE_PROB = 0, 1
 SCORE_NCONF, SCORE_NSUM, SCORE_MAX_THR = 5, 4, 4096
+RT_NCOUNT, RT_NSUM = 7, 3
+RT_COUNT_NAMES = ["n_scope", "n_rep", "total", "n_inferred", "hits", "mutual", "n_out"]
+RT_SUM_NAMES = ["exp_ties", "exp_hits", "exp_total"]
 PPC_STAT_NAMES = ["n_pos", "total", "sumsq", "mutual", "ties_reported", "ties_agreed"]
 KERNEL_NAMES = ["gamma_mask", "gamma_counts", "phi", "rho", "elbo", "finalize", "rho_elbo", "rho_nostore"]
 
@@ -65,6 +68,7 @@ SIGNATURES = {
     "vmr_edge_table_size": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_uint64)]),
     "vmr_edge_table": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_uint64] + [C.c_void_p] * 14 + [C.c_int]),
     "vmr_score_truth": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p] + [C.c_void_p] * 5),
+    "vmr_reporter_table": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p]),
     "vmr_snapshot": (C.c_int, [C.c_void_p]),
     "vmr_restore": (C.c_int, [C.c_void_p]),
     "vmr_profile": (C.c_int, [C.c_void_p, C.c_int]),

@@ -24,35 +24,7 @@
 
 namespace {
 
-#define PR_HIST_M 2048   // by_reporter in LDS up to this many reporters (32 KB)
 #define PR_SLOTS 256     // tie slots a group walks per workgroup
-
-// a tie's mask row: c 0 empty, 1 all ones, 2 partial -- then mask words (lst null) or a sorted reporter list
-struct MaskRow {
-  int c;
-  unsigned n;
-  const uint64_t* w;
-  const unsigned short* lst;
-};
-
-__device__ __forceinline__ MaskRow mask_row(const uint8_t* cls, const uint64_t* Rb, const unsigned* rq, const unsigned short* Rm, int W, size_t t) {
-  MaskRow r;
-  r.c = cls[t]; r.n = 0; r.w = nullptr; r.lst = nullptr;
-  if (r.c == 2) {
-    if (rq) { const unsigned a = rq[t]; r.lst = Rm + a; r.n = rq[t + 1] - a; }
-    else r.w = Rb + t * (size_t)W;
-  }
-  return r;
-}
-
-__device__ __forceinline__ bool row_has(const MaskRow& r, unsigned m) {
-  if (r.c == 1) return true;
-  if (r.c != 2) return false;
-  if (!r.lst) return (r.w[m >> 6] >> (m & 63)) & 1ull;
-  unsigned a = 0, b = r.n;
-  while (a < b) { const unsigned c = a + ((b - a) >> 1); if ((unsigned)r.lst[c] < m) a = c + 1; else b = c; }
-  return a < r.n && (unsigned)r.lst[a] == m;
-}
 
 struct RepArgs {
   int L, N, M, K, W, G;

@@ -25,6 +25,11 @@ class ScoreArgumentError(EngineError, ValueError):
     are too many, a ground truth of another shape, no output asked for."""
 
 
+class ReporterTableArgumentError(EngineError, ValueError):
+    """An argument `reporter_table` refuses (VMR_EINVAL): a method that gives no categories, a layer out of range, no output
+    asked for."""
+
+
 SCORE_OUTPUTS = ("hist", "conf", "sums", "auc", "auc_pairs")
 
 # columns of `CaviEngine.edge_table`, in the order of vmr_edge_table's output pointers (device=True: the unsigned 32 / 64-bit columns
@@ -619,6 +624,31 @@ class CaviEngine:
         out["n_ties"] = np.full(self.L, self.N * self.N - (self.N if skip_diagonal else 0), np.int64)
         out["thresholds"] = thr
         return out
+
+    def reporter_table(self, method="rho_max", threshold=0.0, layer=None, outputs=("counts", "sums")):
+        """Each reporter's reports against the current rho, on the device (vmr_reporter_table): one pass over rho plus the
+        reports; neither rho nor the support crosses PCIe.  method "rho_max" or "threshold" (`rho_1 >= threshold`), as `readout`.
+        Returns {"counts": int64 [L', M, 7], "sums": float64 [L', M, 3]} -- `_lib.RT_COUNT_NAMES`: n_scope, n_rep, total,
+        n_inferred, hits, mutual, n_out; `_lib.RT_SUM_NAMES`: exp_ties, exp_hits, exp_total -- what `reporters.ReporterTable`
+        takes.  L' = L, or 1 with layer=.  outputs: which of the two to ask for (the other is None).  Bit-identical from run to
+        run: the sums are accumulated in fixed point (`reporters.sum_quanta`)."""
+        codes = {"rho_max": _lib.READ_RHO_MAX, "rho_mean": _lib.READ_RHO_MEAN, "threshold": _lib.READ_THRESHOLD}
+        if method not in codes:
+            raise ReporterTableArgumentError("'method' should be one of \"rho_max\", \"threshold\".")
+        outputs = tuple(outputs)
+        if any(o not in ("counts", "sums") for o in outputs):
+            raise ReporterTableArgumentError("outputs: a subset of (\"counts\", \"sums\") expected")
+        if layer is not None and not 0 <= int(layer) < self.L:
+            raise ReporterTableArgumentError(f"layer {layer} out of range [0, {self.L})")
+        Lq = self.L if layer is None else 1
+        counts = np.zeros((Lq, self.M, _lib.RT_NCOUNT), np.uint64) if "counts" in outputs else None
+        sums = np.zeros((Lq, self.M, _lib.RT_NSUM), np.float64) if "sums" in outputs else None
+        rc = self.lib.vmr_reporter_table(self._h, codes[method], float(threshold), self._layer_arg(layer),
+                                         None if counts is None else counts.ctypes.data, None if sums is None else sums.ctypes.data)
+        if rc == _lib.VMR_EINVAL:
+            raise ReporterTableArgumentError(self.lib.vmr_last_error(self._h).decode())
+        self._check(rc)
+        return {"counts": None if counts is None else counts.astype(np.int64), "sums": sums}
 
     def snapshot(self):
         """Keep the current posteriors on the device (`_update_optimal_parameters`, reference model.py:925-942)."""

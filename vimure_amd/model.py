@@ -818,6 +818,38 @@ class VimureModel(TransformerMixin, BaseEstimator):
                 res["auc"], res["auc_pairs"] = None, None
         return TruthScore(res, thr, heuristic=None if hh is None else (heur[0], hh["hist"]), score=score, skip_diagonal=bool(skip_diagonal))
 
+    def reporter_table(self, method="rho_max", threshold=None, layer=None, X=None, R=None):
+        """Which reporters are reliable, read off the fitted model on the GPU (vmr_reporter_table): per layer and reporter, how
+        many of their reports fall on ties the model infers (hits, false_reports, precision), how many inferred ties within their
+        scope they left out (omissions, recall), and how their report total compares with the expected one (exp_total, residual,
+        ratio) -- a `reporters.ReporterTable`; `frame()` gives one row per (layer, reporter).  One pass over rho plus the
+        reports: neither rho nor the support of R crosses PCIe.  method and threshold as `get_inferred_edgelist` takes them
+        (same warning and fall-back, same errors); layer: that layer only.  Beside the table: theta = G_exp_theta_f, theta_mean
+        = gamma_shp_f / gamma_rte_f and theta_interval, the central 95 % interval of the Gamma posterior (scipy.stats; left out,
+        None, where scipy is not installed).  Engine as in `calculate_mean_poisson`."""
+        from .reporters import ReporterTable
+        if not hasattr(self, "gamma_shp_f"):
+            raise ValueError("the model has not been fitted: call fit(..., keep_engine=True) first, or fit it and pass X=")
+        code, thr = self._edge_method(method, threshold)
+        if layer is not None and not 0 <= int(layer) < self.L:
+            raise ValueError(f"layer {layer} out of range [0, {self.L})")
+        eng, tmp = self._ppc_engine(X, R)
+        try:
+            res = eng.reporter_table(method=code, threshold=thr, layer=layer)
+        finally:
+            if tmp:
+                eng.close()
+        rows = slice(None) if layer is None else slice(int(layer), int(layer) + 1)
+        shp, rte = np.asarray(self.gamma_shp_f, dtype=np.float64)[rows], np.asarray(self.gamma_rte_f, dtype=np.float64)[rows]
+        interval = None
+        try:
+            from scipy import stats
+            interval = np.stack([stats.gamma.ppf(0.025, shp, scale=1.0 / rte), stats.gamma.ppf(0.975, shp, scale=1.0 / rte)], axis=-1)
+        except ImportError:
+            pass
+        return ReporterTable(res, layers=np.arange(self.L)[rows], theta=np.asarray(self.G_exp_theta_f)[rows], theta_mean=shp / rte,
+                             theta_interval=interval, method=code, threshold=thr if code == "threshold" else None)
+
     def predict(self, X=None, method="rho_max", threshold=None):
         """Alias of `get_inferred_model` (the reference's experiment wrapper calls it predict)."""
         return self.get_inferred_model(method=method, threshold=threshold)
