@@ -154,7 +154,9 @@ def test_device_generator_kernel_against_the_references_draws_by_moments(name):
     so it is held to the REFERENCE's own output (fixture K, dumped from the real `_build_X`) statistically: over 300 seeds, per
     (layer, reporter): the mean count, the density of non-zero counts and the reciprocity sum_ij X_ij X_ji of the reference's draw
     must lie inside the kernel's distribution (inside the range of the 300 draws cell by cell, |z| < 4.5 pooled over a layer's
-    reporters), and the ensemble mean of every cell must match the analytic mean (lambda theta + eta mirror) / (1 - eta^2) within 5 standard errors."""
+    reporters), and the ensemble mean of every cell must match the analytic mean (lambda theta + eta mirror) / (1 - eta^2) within 5 standard errors.
+    This holds the ALGORITHM to the reference's own draws; the kernel's stream itself -- Philox, the counter words, both Poisson
+    branches, the clamp -- is held element by element to its NumPy restatement in tests/test_hip_draws_exact.py."""
     import torch
     theta, lam = G[f"{name}_theta"], G[f"{name}_lambda_k"]
     eta, self_rep = float(G[f"{name}_build_mutuality"]), bool(G[f"{name}_build_flag_self_reporter"])

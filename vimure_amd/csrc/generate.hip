@@ -8,7 +8,9 @@
 // reporter, draw) -- a draw depends on its coordinates only, so the result does not depend on the launch shape.  Output: the uint8
 // [L][N][N][M] tensor vmr_create takes (counts clamped to 255), written once, coalesced along the reporters.
 // Not the reference's RandomState stream (a GPU cannot follow MT19937 draw by draw): the host classes keep that exact mode
-// (vimure_amd/synthetic.py, pinned bit for bit by tests/golden/K_generators.npz); this one is held to it by moments.
+// (vimure_amd/synthetic.py, pinned bit for bit by tests/golden/K_generators.npz); this one is held to it by moments
+// (tests/test_generators.py) and, element by element, to the NumPy restatement of its own stream (tests/draws_ref.py,
+// tests/test_hip_draws_exact.py).
 #include "vmr_internal.h"
 #include "report_draw.h"
 

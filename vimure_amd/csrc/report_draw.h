@@ -16,7 +16,9 @@ struct Rng {   // a stream of uniforms for one (layer, pair, reporter): Philox c
   unsigned w[4];
   __device__ Rng(unsigned long long seed, unsigned l, unsigned long long pair, unsigned m)
       : k0((unsigned)seed), k1((unsigned)(seed >> 32)), c0((unsigned)pair), c1((unsigned)(pair >> 32)), c2(m ^ (l << 20)), n(0), have(0) {}
-  __device__ double uniform() {   // (0, 1): 53 bits, never 0
+  // [2^-54, 1]: 53 bits + 0.5, never 0.  A call's words are consumed 3, 2 then 1, 0.  The + 0.5 is exact below 2^52 and rounds to even
+  // from there on, so all-ones words (the integer 2^53 - 1) give exactly 1.0 -- at probability 2^-53, left as it is.
+  __device__ double uniform() {
     if (have < 2) {
       unsigned c[4] = {c0, c1, c2, n++};
       philox4x32_10(c, k0, k1);
