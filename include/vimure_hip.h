@@ -406,6 +406,52 @@ int vmr_score_truth(vmr_handle h, const uint8_t* y_true, int y_true_on_device, i
 int vmr_reporter_table(vmr_handle h, int method, double threshold, int layer,
                        uint64_t* counts /* [L'][M][VMR_RT_NCOUNT] */, double* sums /* [L'][M][VMR_RT_NSUM] */);
 
+/* The log predictive density of HELD-OUT reports under the fitted posterior, scored where rho lives -- what k-fold
+ * cross-validation needs to compare K, mutuality or priors on data without a ground truth (ELBOs of different K are not
+ * comparable).  It stands beside the data term of `__ELBO` (model.py:948-1019), which is the same Poisson likelihood in
+ * expectation over the entries INSIDE the mask, and `_calculate_mean_poisson` (model.py:1220-1293), whose value `mean` is.  An
+ * entry (l,i,j,m) with R = 0 is outside the model: its count is discarded and it adds nothing to the rates (vmr_reporter_table
+ * counts such reports as n_out); this function evaluates the likelihood at such entries, which no other entry point does.
+ * The list: n entries el, ei, ej, em (int32 subscripts), ex the held-out counts (>= 0), ext the mirrored counts X[l,j,i,m] to
+ * condition on (>= 0; NULL: all 0); device pointers when in_on_device != 0.  It must be non-decreasing in el; entries need not be
+ * sorted otherwise and may repeat.  A list sorted by (l,i,j,m) reads each rho row from neighbouring lanes and is the fast case.
+ * theta host [L][M], lambda host [L][K] and eta are the caller's (as vmr_ppc_replicates takes its tables): the function is a
+ * pure function of (rho, the list, theta, lambda, eta, the handle's mask).  The handle's X is never read and no tie-major index
+ * is built; report-list handles take the tie -> position table of vmr_mean_poisson (4 B per tie of a layer).
+ * Per entry e, with rho the CURRENT row of tie (l,i,j) (after vmr_restore: the snapshot's) and x = ex[e]:
+ *   mu_k    = theta[l][m] lambda[l][k] + eta ext[e]
+ *   mean[e] = sum_k rho_k mu_k, k ascending, every product and every sum rounded on its own (`mean` of vmr_edge_table's convention)
+ *   logp[e] = log sum_k rho_k Poisson(x; mu_k), as a log-sum-exp over the categories with rho_k > 0 of
+ *             b_k = x log(mu_k) - mu_k + log(rho_k), lgamma(x + 1) subtracted once.  mu_k = 0 and x = 0 contributes log(rho_k);
+ *             mu_k = 0 and x > 0 contributes nothing; if no category contributes, logp[e] = -inf.
+ * logp, mean: [n] or NULL, device pointers when out_on_device != 0.  Per layer, over the layer's entries:
+ *   sums   host [L][VMR_HO_NSUM] or NULL:    0 sum logp over the entries with finite logp    1 sum (x - mean)^2    2 sum x    3 sum mean
+ *   counts host [L][VMR_HO_NCOUNT] or NULL:  0 entries    1 entries with x > 0    2 entries with logp = -inf (left out of sums[l][0])
+ *          3 entries whose (l,i,j,m) lies INSIDE the handle's own mask: in-sample entries, not an error (a cross-validation
+ *            driver asserts 0)
+ * K <= 8: one lane per entry (K = 2: the row in one 16-byte load); larger K, up to 256: a group of 16 lanes per entry, which folds
+ * the running maximum and the scaled sum by shuffles in a fixed order.  All sums are doubles reduced by a fixed two-stage tree
+ * (a workgroup per 1024 consecutive entries of a layer's segment, then one workgroup per layer) whose shape depends on the
+ * segment length alone: no floating-point atomics, no tickets, bit-identical from run to run.
+ * VMR_EINVAL with a message, before any launch: NULL handle (no message), a NULL subscript or count array, all four outputs NULL,
+ * n = 0 or n >= 2^31, NULL theta or lambda, a negative or non-finite theta, lambda or eta, a temporary that does not fit in the free
+ * device memory (host lists: 24 n B; host logp / mean: 8 n B each; 64 B per 1024 entries).  VMR_ESTATE before vmr_set_state.
+ * VMR_EINVAL from the kernels: a subscript out of range, a negative ex or ext, a decreasing el -- the entry sets a flag, reads
+ * nothing and adds nothing; the outputs are then unspecified.  VMR_ENAN, after the kernel: a logp or a mean is NaN.
+ * Any K, both data formats, every mask layout, handles of vmr_create_coo; fewer than 2^31 ties per layer.  Synchronises;
+ * temporaries are freed on every exit path. */
+#define VMR_HO_NSUM 4
+#define VMR_HO_NCOUNT 4
+int vmr_heldout_loglik(vmr_handle h, uint64_t n,
+                       const int32_t* el, const int32_t* ei, const int32_t* ej, const int32_t* em,
+                       const int32_t* ex,   /* the held-out counts, >= 0 */
+                       const int32_t* ext,  /* the mirrored counts X[l,j,i,m] to condition on, or NULL = 0 */
+                       int in_on_device,
+                       const double* theta /* host [L][M] */, const double* lambda /* host [L][K] */, double eta,
+                       double* logp /* [n] or NULL */, double* mean /* [n] or NULL */, int out_on_device,
+                       double* sums   /* host [L][VMR_HO_NSUM] or NULL */,
+                       uint64_t* counts /* host [L][VMR_HO_NCOUNT] or NULL */);
+
 /* exp(E[log .]) of theta [L,M], lambda [L,K], nu from the current shape/rate parameters
  * (model.py:676-684), plus g_nu_cache = the G_exp_nu the last cache refresh held, i.e. the
  * value computed BEFORE the last nu update -- what `model.G_exp_nu` reads after `fit` and what

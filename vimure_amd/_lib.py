@@ -19,6 +19,9 @@ SCORE_NCONF, SCORE_NSUM, SCORE_MAX_THR = 5, 4, 4096
 RT_NCOUNT, RT_NSUM = 7, 3
 RT_COUNT_NAMES = ["n_scope", "n_rep", "total", "n_inferred", "hits", "mutual", "n_out"]
 RT_SUM_NAMES = ["exp_ties", "exp_hits", "exp_total"]
+HO_NSUM, HO_NCOUNT = 4, 4
+HO_SUM_NAMES = ["logp", "sq_err", "total", "exp_total"]
+HO_COUNT_NAMES = ["n", "n_pos", "n_inf", "n_in_mask"]
 PPC_STAT_NAMES = ["n_pos", "total", "sumsq", "mutual", "ties_reported", "ties_agreed"]
 KERNEL_NAMES = ["gamma_mask", "gamma_counts", "phi", "rho", "elbo", "finalize", "rho_elbo", "rho_nostore"]
 
@@ -69,6 +72,8 @@ SIGNATURES = {
     "vmr_edge_table": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_uint64] + [C.c_void_p] * 14 + [C.c_int]),
     "vmr_score_truth": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p] + [C.c_void_p] * 5),
     "vmr_reporter_table": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p]),
+    "vmr_heldout_loglik": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_void_p, C.c_double,
+                                     C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "vmr_snapshot": (C.c_int, [C.c_void_p]),
     "vmr_restore": (C.c_int, [C.c_void_p]),
     "vmr_profile": (C.c_int, [C.c_void_p, C.c_int]),

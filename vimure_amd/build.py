@@ -35,7 +35,8 @@ def units(dev=False):
          ("ppc_rep", os.path.join(CSRC, "ppc_rep.hip"), extra),        # posterior predictive replicates, reduced
          ("edge_table", os.path.join(CSRC, "edge_table.hip"), extra),  # the inferred network as an edge table
          ("score_truth", os.path.join(CSRC, "score_truth.hip"), extra),  # the posterior scored against a ground truth
-         ("reporter_table", os.path.join(CSRC, "reporter_table.hip"), extra)]  # each reporter's reports against the posterior
+         ("reporter_table", os.path.join(CSRC, "reporter_table.hip"), extra),  # each reporter's reports against the posterior
+         ("heldout", os.path.join(CSRC, "heldout.hip"), extra)]        # held-out reports scored under the posterior
     dev_ks = tuple(int(k) for k in os.environ.get("VMR_DEV_KS", "2").split(","))   # (VMR_DEV_KS=2,3: also the K = 3 sweep kernels)
     for k in (dev_ks if dev else KS):
         u.append((f"sweep_sl_k{k}", os.path.join(CSRC, "sweep_sl.hip"), extra + [f"-DVMR_K={k}"]))

@@ -225,7 +225,7 @@ int ppc_layer_mask(vmr_ctx* h, int l, PpcLayer& p) {
   return VMR_OK;
 }
 
-int ppc_prep_layer(vmr_ctx* h, Tmp& tm, int l, bool positives, bool walk, LayerPrep& lp, bool want_index, bool offsets) {
+int ppc_prep_layer(vmr_ctx* h, Tmp& tm, int l, bool positives, bool walk, LayerPrep& lp, bool want_index, bool offsets, bool mirror) {
   const Geo& g = h->g;
   const size_t T = (size_t)g.N * g.N, NS = (T + 63) / 64;
   const ParOff o = par_off(g.L, g.Mp, g.K);
@@ -237,7 +237,7 @@ int ppc_prep_layer(vmr_ctx* h, Tmp& tm, int l, bool positives, bool walk, LayerP
   p.gla = h->par + o.G_la + (size_t)l * g.K;
   p.gnu = h->par + o.sc + SC_G_NU;
   auto take = [&](auto** q, size_t bytes, const char* what) { const int rc = tm.get(q, bytes, what); if (!rc) lp.mine.push_back(*q); return rc; };
-  const bool index = h->sparse && (want_index || positives || (walk && g.mut));   // the counts are needed: positives, or XT
+  const bool index = h->sparse && (want_index || positives || (walk && g.mut && mirror));   // the counts are needed: positives, or XT
   if (h->sparse) {
     if (walk) {
       unsigned* inv = nullptr;

@@ -110,8 +110,10 @@ int ppc_layer_mask(vmr_ctx* h, int l, PpcLayer& p);
 
 // positives: the counts are needed (the index of report-list handles is built) and poff is filled; walk: rho is read by tie (the
 // tie -> position table) and, with mutuality, the mirror counts; index: build the index of a report-list handle in any case;
-// offsets = false: no support offsets (off stays null, nsup 0) for a caller that walks ties, not the support (edge_table.hip).
-int ppc_prep_layer(vmr_ctx* h, Tmp& tm, int l, bool positives, bool walk, LayerPrep& lp, bool index = false, bool offsets = true);
+// offsets = false: no support offsets (off stays null, nsup 0) for a caller that walks ties, not the support (edge_table.hip);
+// mirror = false: a walk whose mirror counts come from its caller (heldout.hip): mutuality alone builds no index for them.
+int ppc_prep_layer(vmr_ctx* h, Tmp& tm, int l, bool positives, bool walk, LayerPrep& lp, bool index = false, bool offsets = true,
+                   bool mirror = true);
 void ppc_release_layer(Tmp& tm, LayerPrep& lp);
 
 #endif  // VMR_PPC_LAYER_H

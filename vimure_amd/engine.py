@@ -30,6 +30,11 @@ class ReporterTableArgumentError(EngineError, ValueError):
     asked for."""
 
 
+class HeldoutArgumentError(EngineError, ValueError):
+    """An argument `heldout_loglik` refuses (VMR_EINVAL): an empty list, a subscript out of range, a negative count, a list that
+    decreases in the layer, a negative or non-finite table entry."""
+
+
 SCORE_OUTPUTS = ("hist", "conf", "sums", "auc", "auc_pairs")
 
 # columns of `CaviEngine.edge_table`, in the order of vmr_edge_table's output pointers (device=True: the unsigned 32 / 64-bit columns
@@ -649,6 +654,66 @@ class CaviEngine:
             raise ReporterTableArgumentError(self.lib.vmr_last_error(self._h).decode())
         self._check(rc)
         return {"counts": None if counts is None else counts.astype(np.int64), "sums": sums}
+
+    def heldout_loglik(self, subs, x, xt=None, theta=None, lam=None, eta=0.0, per_entry=True, device=False):
+        """The log predictive density of held-out reports under the current rho, on the device (vmr_heldout_loglik).  subs: the 4
+        index arrays (l, i, j, m) of the entries, non-decreasing in l (a list sorted by (l, i, j, m) is the fast case); x: their
+        held-out counts (>= 0); xt: the mirrored counts X[l,j,i,m] to condition on (None: 0); NumPy arrays, or int32 CUDA tensors
+        (all of them).  theta [L, M], lam [L, K], eta: the caller's tables -- the rate of category k is theta[l,m] lam[l,k] + eta xt.
+        This engine's X is not read; its mask only counts the entries that lie inside it.  Returns {"logp": [n], "mean": [n]
+        (None without per_entry; torch tensors on the GPU with device=True), "sums": float64 [L, 4] (`_lib.HO_SUM_NAMES`: the sum
+        of the finite logp, of (x - mean)^2, of x, of mean), "counts": int64 [L, 4] (`_lib.HO_COUNT_NAMES`: entries, entries
+        with x > 0, entries with logp = -inf, entries inside the mask)}.  Bit-identical from run to run."""
+        if theta is None or lam is None:
+            raise HeldoutArgumentError("theta and lam are needed: the tables the held-out reports are scored under")
+        theta, lam = _f64(theta), _f64(lam)
+        if theta.shape != (self.L, self.M) or lam.shape != (self.L, self.K):
+            raise HeldoutArgumentError(f"theta {theta.shape}, lam {lam.shape}: expected ({self.L}, {self.M}), ({self.L}, {self.K})")
+        if len(subs) != 4:
+            raise HeldoutArgumentError("subs must be the 4 index arrays (l, i, j, m)")
+        cols = list(subs) + [x] + ([] if xt is None else [xt])
+        on_dev = _is_torch(x)
+        if any(_is_torch(a) != on_dev for a in cols):
+            raise HeldoutArgumentError("subs, x and xt must be all NumPy arrays or all GPU tensors")
+        if on_dev:
+            import torch
+            if any(not _is_torch(a) or not a.is_cuda or a.dtype != torch.int32 or not a.is_contiguous() for a in cols):
+                raise HeldoutArgumentError("device lists must be contiguous torch.int32 GPU tensors, all of them")
+            torch.cuda.synchronize(x.device)
+            ptrs = [a.data_ptr() for a in cols]
+        else:
+            for a in cols:   # (what fits is handed on: the entry point names a subscript out of range or a negative count)
+                a = np.asarray(a)
+                if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+                    raise HeldoutArgumentError("subscripts and counts travel as 32-bit integers: a value does not fit")
+            cols = [np.ascontiguousarray(np.asarray(a).reshape(-1), dtype=np.int32) for a in cols]
+            ptrs = [a.ctypes.data for a in cols]
+        n = int(cols[0].shape[0])
+        if any(int(a.shape[0]) != n or a.ndim != 1 for a in cols):
+            raise HeldoutArgumentError("subs, x and xt: 1-D arrays of one length expected")
+        if xt is None:
+            ptrs.append(None)
+        logp = mean = None
+        lp_ptr = mn_ptr = None
+        if per_entry:
+            if device:
+                import torch
+                dev = torch.device("cuda", self.device)
+                logp, mean = torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.float64, device=dev)
+                torch.cuda.synchronize(dev)
+                lp_ptr, mn_ptr = logp.data_ptr(), mean.data_ptr()
+            else:
+                logp, mean = np.empty(n), np.empty(n)
+                lp_ptr, mn_ptr = logp.ctypes.data, mean.ctypes.data
+        sums = np.zeros((self.L, _lib.HO_NSUM), np.float64)
+        counts = np.zeros((self.L, _lib.HO_NCOUNT), np.uint64)
+        rc = self.lib.vmr_heldout_loglik(self._h, n, *ptrs, int(on_dev), theta.ctypes.data, lam.ctypes.data, float(eta), lp_ptr, mn_ptr,
+                                         int(bool(device and per_entry)), sums.ctypes.data, counts.ctypes.data)
+        del cols
+        if rc == _lib.VMR_EINVAL:
+            raise HeldoutArgumentError(self.lib.vmr_last_error(self._h).decode())
+        self._check(rc)
+        return {"logp": logp, "mean": mean, "sums": sums, "counts": counts.astype(np.int64)}
 
     def snapshot(self):
         """Keep the current posteriors on the device (`_update_optimal_parameters`, reference model.py:925-942)."""

@@ -850,6 +850,28 @@ class VimureModel(TransformerMixin, BaseEstimator):
         return ReporterTable(res, layers=np.arange(self.L)[rows], theta=np.asarray(self.G_exp_theta_f)[rows], theta_mean=shp / rte,
                              theta_interval=interval, method=code, threshold=thr if code == "threshold" else None)
 
+    def heldout_loglik(self, subs, x, xt=None, estimate="mean", X=None, R=None):
+        """The log predictive density of reports the fit never saw, scored on the GPU under the best realisation
+        (vmr_heldout_loglik): subs the 4 index arrays (l, i, j, m) of the held-out entries (non-decreasing in l), x their counts,
+        xt the mirrored counts X[l,j,i,m] their rates condition on (None: taken from X= when it is given and the model has
+        mutuality, else 0).  estimate "mean" plugs in the posterior means of theta, lambda and eta, "geometric" the g_theta,
+        g_lambda, g_nu `calculate_mean_poisson` uses (`crossval.plug_in_tables`).  Returns the dict of
+        `CaviEngine.heldout_loglik`: logp and mean per entry, and per layer the sums and counts -- `counts[:, 3]` is the number of
+        entries that lie INSIDE the engine's mask, i.e. that the fit has seen.  `crossval.cross_validate` drives whole folds
+        through this.  Engine as in `calculate_mean_poisson`."""
+        from .crossval import mirror_counts, plug_in_tables
+        if not hasattr(self, "gamma_shp_f"):
+            raise ValueError("the model has not been fitted: call fit(..., keep_engine=True) first, or fit it and pass X=")
+        if xt is None and X is not None and self.mutuality and not (isinstance(X, pd.DataFrame) or type(X).__name__ == "Graph"):
+            xt = mirror_counts(X, subs)
+        eng, tmp = self._ppc_engine(X, R)
+        try:
+            theta, lam, eta = plug_in_tables(self, eng, estimate)
+            return eng.heldout_loglik(subs, x, xt, theta=theta, lam=lam, eta=eta)
+        finally:
+            if tmp:
+                eng.close()
+
     def predict(self, X=None, method="rho_max", threshold=None):
         """Alias of `get_inferred_model` (the reference's experiment wrapper calls it predict)."""
         return self.get_inferred_model(method=method, threshold=threshold)
