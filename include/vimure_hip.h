@@ -452,6 +452,63 @@ int vmr_heldout_loglik(vmr_handle h, uint64_t n,
                        double* sums   /* host [L][VMR_HO_NSUM] or NULL */,
                        uint64_t* counts /* host [L][VMR_HO_NCOUNT] or NULL */);
 
+/* Every report of the support scored under the posterior, where rho lives: which individual reports, and which omissions, does
+ * the fitted model disbelieve -- the per-report counterpart of vmr_reporter_table, and the exact in-sample log predictive density
+ * beside the held-out one of vmr_heldout_loglik.  The in-sample support cannot be handed to vmr_heldout_loglik as a list (24 B
+ * per element; L N^2 M elements without a mask); this walks it, keeps integer histograms and a few sums, and writes out only the
+ * rows worth reading.
+ * The support S = {(l,i,j,m) : R != 0}; without R every (i,j,m), the diagonal included: vmr_mean_poisson's support, walked in its
+ * lexicographic (l,i,j,m) order.  For an element e of S, from the handle's own data and the CURRENT rho (after vmr_restore: the
+ * snapshot's):  x = X[l,i,j,m];  xt = X[l,j,i,m] with mutuality, else 0;  theta host [L][M], lambda host [L][K] and eta are the
+ * caller's tables, as vmr_heldout_loglik takes them;  mean[e] and logp[e] are what vmr_heldout_loglik defines for the entry
+ * (l,i,j,m) with ex = x and ext = xt -- the same device functions, term for term, with the same -inf and NaN rules, so the same
+ * bits.  The score is s = -logp (+inf where logp = -inf).  An element is a REPORT when x > 0, an OMISSION when x = 0; it is FLAGGED
+ * iff its class is in `select` (VMR_RS_REPORTS | VMR_RS_OMISSIONS: 1, 2 or 3) and s >= threshold (finite, or +inf: only the
+ * elements with logp = -inf).
+ * Outputs, host arrays unless noted, any of them NULL (not all); L' = L for layer < 0, else 1:
+ *   hist   [L'][n_edges + 1][2]: over ALL of S whatever `select` is, hist[l][c][b] = #{e : c = #{tau : edges[tau] <= s}}, b = 0
+ *          for reports, 1 for omissions; edges finite and non-decreasing, n_edges in [0, VMR_RS_MAX_EDGES] (vmr_score_truth's
+ *          convention; s = +inf lands in the last bin).  Without hist the edges are not read.
+ *   sums   [L'][VMR_RS_NSUM]:   0 sum logp over the elements with finite logp (the in-sample log predictive density)
+ *          1 sum (x - mean)^2    2 sum x    3 sum mean          (the columns of VMR_HO_NSUM)
+ *   counts [L'][VMR_RS_NCOUNT]: 0 elements    1 reports    2 elements with logp = -inf    3 flagged elements
+ *   by_reporter [L'][M][2]: the flagged elements of reporter m, by class
+ *   the table: one row per flagged element in lexicographic (l,i,j,m) order -- sl, si, sj, sm, x, xt (int32), logp, mean; n is the
+ *          capacity: below the row count VMR_EINVAL before anything is written; n = 0 and every row pointer NULL: no table pass;
+ *          device pointers when out_on_device != 0.
+ * vmr_report_scores_size gives the row count, the sum over the layers of counts[.][3], for the same arguments.
+ * A count pass walks the support (a group of lanes per tie, the tie's support reporters in ascending m): the likelihood at every
+ * element, the integer bins in LDS first (reporters up to 2048, the histogram where it fits beside them, global integer atomics
+ * beyond), a tie's flagged count; an exclusive 64-bit sum of those gives a tie's first row, and a fill pass -- only when rows are
+ * asked for, only over ties that hold one -- writes a flagged element at its tie's offset plus its rank among the group's lanes.
+ * The sums are doubles: a workgroup owns a fixed contiguous range of ties, a lane adds its elements in walk order, the waves fold
+ * by shuffles, the workgroup in LDS, and a last kernel adds the workgroups' partials in index order.  No floating-point atomics,
+ * no tickets, a tree that depends on N and M alone: every output is bit-identical from run to run.
+ * Any K up to 256, both data formats, every mask layout, handles of vmr_create_coo, counts up to 2^31 - 1; fewer than 2^31 ties per
+ * layer.  Layers are processed one at a time; report-list handles take the tie-major index of vmr_mean_poisson and the tie ->
+ * position table per layer.
+ * VMR_EINVAL with a message, before any launch: NULL handle (no message), NULL theta or lambda, a negative or non-finite theta,
+ * lambda or eta, select outside 1..3, a NaN or -inf threshold, layer >= L, every output NULL, n_edges out of range, hist with
+ * n_edges > 0 and edges NULL, a non-finite or decreasing edge, a temporary that does not fit in the free device memory (8 B per
+ * tie of a layer, and of every layer asked for when rows are; 64 B per workgroup; the bins; host rows: 40 B per row of a layer).
+ * VMR_ESTATE before vmr_set_state.  VMR_ENAN, after the count pass: a logp or a mean is NaN (no row is then written).
+ * Synchronises; temporaries are freed on every exit path. */
+enum { VMR_RS_REPORTS = 1, VMR_RS_OMISSIONS = 2 };
+#define VMR_RS_NSUM 4
+#define VMR_RS_NCOUNT 4
+#define VMR_RS_MAX_EDGES 4096
+int vmr_report_scores_size(vmr_handle h, int layer, const double* theta, const double* lambda, double eta,
+                           int select, double threshold, uint64_t* n);
+int vmr_report_scores(vmr_handle h, int layer, const double* theta /* host [L][M] */, const double* lambda /* host [L][K] */, double eta,
+                      int select, double threshold,
+                      int n_edges, const double* edges,
+                      uint64_t* hist        /* [L'][n_edges + 1][2] or NULL */,
+                      double*   sums        /* [L'][VMR_RS_NSUM] or NULL */,
+                      uint64_t* counts      /* [L'][VMR_RS_NCOUNT] or NULL */,
+                      uint64_t* by_reporter /* [L'][M][2] or NULL */,
+                      uint64_t n, int32_t* sl, int32_t* si, int32_t* sj, int32_t* sm,
+                      int32_t* x, int32_t* xt, double* logp, double* mean, int out_on_device);
+
 /* exp(E[log .]) of theta [L,M], lambda [L,K], nu from the current shape/rate parameters
  * (model.py:676-684), plus g_nu_cache = the G_exp_nu the last cache refresh held, i.e. the
  * value computed BEFORE the last nu update -- what `model.G_exp_nu` reads after `fit` and what

@@ -22,6 +22,10 @@ RT_SUM_NAMES = ["exp_ties", "exp_hits", "exp_total"]
 HO_NSUM, HO_NCOUNT = 4, 4
 HO_SUM_NAMES = ["logp", "sq_err", "total", "exp_total"]
 HO_COUNT_NAMES = ["n", "n_pos", "n_inf", "n_in_mask"]
+RS_REPORTS, RS_OMISSIONS = 1, 2
+RS_NSUM, RS_NCOUNT, RS_MAX_EDGES = 4, 4, 4096
+RS_SUM_NAMES = ["logp", "sq_err", "total", "exp_total"]
+RS_COUNT_NAMES = ["n", "n_reports", "n_inf", "n_flagged"]
 PPC_STAT_NAMES = ["n_pos", "total", "sumsq", "mutual", "ties_reported", "ties_agreed"]
 KERNEL_NAMES = ["gamma_mask", "gamma_counts", "phi", "rho", "elbo", "finalize", "rho_elbo", "rho_nostore"]
 
@@ -74,6 +78,9 @@ SIGNATURES = {
     "vmr_reporter_table": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p]),
     "vmr_heldout_loglik": (C.c_int, [C.c_void_p, C.c_uint64] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_void_p, C.c_double,
                                      C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "vmr_report_scores_size": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_double, C.POINTER(C.c_uint64)]),
+    "vmr_report_scores": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_double, C.c_int, C.c_void_p]
+                          + [C.c_void_p] * 4 + [C.c_uint64] + [C.c_void_p] * 8 + [C.c_int]),
     "vmr_snapshot": (C.c_int, [C.c_void_p]),
     "vmr_restore": (C.c_int, [C.c_void_p]),
     "vmr_profile": (C.c_int, [C.c_void_p, C.c_int]),

@@ -17,6 +17,7 @@ HOST_SRC = os.path.join(CSRC, "host_init.c")
 HOST_LIB = os.path.join(HERE, "libvimure_host.so")
 HEADERS = [os.path.join(CSRC, "vmr_internal.h"), os.path.join(CSRC, "sweep_sl.h"), os.path.join(CSRC, "sweep_gen.h"),
            os.path.join(CSRC, "sample_draw.h"), os.path.join(CSRC, "report_draw.h"), os.path.join(CSRC, "ppc_layer.h"), os.path.join(CSRC, "rho_row.h"),
+           os.path.join(CSRC, "report_lik.h"),
            os.path.join(ROOT, "include", "vimure_hip.h")]
 KS = (2, 3, 4, 5, 6, 7, 8)
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
@@ -36,7 +37,8 @@ def units(dev=False):
          ("edge_table", os.path.join(CSRC, "edge_table.hip"), extra),  # the inferred network as an edge table
          ("score_truth", os.path.join(CSRC, "score_truth.hip"), extra),  # the posterior scored against a ground truth
          ("reporter_table", os.path.join(CSRC, "reporter_table.hip"), extra),  # each reporter's reports against the posterior
-         ("heldout", os.path.join(CSRC, "heldout.hip"), extra)]        # held-out reports scored under the posterior
+         ("heldout", os.path.join(CSRC, "heldout.hip"), extra),        # held-out reports scored under the posterior
+         ("report_scores", os.path.join(CSRC, "report_scores.hip"), extra)]  # every report of the support scored under the posterior
     dev_ks = tuple(int(k) for k in os.environ.get("VMR_DEV_KS", "2").split(","))   # (VMR_DEV_KS=2,3: also the K = 3 sweep kernels)
     for k in (dev_ks if dev else KS):
         u.append((f"sweep_sl_k{k}", os.path.join(CSRC, "sweep_sl.hip"), extra + [f"-DVMR_K={k}"]))

@@ -23,13 +23,13 @@
 #include "vmr_internal.h"
 #include "ppc_layer.h"
 #include "rho_row.h"
+#include "report_lik.h"
 
 namespace {
 
 #define HO_TPB 256
 #define HO_CHUNK 1024   // entries of a workgroup
 #define HO_G 16         // lanes of an entry's group (K > KMAX)
-#define HO_LGT 256      // lgamma(x + 1) tabulated below this count
 
 // flag bits
 #define HO_BAD_NAN 1
@@ -54,49 +54,6 @@ struct HoAcc {
   double s[VMR_HO_NSUM];
   u64 c[VMR_HO_NCOUNT];
 };
-
-// mu_k = theta lambda_k + eta xt and the mean's running sum: every product and every sum rounded on its own (rho_row.h's convention)
-__device__ __forceinline__ double ho_rate(double th, double la, double exy) {
-#pragma clang fp contract(off)
-  const double a = th * la;
-  return a + exy;
-}
-__device__ __forceinline__ double ho_mul(double a, double b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
-__device__ __forceinline__ double ho_add(double a, double b) {
-#pragma clang fp contract(off)
-  return a + b;
-}
-
-// b_k = x log mu_k - mu_k + log rho_k, or -inf where the category adds nothing (rho_k not positive; a zero rate against x > 0)
-__device__ __forceinline__ double ho_term(double r, double mu, double xd, bool xpos) {
-  if (!(r > 0.0)) return -INFINITY;
-  if (mu == 0.0) return xpos ? -INFINITY : log(r);
-  return xd * log(mu) - mu + log(r);
-}
-
-// lgamma(x + 1)
-__device__ __forceinline__ double ho_lgam1(unsigned x, const double* __restrict__ lgt) {
-  if (x < HO_LGT) return lgt[x];
-  const double z = (double)x + 1.0, r = 1.0 / z, r2 = r * r;   // z >= 257: the next term of the series is below 1e-20
-  return fma(z - 0.5, log(z), -z) + 0.91893853320467274178 + r * (1.0 / 12.0 - r2 * (1.0 / 360.0 - r2 * (1.0 / 1260.0)));
-}
-
-// maximum mx and sum s of exp(b - mx), folded with another pair (either may be empty: mx = -inf, s = 0; a NaN sits in s)
-__device__ __forceinline__ void ho_fold(double& mx, double& s, double mx2, double s2) {
-  const double m = mx2 > mx ? mx2 : mx;
-  const double e1 = mx == m ? 1.0 : exp(mx - m), e2 = mx2 == m ? 1.0 : exp(mx2 - m);
-  s = s * e1 + s2 * e2;
-  mx = m;
-}
-
-__device__ __forceinline__ double ho_logp(double mx, double s, double lg) {
-  if (s != s) return s;
-  if (mx == -INFINITY) return -INFINITY;
-  return mx + log(s) - lg;
-}
 
 // The subscripts of entry e, checked: false (and a flag) where the entry may not be read.
 __device__ __forceinline__ bool ho_entry(const PpcLayer& p, const HoIn& in, size_t e, int& i, int& j, int& m, int& x, int& xt, int* __restrict__ bad) {
@@ -332,10 +289,7 @@ extern "C" int vmr_heldout_loglik(vmr_handle h, uint64_t n, const int32_t* el, c
   std::vector<double> par_h(n_par);
   memcpy(par_h.data(), theta, (size_t)L * M * 8);
   memcpy(par_h.data() + (size_t)L * M, lambda, (size_t)L * K * 8);
-  for (int x = 0; x < HO_LGT; ++x) {
-    int sign = 0;
-    par_h[(size_t)L * M + (size_t)L * K + x] = lgamma_r((double)x + 1.0, &sign);
-  }
+  ho_lgt_fill(par_h.data() + (size_t)L * M + (size_t)L * K);
 
   const size_t nb_all = (size_t)((n + HO_CHUNK - 1) / HO_CHUNK) + (size_t)L;   // workgroups of all segments at most
   Tmp tm(h);

@@ -35,7 +35,17 @@ class HeldoutArgumentError(EngineError, ValueError):
     decreases in the layer, a negative or non-finite table entry."""
 
 
+class ReportScoresArgumentError(EngineError, ValueError):
+    """An argument `report_scores` / `report_scores_size` refuse (VMR_EINVAL): a selection other than reports, omissions or both,
+    a NaN or -inf threshold, edges that are not finite, that decrease or that are too many, a negative or non-finite table
+    entry, a layer out of range, a table shorter than the flagged rows."""
+
+
 SCORE_OUTPUTS = ("hist", "conf", "sums", "auc", "auc_pairs")
+RS_SELECT = {"reports": _lib.RS_REPORTS, "omissions": _lib.RS_OMISSIONS, "both": _lib.RS_REPORTS | _lib.RS_OMISSIONS}
+# columns of the table of `CaviEngine.report_scores`, in the order of vmr_report_scores' row pointers
+RS_COLUMNS = (("l", np.int32), ("i", np.int32), ("j", np.int32), ("m", np.int32), ("x", np.int32), ("xt", np.int32),
+              ("logp", np.float64), ("mean", np.float64))
 
 # columns of `CaviEngine.edge_table`, in the order of vmr_edge_table's output pointers (device=True: the unsigned 32 / 64-bit columns
 # are torch.int32 / torch.int64 tensors holding the same bits -- every value is below 2^31 / 2^63)
@@ -714,6 +724,105 @@ class CaviEngine:
             raise HeldoutArgumentError(self.lib.vmr_last_error(self._h).decode())
         self._check(rc)
         return {"logp": logp, "mean": mean, "sums": sums, "counts": counts.astype(np.int64)}
+
+    def _rs_args(self, theta, lam, eta, threshold, select, layer):
+        if theta is None or lam is None:
+            raise ReportScoresArgumentError("theta and lam are needed: the tables the reports are scored under")
+        theta, lam = _f64(theta), _f64(lam)
+        if theta.shape != (self.L, self.M) or lam.shape != (self.L, self.K):
+            raise ReportScoresArgumentError(f"theta {theta.shape}, lam {lam.shape}: expected ({self.L}, {self.M}), ({self.L}, {self.K})")
+        if isinstance(select, str):
+            if select not in RS_SELECT:
+                raise ReportScoresArgumentError("select must be \"reports\", \"omissions\" or \"both\"")
+            select = RS_SELECT[select]
+        if layer is not None and not 0 <= int(layer) < self.L:
+            raise ReportScoresArgumentError(f"layer {layer} out of range [0, {self.L})")
+        return theta, lam, float(eta), float(threshold), int(select), self._layer_arg(layer)
+
+    def _check_rs(self, rc):
+        if rc == _lib.VMR_EINVAL:
+            raise ReportScoresArgumentError(self.lib.vmr_last_error(self._h).decode())
+        self._check(rc)
+
+    def report_scores_size(self, theta, lam, eta, threshold, select="both", layer=None):
+        """Rows of `report_scores` for the same arguments (vmr_report_scores_size): the flagged elements."""
+        theta, lam, eta, thr, sel, la = self._rs_args(theta, lam, eta, threshold, select, layer)
+        n = C.c_uint64()
+        self._check_rs(self.lib.vmr_report_scores_size(self._h, la, theta.ctypes.data, lam.ctypes.data, eta, sel, thr, C.byref(n)))
+        return int(n.value)
+
+    def report_scores(self, theta, lam, eta, threshold, select="both", layer=None, edges=None, rows=True, by_reporter=True, device=False,
+                      out=None):
+        """Every element (l, i, j, m) of the support scored under the current rho, on the device (vmr_report_scores): x the
+        engine's own count, xt its mirror X[l,j,i,m] (mutuality), logp and mean what `heldout_loglik` gives the entry under
+        theta [L, M], lam [L, K], eta; the surprise is -logp.  An element is flagged when its class is in select ("reports": x > 0,
+        "omissions": x = 0, "both") and -logp >= threshold (finite, or +inf: only the elements with logp = -inf).  Returns a dict:
+        "counts" int64 [L', 4] (`_lib.RS_COUNT_NAMES`: elements, reports, elements with logp = -inf, flagged), "sums" float64
+        [L', 4] (`_lib.RS_SUM_NAMES`; sums[:, 0] is the in-sample log predictive density), "hist" int64 [L', n_edges + 1, 2] with
+        edges= (finite, non-decreasing, at most `_lib.RS_MAX_EDGES`: hist[l, c, b] counts the elements of ALL the support with
+        exactly c edges <= -logp, b = 0 reports, 1 omissions; else None) and "edges", "by_reporter" int64 [L', M, 2] (the flagged
+        elements of a reporter by class; None with by_reporter=False), and with rows=True the table, one row per flagged element
+        in lexicographic order: "l", "i", "j", "m", "x", "xt" (int32), "logp", "mean" (torch tensors on the GPU with device=True;
+        None with rows=False, and then no table pass runs).  L' = L, or 1 with layer=.  out: a dict of preallocated columns (one
+        length, the capacity) to fill instead: a capacity below the flagged count is refused before anything is written.
+        Bit-identical from run to run."""
+        theta, lam, eta, thr, sel, la = self._rs_args(theta, lam, eta, threshold, select, layer)
+        Lq = self.L if layer is None else 1
+        ed = None
+        if edges is not None:
+            try:
+                ed = np.ascontiguousarray(np.atleast_1d(edges), dtype=np.float64)
+            except (TypeError, ValueError) as e:
+                raise ReportScoresArgumentError(f"edges: {e}") from None
+            if ed.ndim != 1:
+                raise ReportScoresArgumentError("edges: a 1-D sequence expected")
+        n_edges = 0 if ed is None else int(ed.shape[0])
+        hist = None if ed is None else np.zeros((Lq, n_edges + 1, 2), np.uint64)
+        sums = np.zeros((Lq, _lib.RS_NSUM), np.float64)
+        counts = np.zeros((Lq, _lib.RS_NCOUNT), np.uint64)
+        rep = np.zeros((Lq, self.M, 2), np.uint64) if by_reporter else None
+        cols, n = {}, 0
+        if out is not None:
+            cap = {int(a.shape[0]) for a in out.values()}
+            if len(cap) != 1:
+                raise ValueError("out: arrays of one length expected")
+            n, cols = cap.pop(), out
+        elif rows:
+            n = self.report_scores_size(theta, lam, eta, thr, sel, layer)
+            if device:
+                import torch
+                dev = torch.device("cuda", self.device)
+                cols = {c: torch.empty(n, dtype=getattr(torch, np.dtype(t).name), device=dev) for c, t in RS_COLUMNS}
+            else:
+                cols = {c: np.empty(n, t) for c, t in RS_COLUMNS}
+        ptrs = []
+        for c, t in RS_COLUMNS:
+            a = cols.get(c)
+            if a is None:
+                ptrs.append(None)
+            elif _is_torch(a):
+                assert a.is_cuda and a.is_contiguous() and a.element_size() == np.dtype(t).itemsize
+                ptrs.append(a.data_ptr())
+            else:
+                assert a.dtype == np.dtype(t) and a.flags.c_contiguous
+                ptrs.append(a.ctypes.data)
+        on_dev = any(_is_torch(a) for a in cols.values())
+        if on_dev:
+            import torch
+            torch.cuda.synchronize(torch.device("cuda", self.device))
+        rc = self.lib.vmr_report_scores(self._h, la, theta.ctypes.data, lam.ctypes.data, eta, sel, thr, n_edges,
+                                        ed.ctypes.data if n_edges else None, None if hist is None else hist.ctypes.data,
+                                        sums.ctypes.data, counts.ctypes.data, None if rep is None else rep.ctypes.data,
+                                        n if (rows or out is not None) else 0, *ptrs, int(on_dev))
+        self._check_rs(rc)
+        res = {"counts": counts.astype(np.int64), "sums": sums, "hist": None if hist is None else hist.astype(np.int64), "edges": ed,
+               "by_reporter": None if rep is None else rep.astype(np.int64),
+               "layers": np.arange(self.L) if layer is None else np.array([int(layer)]), "threshold": thr, "select": sel}
+        n_rows = int(res["counts"][:, 3].sum())
+        for c, _ in RS_COLUMNS:
+            a = cols.get(c)
+            res[c] = None if a is None else (a if out is not None else a[:n_rows])
+        return res
 
     def snapshot(self):
         """Keep the current posteriors on the device (`_update_optimal_parameters`, reference model.py:925-942)."""

@@ -872,6 +872,47 @@ class VimureModel(TransformerMixin, BaseEstimator):
             if tmp:
                 eng.close()
 
+    def surprising_reports(self, top=100, threshold=None, select="both", estimate="mean", layer=None, max_rows=10_000_000, X=None,
+                           R=None):
+        """Which individual reports does the fitted model disbelieve, and which omissions?  Every element (l, i, j, m) of the
+        support of R is scored on the GPU (vmr_report_scores) under the best realisation: its surprise is -log p of the observed
+        count (or zero) under the posterior mixture of Poissons, the likelihood of `heldout_loglik`; neither rho nor the support
+        crosses PCIe.  Exactly one of `top` and `threshold` is given (top=None with threshold=): threshold -- one call, every
+        selected element with surprise >= threshold, in (layer, source, target, reporter) order; top -- a first pass over a fixed
+        grid of surprise levels (4096 edges, 1/64 nat apart, from 0) finds the largest level with at least `top` selected elements
+        at or above it (0 when there is none), a second one fetches those rows (more than `max_rows` of them: ValueError naming
+        the count), which are sorted by (-surprise, layer, source, target, reporter) and cut to `top`.  select "reports" (x > 0),
+        "omissions" (x = 0) or "both"; estimate as `heldout_loglik` ("mean", "geometric"); layer: that layer only.  Returns a
+        `residuals.ReportScores`: `frame()` (layer, source, target, reporter, x, x_mirror, logp, surprise, expected, residual),
+        `reporters()`, `lppd` -- the exact in-sample log predictive density per layer, the training-side figure beside
+        `crossval.CVResult.lpd` -- and with `top` the histogram of the surprise over the grid.  Engine as in
+        `calculate_mean_poisson`."""
+        from .crossval import plug_in_tables
+        from .residuals import ReportScores, grid_edges, select_code, threshold_for_top, top_rows
+        if (top is None) == (threshold is None):
+            raise ValueError("exactly one of top and threshold is given (top=None with threshold=)")
+        sel = select_code(select)
+        if top is not None and int(top) < 1:
+            raise ValueError("top must be at least 1")
+        if not hasattr(self, "gamma_shp_f"):
+            raise ValueError("the model has not been fitted: call fit(..., keep_engine=True) first, or fit it and pass X=")
+        if layer is not None and not 0 <= int(layer) < self.L:
+            raise ValueError(f"layer {layer} out of range [0, {self.L})")
+        eng, tmp = self._ppc_engine(X, R)
+        try:
+            theta, lam, eta = plug_in_tables(self, eng, estimate)
+            if threshold is not None:
+                return ReportScores(eng.report_scores(theta, lam, eta, float(threshold), select=sel, layer=layer), estimate=estimate)
+            agg = eng.report_scores(theta, lam, eta, np.inf, select=sel, layer=layer, edges=grid_edges(), rows=False, by_reporter=False)
+            thr, _ = threshold_for_top(agg["hist"], agg["edges"], top, sel, max_rows=max_rows)
+            res = eng.report_scores(theta, lam, eta, thr, select=sel, layer=layer)
+        finally:
+            if tmp:
+                eng.close()
+        res.update(top_rows(res, top))
+        res["hist"], res["edges"] = agg["hist"], agg["edges"]
+        return ReportScores(res, estimate=estimate, top=int(top))
+
     def predict(self, X=None, method="rho_max", threshold=None):
         """Alias of `get_inferred_model` (the reference's experiment wrapper calls it predict)."""
         return self.get_inferred_model(method=method, threshold=threshold)
