@@ -509,6 +509,75 @@ int vmr_report_scores(vmr_handle h, int layer, const double* theta /* host [L][M
                       uint64_t n, int32_t* sl, int32_t* si, int32_t* sj, int32_t* sm,
                       int32_t* x, int32_t* xt, double* logp, double* mean, int out_on_device);
 
+/* Reporter influence: whose word does an inferred tie rest on?  For every element (l,i,j,m) of the support, the row of rho the
+ * tie would hold had reporter m said nothing about it -- the leave-one-reporter-out posterior, computed where rho lives.
+ * vmr_reporter_table says whether a reporter agrees with the posterior and vmr_report_scores which reports the posterior
+ * disbelieves; this says which reports DECIDE it.  The CAVI update of a tie's row is additive over the reporters of its mask
+ * (`_update_rho`, model.py:763-818):  log rho_k = logpr_k + sum_m c_mk + const,  so dividing reporter m's factor exp(c_mk) out
+ * of the row and normalising again gives exactly the row the update would have produced with R[l,i,j,m] = 0 -- closed form, no
+ * refit.  The parameters are held fixed and ONE factor leaves ONE tie: the numbers are an exact refit of that row only when rho
+ * is the update's fixed point for the tables given.
+ * The caller's tables, host arrays as vmr_report_scores takes theta and lambda: e_theta [L][M] = E[theta] (shape / rate),
+ * elog_theta [L][M] = E[log theta] (psi(shape) - log(rate)), e_lambda [L][K], elog_lambda [L][K] likewise, and g_nu =
+ * exp(E[log nu]) (ignored, 0, on a handle without mutuality).  The entry forms g_theta = exp(elog_theta), g_lambda =
+ * exp(elog_lambda) on the host.
+ * The support S is vmr_mean_poisson's, walked in its lexicographic (l,i,j,m) order.  Per element, from the handle's own data and
+ * the CURRENT rho (after vmr_restore: the snapshot's): x = X[l,i,j,m]; xt = X[l,j,i,m] with mutuality, else 0; rho the tie's row.
+ * Every product, quotient and sum below is rounded on its own (no fused multiply-add), in the order written:
+ *   z1_k  = g_theta[l][m] g_lambda[l][k];   den_k = z1_k + (g_nu xt), a zero den_k replaced by 1;   w1_k = z1_k / den_k
+ *   c_k   = (elog_theta[l][m] + elog_lambda[l][k]) (x w1_k) - e_theta[l][m] e_lambda[l][k]      reporter m's factor, d_k = -c_k
+ *   over the categories with rho_k > 0 only (the others keep q_k = 0):  mx = max d_k;  u_k = rho_k exp(d_k - mx);
+ *   S = sum u_k, k ascending;  q_k = u_k / S.      A row of all zeros (one the engine keeps) gives q = 0.
+ *   prob     = sum_{k>=1} rho_k, k ascending (`prob` of vmr_edge_table; K = 2: rho_1 bit for bit)
+ *   prob_loo = sum_{k>=1} q_k, k ascending;     tv = (sum_k |q_k - rho_k|) / 2, k ascending: the total variation between the rows
+ *   y  the byte vmr_readout(h, method, threshold, ..) writes for the tie, y' the same rule applied to q: VMR_READ_RHO_MAX the
+ *      first maximum, VMR_READ_THRESHOLD q_1 >= threshold (VMR_READ_RHO_MEAN: VMR_EINVAL)
+ *   LOST: y > 0 and y' = 0 (the inferred tie rests on this report);  GAINED: y = 0 and y' > 0 (this report alone holds it down).
+ * An element is FLAGGED iff it is lost and select & VMR_INF_LOST, or gained and select & VMR_INF_GAINED, or tv >= min_tv
+ * (select in 0..3; min_tv in [0, +inf], +inf: flips only).
+ * Outputs, host arrays unless noted, any of them NULL (not all); L' = L for layer < 0, else 1:
+ *   counts [L'][M][VMR_INF_NCOUNT], exact:  0 n_scope = #S_m (column 0 of vmr_reporter_table)   1 lost   2 gained   3 flagged
+ *   sums   [L'][M][VMR_INF_NSUM]:  0 sum_{S_m} tv    1 sum_{S_m} (prob_loo - prob)
+ *          accumulated in FIXED POINT, as vmr_reporter_table's exp_ties: with b = ceil(log2 N^2) every term is rounded to a
+ *          multiple of q = 2^-(61 - b) and added by signed 64-bit integer atomics, so a reporter's sum is within n_scope q / 2 of
+ *          the exact sum of its terms.  A term beyond 2 in size (a row of rho that sums to more than 2) does not fit: VMR_EINVAL.
+ *   hist   [L'][n_edges + 1][2]: over ALL of S, hist[l][c][b] = #{e : c = #{tau : edges[tau] <= tv}}, b = 0 for x > 0, 1 for
+ *          x = 0; edges finite and non-decreasing, n_edges in [0, VMR_INF_MAX_EDGES].  Without hist the edges are not read.
+ *   the table: one row per flagged element in lexicographic (l,i,j,m) order -- sl, si, sj, sm, x, xt (int32), prob, prob_loo, tv
+ *          (double), each column optional; n is the capacity: below the row count VMR_EINVAL before anything is written; n = 0 and
+ *          every row pointer NULL: no table pass; device pointers when out_on_device != 0.
+ * vmr_reporter_influence_size gives the row count, the sum of counts[.][.][3], for the same arguments.
+ * The passes are vmr_report_scores': a count pass (a group of lanes per tie, the tie's support reporters in ascending m; the
+ * integer bins in LDS first -- reporters up to 2048, the histogram where it fits beside them in 128 KB, global integer atomics
+ * beyond), an exclusive 64-bit sum of the ties' flagged counts, and a fill pass that places a row by its ballot rank.  K = 2 and
+ * K <= 8 keep the row in registers, larger K streams it; the variants perform the same operations.  Every accumulator is an
+ * integer: no floating-point atomics, every output bit-identical from run to run.
+ * Any K up to 256, both data formats, every mask layout, handles of vmr_create_coo, mutuality on or off; fewer than 2^31 ties
+ * per layer.  VMR_EINVAL with a message, before any launch: NULL handle (no message), a NULL table, e_theta or e_lambda negative
+ * or not finite, elog_theta or elog_lambda not finite (or with an exp that overflows), g_nu negative or not finite, a bad method,
+ * select outside 0..3, min_tv NaN or negative, layer >= L, every output NULL, n_edges out of range, hist with n_edges > 0 and
+ * edges NULL, a non-finite or decreasing edge, a temporary that does not fit in the free device memory (8 B per tie of a layer,
+ * and of every layer asked for when rows are; 48 B per reporter and layer; host rows: 48 B per row of a layer).  VMR_ESTATE before
+ * vmr_set_state.  VMR_ENAN, after the count pass: a prob, prob_loo or tv is NaN (no row is then written).  Synchronises;
+ * temporaries are freed on every exit path. */
+enum { VMR_INF_LOST = 1, VMR_INF_GAINED = 2 };
+#define VMR_INF_NCOUNT 4
+#define VMR_INF_NSUM 2
+#define VMR_INF_MAX_EDGES 4096
+int vmr_reporter_influence_size(vmr_handle h, int layer, const double* e_theta, const double* elog_theta, const double* e_lambda,
+                                const double* elog_lambda, double g_nu, int method, double threshold, int select, double min_tv,
+                                uint64_t* n);
+int vmr_reporter_influence(vmr_handle h, int layer,
+                           const double* e_theta /* host [L][M] */, const double* elog_theta /* host [L][M] */,
+                           const double* e_lambda /* host [L][K] */, const double* elog_lambda /* host [L][K] */, double g_nu,
+                           int method, double threshold, int select, double min_tv,
+                           int n_edges, const double* edges,
+                           uint64_t* hist   /* [L'][n_edges + 1][2] or NULL */,
+                           uint64_t* counts /* [L'][M][VMR_INF_NCOUNT] or NULL */,
+                           double*   sums   /* [L'][M][VMR_INF_NSUM] or NULL */,
+                           uint64_t n, int32_t* sl, int32_t* si, int32_t* sj, int32_t* sm,
+                           int32_t* x, int32_t* xt, double* prob, double* prob_loo, double* tv, int out_on_device);
+
 /* exp(E[log .]) of theta [L,M], lambda [L,K], nu from the current shape/rate parameters
  * (model.py:676-684), plus g_nu_cache = the G_exp_nu the last cache refresh held, i.e. the
  * value computed BEFORE the last nu update -- what `model.G_exp_nu` reads after `fit` and what

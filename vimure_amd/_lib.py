@@ -26,6 +26,10 @@ RS_REPORTS, RS_OMISSIONS = 1, 2
 RS_NSUM, RS_NCOUNT, RS_MAX_EDGES = 4, 4, 4096
 RS_SUM_NAMES = ["logp", "sq_err", "total", "exp_total"]
 RS_COUNT_NAMES = ["n", "n_reports", "n_inf", "n_flagged"]
+INF_LOST, INF_GAINED = 1, 2
+INF_NCOUNT, INF_NSUM, INF_MAX_EDGES = 4, 2, 4096
+INF_COUNT_NAMES = ["n_scope", "lost", "gained", "flagged"]
+INF_SUM_NAMES = ["tv", "shift"]
 PPC_STAT_NAMES = ["n_pos", "total", "sumsq", "mutual", "ties_reported", "ties_agreed"]
 KERNEL_NAMES = ["gamma_mask", "gamma_counts", "phi", "rho", "elbo", "finalize", "rho_elbo", "rho_nostore"]
 
@@ -81,6 +85,10 @@ SIGNATURES = {
     "vmr_report_scores_size": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_double, C.POINTER(C.c_uint64)]),
     "vmr_report_scores": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.c_double, C.c_int, C.c_void_p]
                           + [C.c_void_p] * 4 + [C.c_uint64] + [C.c_void_p] * 8 + [C.c_int]),
+    "vmr_reporter_influence_size": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_double, C.c_int, C.c_double, C.c_int, C.c_double,
+                                              C.POINTER(C.c_uint64)]),
+    "vmr_reporter_influence": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_double, C.c_int, C.c_double, C.c_int, C.c_double,
+                                         C.c_int, C.c_void_p] + [C.c_void_p] * 3 + [C.c_uint64] + [C.c_void_p] * 9 + [C.c_int]),
     "vmr_snapshot": (C.c_int, [C.c_void_p]),
     "vmr_restore": (C.c_int, [C.c_void_p]),
     "vmr_profile": (C.c_int, [C.c_void_p, C.c_int]),

@@ -38,7 +38,8 @@ def units(dev=False):
          ("score_truth", os.path.join(CSRC, "score_truth.hip"), extra),  # the posterior scored against a ground truth
          ("reporter_table", os.path.join(CSRC, "reporter_table.hip"), extra),  # each reporter's reports against the posterior
          ("heldout", os.path.join(CSRC, "heldout.hip"), extra),        # held-out reports scored under the posterior
-         ("report_scores", os.path.join(CSRC, "report_scores.hip"), extra)]  # every report of the support scored under the posterior
+         ("report_scores", os.path.join(CSRC, "report_scores.hip"), extra),  # every report of the support scored under the posterior
+         ("influence", os.path.join(CSRC, "influence.hip"), extra)]    # the leave-one-reporter-out posterior of every element
     dev_ks = tuple(int(k) for k in os.environ.get("VMR_DEV_KS", "2").split(","))   # (VMR_DEV_KS=2,3: also the K = 3 sweep kernels)
     for k in (dev_ks if dev else KS):
         u.append((f"sweep_sl_k{k}", os.path.join(CSRC, "sweep_sl.hip"), extra + [f"-DVMR_K={k}"]))

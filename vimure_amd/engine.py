@@ -41,7 +41,17 @@ class ReportScoresArgumentError(EngineError, ValueError):
     entry, a layer out of range, a table shorter than the flagged rows."""
 
 
+class ReporterInfluenceArgumentError(EngineError, ValueError):
+    """An argument `reporter_influence` / `reporter_influence_size` refuse (VMR_EINVAL): a method that gives no categories, a
+    selection other than lost, gained, both or none, a NaN or negative min_tv, edges that are not finite, that decrease or that
+    are too many, a table entry out of range, a layer out of range, a table shorter than the flagged rows."""
+
+
 SCORE_OUTPUTS = ("hist", "conf", "sums", "auc", "auc_pairs")
+INF_SELECT = {"none": 0, "lost": _lib.INF_LOST, "gained": _lib.INF_GAINED, "both": _lib.INF_LOST | _lib.INF_GAINED}
+# columns of the table of `CaviEngine.reporter_influence`, in the order of vmr_reporter_influence's row pointers
+INF_COLUMNS = (("l", np.int32), ("i", np.int32), ("j", np.int32), ("m", np.int32), ("x", np.int32), ("xt", np.int32),
+               ("prob", np.float64), ("prob_loo", np.float64), ("tv", np.float64))
 RS_SELECT = {"reports": _lib.RS_REPORTS, "omissions": _lib.RS_OMISSIONS, "both": _lib.RS_REPORTS | _lib.RS_OMISSIONS}
 # columns of the table of `CaviEngine.report_scores`, in the order of vmr_report_scores' row pointers
 RS_COLUMNS = (("l", np.int32), ("i", np.int32), ("j", np.int32), ("m", np.int32), ("x", np.int32), ("xt", np.int32),
@@ -822,6 +832,131 @@ class CaviEngine:
         for c, _ in RS_COLUMNS:
             a = cols.get(c)
             res[c] = None if a is None else (a if out is not None else a[:n_rows])
+        return res
+
+    def _inf_args(self, e_theta, elog_theta, e_lambda, elog_lambda, g_nu, method, threshold, select, min_tv, layer):
+        if any(a is None for a in (e_theta, elog_theta, e_lambda, elog_lambda)):
+            raise ReporterInfluenceArgumentError("e_theta, elog_theta, e_lambda and elog_lambda are needed: the tables of the update")
+        tabs = [_f64(a) for a in (e_theta, elog_theta, e_lambda, elog_lambda)]
+        want = [(self.L, self.M), (self.L, self.M), (self.L, self.K), (self.L, self.K)]
+        if any(a.shape != w for a, w in zip(tabs, want)):
+            raise ReporterInfluenceArgumentError(f"tables of shapes {[a.shape for a in tabs]}: expected {want}")
+        codes = {"rho_max": _lib.READ_RHO_MAX, "rho_mean": _lib.READ_RHO_MEAN, "threshold": _lib.READ_THRESHOLD}
+        if isinstance(method, str):
+            if method not in codes:
+                raise ReporterInfluenceArgumentError("'method' should be one of \"rho_max\", \"threshold\".")
+            method = codes[method]
+        if isinstance(select, str):
+            if select not in INF_SELECT:
+                raise ReporterInfluenceArgumentError("select must be \"lost\", \"gained\", \"both\" or \"none\"")
+            select = INF_SELECT[select]
+        if layer is not None and not 0 <= int(layer) < self.L:
+            raise ReporterInfluenceArgumentError(f"layer {layer} out of range [0, {self.L})")
+        return tabs, float(g_nu), int(method), float(threshold), int(select), float(min_tv), self._layer_arg(layer)
+
+    def _check_inf(self, rc):
+        if rc == _lib.VMR_EINVAL:
+            raise ReporterInfluenceArgumentError(self.lib.vmr_last_error(self._h).decode())
+        self._check(rc)
+
+    def reporter_influence_size(self, e_theta, elog_theta, e_lambda, elog_lambda, g_nu, method="rho_max", threshold=0.0, select="both",
+                                min_tv=np.inf, layer=None):
+        """Rows of `reporter_influence` for the same arguments (vmr_reporter_influence_size): the flagged elements."""
+        tabs, g_nu, code, thr, sel, mtv, la = self._inf_args(e_theta, elog_theta, e_lambda, elog_lambda, g_nu, method, threshold, select,
+                                                            min_tv, layer)
+        n = C.c_uint64()
+        self._check_inf(self.lib.vmr_reporter_influence_size(self._h, la, *[a.ctypes.data for a in tabs], g_nu, code, thr, sel, mtv,
+                                                             C.byref(n)))
+        return int(n.value)
+
+    def reporter_influence(self, e_theta, elog_theta, e_lambda, elog_lambda, g_nu, method="rho_max", threshold=0.0, select="both",
+                           min_tv=np.inf, layer=None, edges=None, rows=True, device=False, out=None, flips=True):
+        """The leave-one-reporter-out posterior of every element (l, i, j, m) of the support, on the device
+        (vmr_reporter_influence): the tie's row of the current rho with reporter m's factor of the CAVI update divided out, under
+        the tables e_theta, elog_theta [L, M] (E[theta], E[log theta]), e_lambda, elog_lambda [L, K] and g_nu = exp(E[log nu]).
+        The parameters are held fixed and one factor leaves one tie: an exact refit of that row only when rho is the update's
+        fixed point for these tables.  prob = sum_{k>=1} rho_k, prob_loo the same of the leave-one-out row, tv the total variation
+        between the two rows; an element is LOST when the readout (method "rho_max", or "threshold": rho_1 >= threshold) infers
+        the tie and the leave-one-out row does not, GAINED the other way round; it is flagged when it is lost and select holds
+        "lost", gained and select holds "gained" ("both", "none"), or tv >= min_tv (+inf: flips only).  Returns a dict: "counts"
+        int64 [L', M, 4] (`_lib.INF_COUNT_NAMES`: n_scope, lost, gained, flagged), "sums" float64 [L', M, 2]
+        (`_lib.INF_SUM_NAMES`: sum tv, sum prob_loo - prob; fixed point, `influence.sum_quantum`), "hist" int64 [L', n_edges + 1, 2]
+        with edges= (exactly c edges <= tv; class 0: x > 0, 1: x = 0; else None) and "edges", and with rows=True the table, one
+        row per flagged element in lexicographic order: "l", "i", "j", "m", "x", "xt" (int32), "prob", "prob_loo", "tv" (torch
+        tensors on the GPU with device=True; None with rows=False, and then no table pass runs) and, with flips=True and host
+        rows, the boolean marks "lost" and "gained" of every row (two more calls that fetch the flips' subscripts alone, made only
+        where a flip exists).  L' = L, or 1 with layer=.  out: a dict of preallocated columns (one length, the capacity) to fill
+        instead: a capacity below the flagged count is refused before anything is written.  Bit-identical from run to run."""
+        tabs, g_nu, code, thr, sel, mtv, la = self._inf_args(e_theta, elog_theta, e_lambda, elog_lambda, g_nu, method, threshold, select,
+                                                            min_tv, layer)
+        tp = [a.ctypes.data for a in tabs]
+        Lq = self.L if layer is None else 1
+        ed = None
+        if edges is not None:
+            try:
+                ed = np.ascontiguousarray(np.atleast_1d(edges), dtype=np.float64)
+            except (TypeError, ValueError) as e:
+                raise ReporterInfluenceArgumentError(f"edges: {e}") from None
+            if ed.ndim != 1:
+                raise ReporterInfluenceArgumentError("edges: a 1-D sequence expected")
+        n_edges = 0 if ed is None else int(ed.shape[0])
+        hist = None if ed is None else np.zeros((Lq, n_edges + 1, 2), np.uint64)
+        counts = np.zeros((Lq, self.M, _lib.INF_NCOUNT), np.uint64)
+        sums = np.zeros((Lq, self.M, _lib.INF_NSUM), np.float64)
+        cols, n = {}, 0
+        if out is not None:
+            cap = {int(a.shape[0]) for a in out.values()}
+            if len(cap) != 1:
+                raise ValueError("out: arrays of one length expected")
+            n, cols = cap.pop(), out
+        elif rows:
+            n = self.reporter_influence_size(*tabs, g_nu, code, thr, sel, mtv, layer)
+            if device:
+                import torch
+                dev = torch.device("cuda", self.device)
+                cols = {c: torch.empty(n, dtype=getattr(torch, np.dtype(t).name), device=dev) for c, t in INF_COLUMNS}
+            else:
+                cols = {c: np.empty(n, t) for c, t in INF_COLUMNS}
+        ptrs = []
+        for c, t in INF_COLUMNS:
+            a = cols.get(c)
+            if a is None:
+                ptrs.append(None)
+            elif _is_torch(a):
+                assert a.is_cuda and a.is_contiguous() and a.element_size() == np.dtype(t).itemsize
+                ptrs.append(a.data_ptr())
+            else:
+                assert a.dtype == np.dtype(t) and a.flags.c_contiguous
+                ptrs.append(a.ctypes.data)
+        on_dev = any(_is_torch(a) for a in cols.values())
+        if on_dev:
+            import torch
+            torch.cuda.synchronize(torch.device("cuda", self.device))
+        rc = self.lib.vmr_reporter_influence(self._h, la, *tp, g_nu, code, thr, sel, mtv, n_edges, ed.ctypes.data if n_edges else None,
+                                             None if hist is None else hist.ctypes.data, counts.ctypes.data, sums.ctypes.data,
+                                             n if (rows or out is not None) else 0, *ptrs, int(on_dev))
+        self._check_inf(rc)
+        res = {"counts": counts.astype(np.int64), "sums": sums, "hist": None if hist is None else hist.astype(np.int64), "edges": ed,
+               "layers": np.arange(self.L) if layer is None else np.array([int(layer)]), "method": code, "threshold": thr,
+               "select": sel, "min_tv": mtv}
+        n_rows = int(res["counts"][:, :, 3].sum())
+        for c, _ in INF_COLUMNS:
+            a = cols.get(c)
+            res[c] = None if a is None else (a if out is not None else a[:n_rows])
+        if flips and rows and out is None and not on_dev:
+            # which rows are flips: the subscripts of the lost (gained) elements alone, looked up among the rows
+            shape = (self.L, self.N, self.N, self.M)
+            key = np.ravel_multi_index(tuple(res[c].astype(np.int64) for c in "lijm"), shape) if n_rows else np.zeros(0, np.int64)
+            for name, bit, col in (("lost", _lib.INF_LOST, 1), ("gained", _lib.INF_GAINED, 2)):
+                mark = np.zeros(n_rows, bool)
+                nf = int(res["counts"][:, :, col].sum())
+                if nf and n_rows:
+                    sub = {c: np.empty(nf, np.int32) for c in "lijm"}
+                    p4 = [sub[c].ctypes.data for c in "lijm"] + [None] * 5
+                    self._check_inf(self.lib.vmr_reporter_influence(self._h, la, *tp, g_nu, code, thr, bit, np.inf, 0, None, None, None,
+                                                                    None, nf, *p4, 0))
+                    mark = np.isin(key, np.ravel_multi_index(tuple(sub[c].astype(np.int64) for c in "lijm"), shape))
+                res[name] = mark
         return res
 
     def snapshot(self):

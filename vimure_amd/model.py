@@ -913,6 +913,63 @@ class VimureModel(TransformerMixin, BaseEstimator):
         res["hist"], res["edges"] = agg["hist"], agg["edges"]
         return ReportScores(res, estimate=estimate, top=int(top))
 
+    def influence_tables(self):
+        """(e_theta [L,M], elog_theta [L,M], e_lambda [L,K], elog_lambda [L,K], g_nu) of the best realisation, the tables of the
+        CAVI update of rho: shp / rte and psi(shp) - log(rte) of gamma_*_f and phi_*_f, exp(psi(nu_shp_f) - log(nu_rte_f)); g_nu
+        is 0 without mutuality."""
+        gs, gr = np.asarray(self.gamma_shp_f, dtype=np.float64), np.asarray(self.gamma_rte_f, dtype=np.float64)
+        ps, pr = np.asarray(self.phi_shp_f, dtype=np.float64), np.asarray(self.phi_rte_f, dtype=np.float64)
+        g_nu = float(np.exp(sp.psi(float(self.nu_shp_f)) - np.log(float(self.nu_rte_f)))) if self.mutuality else 0.0
+        return gs / gr, sp.psi(gs) - np.log(gr), ps / pr, sp.psi(ps) - np.log(pr), g_nu
+
+    def reporter_influence(self, method="rho_max", threshold=None, select="both", min_shift=None, top=None, layer=None,
+                           max_rows=10_000_000, X=None, R=None):
+        """Whose word does an inferred tie rest on?  For every element (l, i, j, m) of the support of R the tie's row of rho is
+        recomputed on the GPU without reporter m's report (vmr_reporter_influence): the CAVI update of a row is additive over the
+        reporters of its mask, so dividing one reporter's factor out of the fitted row gives the row the update would have
+        produced with R[l,i,j,m] = 0; neither rho nor the support crosses PCIe.
+        What the numbers are: the parameters (theta, lambda, nu of the best realisation) are held fixed and one reporter's factor
+        is removed from one tie.  They are an exact refit of that row only when rho is the update's fixed point for those
+        parameters -- a converged fit is close to one -- and never a refit of the whole model.
+        method and threshold as `get_inferred_edgelist` takes them (same warning and fall-back, same errors).  An element is LOST
+        when the tie is inferred and its leave-one-out row is not, GAINED the other way round; its shift is the total variation
+        tv between the two rows.  select "lost", "gained", "both" or "none": which flips are listed; min_shift: also every
+        element with tv >= min_shift; top=n instead: the n elements with the largest tv -- a first pass over a fixed grid of 4096
+        edges over [0, 1] finds the largest level with at least n elements at or above it, a second one fetches those rows (more
+        than `max_rows`: ValueError naming the count), sorted by (-tv, layer, source, target, reporter) and cut.  layer: that
+        layer only.  Returns an `influence.ReporterInfluence`: `frame()` one row per (layer, reporter) -- n_scope, lost, gained,
+        mean_tv, mean_shift -- `rows()` the listed elements, `fragile_ties()` those whose removal loses the tie.  Engine as in
+        `calculate_mean_poisson`."""
+        from .influence import ReporterInfluence, grid_edges, min_tv_for_top, select_code, top_rows
+        if top is not None and min_shift is not None:
+            raise ValueError("at most one of top and min_shift is given")
+        sel = select_code(select)
+        if top is not None and int(top) < 1:
+            raise ValueError("top must be at least 1")
+        if min_shift is not None and not float(min_shift) >= 0.0:
+            raise ValueError("min_shift must lie in [0, +inf]")
+        if not hasattr(self, "gamma_shp_f"):
+            raise ValueError("the model has not been fitted: call fit(..., keep_engine=True) first, or fit it and pass X=")
+        code, thr = self._edge_method(method, threshold)
+        if layer is not None and not 0 <= int(layer) < self.L:
+            raise ValueError(f"layer {layer} out of range [0, {self.L})")
+        tabs = self.influence_tables()
+        eng, tmp = self._ppc_engine(X, R)
+        try:
+            if top is None:
+                min_tv = np.inf if min_shift is None else float(min_shift)
+                return ReporterInfluence(eng.reporter_influence(*tabs, method=code, threshold=thr, select=sel, min_tv=min_tv, layer=layer))
+            agg = eng.reporter_influence(*tabs, method=code, threshold=thr, select=0, min_tv=np.inf, layer=layer, edges=grid_edges(),
+                                         rows=False)
+            min_tv, _ = min_tv_for_top(agg["hist"], agg["edges"], top, max_rows=max_rows)
+            res = eng.reporter_influence(*tabs, method=code, threshold=thr, select=0, min_tv=min_tv, layer=layer)
+        finally:
+            if tmp:
+                eng.close()
+        res.update(top_rows(res, top))
+        res["hist"], res["edges"] = agg["hist"], agg["edges"]
+        return ReporterInfluence(res, top=int(top))
+
     def predict(self, X=None, method="rho_max", threshold=None):
         """Alias of `get_inferred_model` (the reference's experiment wrapper calls it predict)."""
         return self.get_inferred_model(method=method, threshold=threshold)
