@@ -270,6 +270,38 @@ int vmr_sample_stats(vmr_handle h, uint64_t seed, int n_samples, int n_trials, c
  * (no atomics): bit-identical from run to run.  Temporary: 8 L N^2 bytes (VMR_EINVAL when that does not fit).  Synchronises. */
 int vmr_expected_stats(vmr_handle h, double* out);
 
+/* Triad statistics of n_samples posterior samples of Y, computed where rho lives -- what a user otherwise gets from `A @ A` in
+ * NumPy on every `sample_inferred_model` draw.  Sample s is exactly what vmr_sample(h, seed + s, n_trials, ..) writes (mod 2^64).
+ * Per sample and layer: A_ij = (Y_ij > 0) with the DIAGONAL CLEARED (a self-loop belongs to no triad), U = A | A^T, and i, j, k
+ * pairwise distinct.  counts: host uint64 [n_samples][L][VMR_TRIAD_NSTAT]:
+ *   0 transitive   #{(i,j,k) : i->j, j->k, i->k}                      ((A @ A.T) * A).sum()
+ *   1 cyclic       #{(i,j,k) : i->j, j->k, k->i}, ordered: a 3-cycle counts 3 times    ((A @ A) * A.T).sum()
+ *   2 two_paths    #{(i,j,k) : i->j, j->k}                            (A @ A).sum() - np.trace(A @ A)
+ *   3 triangles_u  triangles of U, each once                          np.trace(U @ U @ U) // 6
+ *   4 wedges_u     sum_i d_i (d_i - 1) / 2, d_i the degree of i in U
+ *   5 edges_u      #{i < j : U_ij}
+ * node_tri[s][l][i]: triangles of U through node i; node_deg[s][l][i] = d_i; host int32 [n_samples][L][N], either may be NULL.
+ * The samples are packed into bit rows (64-bit words, out- and in-neighbours) and counted by AND + popcount.  All sums are
+ * integer sums: bit-identical from run to run.  Reads the CURRENT rho once per chunk of samples; any K, any n_trials >= 1, both
+ * data formats.  A chunk (L N^2 + 16 L N ceil(N/64) bytes per sample plus the outputs; half of the free device memory at most,
+ * 256 samples at most, VMR_NETSTATS_CHUNK at most) is freed before return; a single sample that does not fit is refused with
+ * VMR_EINVAL.  n_samples < 1, n_trials < 1 or counts NULL: VMR_EINVAL; before vmr_set_state: VMR_ESTATE.  Synchronises. */
+#define VMR_TRIAD_NSTAT 6
+int vmr_sample_triads(vmr_handle h, uint64_t seed, int n_samples, int n_trials, uint64_t* counts, int32_t* node_tri,
+                      int32_t* node_deg);
+
+/* The same six quantities in expectation under q(Y) = prod rho, no sampling -- instead of NumPy matrix products on the rho of
+ * `get_state`.  p_ij = sum_{k>=1} rho_ijk (k ascending, the number of vmr_expected_stats), p_ii := 0, and for i != j
+ * u_ij = 1 - (1 - p_ij)(1 - p_ji).  Distinct ties, and distinct unordered pairs, are independent under the mean field, so these
+ * products are exact expectations of the counts:
+ *   out[l] = (sum_ij p_ij (P P^T)_ij, sum_ij (P P)_ij p_ji, sum_j cin_j cout_j - sum_ij p_ij p_ji, tr(U^3) / 6,
+ *             sum_i (s_i^2 - sum_j u_ij^2) / 2 with s_i = sum_j u_ij, sum_{i<j} u_ij)             host double [L][VMR_TRIAD_NSTAT]
+ * They are expectations of COUNTS: a ratio of two of them (a transitivity) is not the expectation of the ratio -- take that from
+ * the samples.  Doubles summed by a fixed two-stage tree on a grid that depends on N only (no atomics): bit-identical from run
+ * to run.  Temporaries: P and U, 16 L N^2 bytes (VMR_EINVAL when they do not fit).  out NULL: VMR_EINVAL; before vmr_set_state:
+ * VMR_ESTATE.  Synchronises. */
+int vmr_expected_triads(vmr_handle h, double* out);
+
 /* Posterior predictive checks: n_rep replicated datasets drawn from the fitted model over the support of the handle's own R and
  * reduced where they are drawn -- no replicate is ever written -- and the same reduction of the observed data.
  * Replicate r: Y_r is exactly what vmr_sample(h, seed_y + r, n_trials, ..) writes (mod 2^64; the CURRENT rho, after vmr_restore

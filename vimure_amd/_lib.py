@@ -13,6 +13,8 @@ STEP_GAMMA, STEP_PHI, STEP_RHO, STEP_NU = 0, 1, 2, 3
 KERNEL_GAMMA_MASK, KERNEL_GAMMA_COUNTS, KERNEL_PHI, KERNEL_RHO, KERNEL_ELBO, KERNEL_FINALIZE, KERNEL_RHO_ELBO, KERNEL_RHO_NOSTORE = range(8)
 READ_RHO_MAX, READ_RHO_MEAN, READ_THRESHOLD = 0, 1, 2
 PPC_NSTAT = 6
+TRIAD_NSTAT = 6
+TRIAD_NAMES = ["transitive", "cyclic", "two_paths", "triangles_u", "wedges_u", "edges_u"]
 EDGE_REPORTED, EDGE_INFERRED = 1, 2
 SCORE_RHO1, SCORE_PROB = 0, 1
 SCORE_NCONF, SCORE_NSUM, SCORE_MAX_THR = 5, 4, 4096
@@ -65,6 +67,8 @@ SIGNATURES = {
     "vmr_sample": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_int]),
     "vmr_sample_stats": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vmr_expected_stats": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "vmr_sample_triads": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vmr_expected_triads": (C.c_int, [C.c_void_p, C.c_void_p]),
     "vmr_ppc_replicates": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
     "vmr_ppc_observed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -203,6 +203,15 @@ int ns_draw_chunk(vmr_ctx* h, uint8_t* Y, unsigned long long seed0, int C, int n
   return VMR_OK;
 }
 
+// declared in vmr_internal.h: the expected triads (triads.hip) start from the same edge probabilities
+int ns_exp_p(vmr_ctx* h, double* P, double* part, int nb) {
+  const Geo& g = h->g;
+  const size_t T = (size_t)g.N * g.N;
+  hipLaunchKernelGGL(k_ns_exp_p, dim3((unsigned)nb, (unsigned)g.L), dim3(256), 0, h->stream, h->rho, P, part, g.K, h->perm, T, (T + 63) / 64);
+  HIPCHK(h, hipGetLastError());
+  return VMR_OK;
+}
+
 extern "C" int vmr_sample_stats(vmr_handle h, uint64_t seed, int n_samples, int n_trials, const uint8_t* y_ref, int y_ref_on_device,
                                 uint64_t* counts, int32_t* deg_out, int32_t* deg_in) {
   if (!h) return VMR_EINVAL;
@@ -278,8 +287,7 @@ extern "C" int vmr_expected_stats(vmr_handle h, double* out) {
   int rc;
   double *P = nullptr, *part = nullptr, *od = nullptr;
   if ((rc = tm.get(h, &P, ties * 8)) || (rc = tm.get(h, &part, (size_t)g.L * nb * 32)) || (rc = tm.get(h, &od, (size_t)g.L * 32))) return rc;
-  hipLaunchKernelGGL(k_ns_exp_p, dim3((unsigned)nb, (unsigned)g.L), dim3(256), 0, h->stream, h->rho, P, part, g.K, h->perm, T, (T + 63) / 64);
-  HIPCHK(h, hipGetLastError());
+  if ((rc = ns_exp_p(h, P, part, nb))) return rc;
   hipLaunchKernelGGL(k_ns_exp_pairs, dim3((unsigned)nb, (unsigned)g.L), dim3(256), 0, h->stream, P, part, g.N);
   HIPCHK(h, hipGetLastError());
   hipLaunchKernelGGL(k_ns_exp_finish, dim3((unsigned)g.L), dim3(256), 0, h->stream, part, nb, od);

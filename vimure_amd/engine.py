@@ -47,6 +47,11 @@ class ReporterInfluenceArgumentError(EngineError, ValueError):
     are too many, a table entry out of range, a layer out of range, a table shorter than the flagged rows."""
 
 
+class TriadArgumentError(EngineError, ValueError):
+    """An argument `sample_triads` / `expected_triads` refuse (VMR_EINVAL): n_samples or n_trials below 1, temporaries that do
+    not fit in the free device memory."""
+
+
 SCORE_OUTPUTS = ("hist", "conf", "sums", "auc", "auc_pairs")
 INF_SELECT = {"none": 0, "lost": _lib.INF_LOST, "gained": _lib.INF_GAINED, "both": _lib.INF_LOST | _lib.INF_GAINED}
 # columns of the table of `CaviEngine.reporter_influence`, in the order of vmr_reporter_influence's row pointers
@@ -434,6 +439,38 @@ class CaviEngine:
         out = np.zeros((self.L, 4), np.float64)
         self._check(self.lib.vmr_expected_stats(self._h, out.ctypes.data))
         return {"edges": out[:, 0].copy(), "weight": out[:, 1].copy(), "mutual": out[:, 2].copy(), "edges_var": out[:, 3].copy()}
+
+    def _check_triads(self, rc):
+        if rc == _lib.VMR_EINVAL:
+            raise TriadArgumentError(self.lib.vmr_last_error(self._h).decode())
+        self._check(rc)
+
+    def sample_triads(self, seed, n_samples, n_trials=1, nodes=False):
+        """Triad statistics of n_samples posterior samples, computed on the device (vmr_sample_triads): sample s is
+        `self.sample(seed + s, n_trials)`, A = (Y > 0) with the diagonal cleared, U = A | A.T.  Returns a dict of int64 [S, L]
+        arrays: `transitive` #{i->j, j->k, i->k}, `cyclic` #{i->j, j->k, k->i} (ordered: a 3-cycle counts 3 times), `two_paths`
+        #{i->j, j->k}, `triangles_u`, `wedges_u` sum_i d_i (d_i - 1) / 2 and `edges_u` of U; with nodes=True also `node_tri` (the
+        triangles of U through each node) and `node_deg` (its degree in U), int32 [S, L, N].  A refused argument raises
+        `TriadArgumentError`."""
+        S = int(n_samples)
+        counts = np.zeros((max(S, 0), self.L, _lib.TRIAD_NSTAT), np.uint64)
+        ntri = np.zeros((max(S, 0), self.L, self.N), np.int32) if nodes else None
+        ndeg = np.zeros((max(S, 0), self.L, self.N), np.int32) if nodes else None
+        self._check_triads(self.lib.vmr_sample_triads(self._h, int(seed) & (2 ** 64 - 1), S, int(n_trials), counts.ctypes.data,
+                                                      ntri.ctypes.data if nodes else None, ndeg.ctypes.data if nodes else None))
+        c = counts.astype(np.int64)
+        out = {k: np.ascontiguousarray(c[..., q]) for q, k in enumerate(_lib.TRIAD_NAMES)}
+        if nodes:
+            out["node_tri"], out["node_deg"] = ntri, ndeg
+        return out
+
+    def expected_triads(self):
+        """The six counts of `sample_triads` in expectation under q(Y) = prod rho (vmr_expected_triads), no sampling: dict of
+        float64 [L] arrays under the same names.  Expectations of counts: a ratio of two of them is not the expectation of the
+        ratio."""
+        out = np.zeros((self.L, _lib.TRIAD_NSTAT), np.float64)
+        self._check_triads(self.lib.vmr_expected_triads(self._h, out.ctypes.data))
+        return {k: out[:, q].copy() for q, k in enumerate(_lib.TRIAD_NAMES)}
 
     def sub_step(self, which):
         self._check(self.lib.vmr_sub_step(self._h, int(which)))

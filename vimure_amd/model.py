@@ -717,14 +717,20 @@ class VimureModel(TransformerMixin, BaseEstimator):
                           UserWarning)
         return float(auc)
 
-    def posterior_network_stats(self, n_samples=100, seed=None, n_trials=1, Y_true=None, degrees=False, X=None, R=None):
+    def posterior_network_stats(self, n_samples=100, seed=None, n_trials=1, Y_true=None, degrees=False, X=None, R=None,
+                                triads=False, local_clustering=False):
         """Posterior distribution of the network's summary statistics, computed on the GPU (vmr_sample_stats,
         vmr_expected_stats): n_samples draws of Y from q(Y) -- sample s is `sample_inferred_model(N=n_trials, seed=seed + s,
         device=True)[0]` -- reduced where rho lives to edges, weight, mutual pairs and, with Y_true [L,N,N], true positives (and
         the degrees when asked); only those counts cross PCIe.  Returns a `netstats.NetworkStats`: the counts, reciprocity
         (`utils.calculate_overall_reciprocity` per sample), density, precision / recall / F1 against Y_true, the analytic
-        expectations (`expected`) and `summary()`.  seed None: the fit's.  Engine as in `calculate_mean_poisson`."""
+        expectations (`expected`) and `summary()`.  seed None: the fit's.  Engine as in `calculate_mean_poisson`.
+        triads=True: also the triad counts of the same samples (vmr_sample_triads: transitive and cyclic triples, two-paths,
+        and triangles, wedges and edges of the symmetrised network, self-loops left out), the transitivity and cyclicity
+        ratios per sample and the expected counts (vmr_expected_triads) as `expected["exp_<name>"]`; local_clustering=True
+        (implies triads): also every node's triangles and degree, its local clustering coefficient and their average."""
         from .netstats import NetworkStats
+        triads = bool(triads or local_clustering)
         if seed is None:
             seed = self.seed
         ref_edges = None
@@ -737,12 +743,17 @@ class VimureModel(TransformerMixin, BaseEstimator):
         try:
             counts = eng.sample_stats(seed, n_samples, n_trials=n_trials, Y_ref=Y_true, degrees=degrees)
             expected = eng.expected_stats()
+            tri = exp_tri = None
+            if triads:
+                tri = eng.sample_triads(seed, n_samples, n_trials=n_trials, nodes=bool(local_clustering))
+                exp_tri = eng.expected_triads()
         finally:
             if tmp:
                 eng.close()
         if Y_true is not None and ref_edges is None:
             ref_edges = (Y_true > 0).sum(dim=(1, 2)).cpu().numpy()
-        return NetworkStats(self.N, counts, expected=expected, ref_edges=ref_edges, seed=seed, n_trials=n_trials)
+        return NetworkStats(self.N, counts, expected=expected, ref_edges=ref_edges, seed=seed, n_trials=n_trials, triads=tri,
+                            expected_triads=exp_tri)
 
     def posterior_predictive_check(self, n_rep=100, seed=None, params="draw", n_trials=1, by_reporter=False, X=None, R=None):
         """Does data drawn from the fitted model look like the data it was fitted to?  n_rep replicated datasets are drawn on the

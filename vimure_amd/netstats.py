@@ -1,9 +1,12 @@
 """Result of `VimureModel.posterior_network_stats`: the counts the device returns per posterior sample and layer
-(`CaviEngine.sample_stats`), the analytic expectations (`CaviEngine.expected_stats`), and what is derived from them on the host.
+(`CaviEngine.sample_stats`, and `CaviEngine.sample_triads` when triads were asked for), the analytic expectations
+(`CaviEngine.expected_stats`, `CaviEngine.expected_triads`), and what is derived from them on the host.
 """
 import numpy as np
 
 _EXPECTED_KEYS = ("edges", "weight", "mutual", "edges_var")
+TRIAD_KEYS = ("transitive", "cyclic", "two_paths", "triangles_u", "wedges_u", "edges_u")
+_TRIAD_RATIOS = ("transitivity_directed", "cyclicity", "transitivity")
 
 
 def _ratio(a, b):
@@ -14,6 +17,12 @@ def _ratio(a, b):
     return out
 
 
+def _nanmean_last(a):
+    """Mean over the last axis leaving NaN out; NaN where every entry is NaN (no warning)."""
+    ok = ~np.isnan(a)
+    return _ratio(np.where(ok, a, 0.0).sum(-1), ok.sum(-1))
+
+
 class NetworkStats:
     """Per sample s and layer l (arrays [S, L]; sample s is the draw of seed + s):
       edges, weight, mutual, tp   the raw integer counts over all (i, j), the diagonal included (tp: zeros without Y_true)
@@ -22,9 +31,20 @@ class NetworkStats:
       precision, recall, f1       with Y_true: tp / edges, tp / ref_edges, 2 tp / (edges + ref_edges); NaN where undefined
       deg_out, deg_in             int32 [S, L, N] when asked for
     ref_edges [L]: (Y_true > 0).sum() per layer.  expected: dict of float64 [L] arrays -- `edges`, `weight`, `mutual`,
-    `edges_var` (`CaviEngine.expected_stats`) and `expected_reciprocity` = mutual / edges."""
+    `edges_var` (`CaviEngine.expected_stats`) and `expected_reciprocity` = mutual / edges.
 
-    def __init__(self, N, counts, expected=None, ref_edges=None, seed=None, n_trials=1):
+    With triads (`CaviEngine.sample_triads`: A = (Y > 0) without its diagonal, U = A | A.T; None otherwise):
+      transitive, cyclic, two_paths, triangles_u, wedges_u, edges_u   the integer counts
+      transitivity_directed       transitive / two_paths
+      cyclicity                   cyclic / two_paths
+      transitivity                3 triangles_u / wedges_u        (NaN where the denominator is 0)
+      node_tri, node_deg          int32 [S, L, N] when asked for: triangles of U through a node, its degree d in U
+      local_clustering            [S, L, N] 2 node_tri / (d (d - 1)), NaN where d < 2; avg_clustering [S, L] its mean over the
+                                  nodes where it is defined
+    and `expected` gains `exp_<count>` (`CaviEngine.expected_triads`): expectations of the counts -- a ratio of them is not the
+    expectation of the ratio."""
+
+    def __init__(self, N, counts, expected=None, ref_edges=None, seed=None, n_trials=1, triads=None, expected_triads=None):
         self.N = int(N)
         self.seed, self.n_trials = seed, int(n_trials)
         for k in ("edges", "weight", "mutual", "tp"):
@@ -44,12 +64,35 @@ class NetworkStats:
         if expected is not None:
             self.expected = {k: np.asarray(expected[k], dtype=np.float64) for k in _EXPECTED_KEYS}
             self.expected["expected_reciprocity"] = _ratio(self.expected["mutual"], self.expected["edges"])
+        for k in TRIAD_KEYS + _TRIAD_RATIOS + ("node_tri", "node_deg", "local_clustering", "avg_clustering"):
+            setattr(self, k, None)
+        self.has_triads = triads is not None
+        if self.has_triads:
+            for k in TRIAD_KEYS:
+                setattr(self, k, np.asarray(triads[k], dtype=np.int64))
+            self.transitivity_directed = _ratio(self.transitive, self.two_paths)
+            self.cyclicity = _ratio(self.cyclic, self.two_paths)
+            self.transitivity = _ratio(3 * self.triangles_u, self.wedges_u)
+            self.node_tri, self.node_deg = triads.get("node_tri"), triads.get("node_deg")
+            if self.node_tri is not None and self.node_deg is not None:
+                d = np.asarray(self.node_deg, dtype=np.int64)
+                self.local_clustering = _ratio(2 * np.asarray(self.node_tri, dtype=np.int64), d * (d - 1))
+                self.avg_clustering = _nanmean_last(self.local_clustering)
+            if expected_triads is not None:
+                if self.expected is None:
+                    self.expected = {}
+                for k in TRIAD_KEYS:
+                    self.expected["exp_" + k] = np.asarray(expected_triads[k], dtype=np.float64)
 
     def statistics(self):
         """name -> [S, L] array of every per-sample statistic this result holds."""
         out = {k: getattr(self, k) for k in ("edges", "weight", "mutual", "reciprocity", "density")}
         if self.ref_edges is not None:
             out.update({k: getattr(self, k) for k in ("tp", "precision", "recall", "f1")})
+        if self.has_triads:
+            out.update({k: getattr(self, k) for k in TRIAD_KEYS + _TRIAD_RATIOS})
+            if self.avg_clustering is not None:
+                out["avg_clustering"] = self.avg_clustering
         return out
 
     def summary(self, q=(0.025, 0.5, 0.975)):
