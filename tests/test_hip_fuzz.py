@@ -23,3 +23,15 @@ def test_random_cases_beyond_eight_categories_and_byte_counts(seed):
     g = np.random.RandomState(seed)
     bad = [i for i in range(30) if not one(i, g, wide=True)]
     assert not bad, bad
+
+
+@pytest.mark.parametrize("seed", [5])
+def test_random_cases_where_the_exponentials_leave_the_range(seed):
+    """The `range` family: the cases of tests/exp_range_util.py with random K in {2, 3, 4, 5, 8, 9, 16}, mask kind, large counts or
+    none, engine shape and layer scales -- rho tie by tie after one update (all-zero rows exact, NaN masks equal, the subnormal-sum
+    bound), then nu, gamma and phi from it."""
+    from tools.fuzz_parity import one_range
+    g = np.random.RandomState(seed)
+    res = [one_range(i, g) for i in range(20)]
+    assert not [i for i, r in enumerate(res) if r is not None and not r]
+    assert res.count(None) == 0, "a drawn case has a tie at an edge and was skipped: 20 cases are to run"

@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """Randomised parity sweep (GPU box): random shapes, K, mutuality, mask kinds, count ranges and engine shapes against the
-coordinate-list oracle -- three sweeps with the ELBO each, state compared at the end.  `python tools/fuzz_parity.py [n] [seed] [wide|long]`.
+coordinate-list oracle -- three sweeps with the ELBO each, state compared at the end.  `python tools/fuzz_parity.py [n] [seed] [wide|long|range]`.
 long: many reports per tie with mirrored counts (the sweep's general body, ties sorted by the second key, level-0 rounds), two passes
-and far lists forced at random."""
+and far lists forced at random.
+range: the rho update where the reference's raw exponentials leave the range of a double (tests/exp_range_util.py: all-zero rows,
+subnormal sums, NaN rows) with random K, mask kind, engine shape and layer scales -- one rho update from the drawn state, tie by tie."""
 import os
 import sys
 import time
@@ -148,15 +150,106 @@ def one(case, g, wide=False, long_=False):
                 os.environ[k] = v
 
 
+def one_range(case, g):
+    """The builder of tests/exp_range_util.py with random K, mask kind, large counts or none, engine shape and scales of the two
+    layers' E[theta]; rho after one update against the oracle band by band (the subnormal-sum bound 2u (1 + K rho) / S included, with
+    the argument term of exp_range_util.argument_bound where S > 2^43 u: a random draw may put rows there that the exp bound alone
+    cannot cover), then nu, gamma and phi from that rho -- relative 1e-9 where the oracle is finite, the same NaN entries where it
+    is not.  Returns True / False, or None for a draw that is no case: a tie at an edge that last bits would decide."""
+    from tests import exp_range_util as u
+    from vimure_amd import CaviEngine, _lib
+    K = int(g.choice([2, 2, 3, 4, 5, 8, 9, 16]))
+    mask = str(g.choice(["partial", "ones"]))
+    kind = str(g.choice(["finite", "overflow"]))
+    seed = int(g.randint(1, 1 << 20))
+    X, R, pri, st = u.build_case(K, mask, seed, kind)
+    # layer 0 stays mild, layer 1 around the edges of the range: under a partial mask T differs tie by tie and any scale leaves
+    # ties on both sides; under the all-ones mask T E[lambda] is one number, 752 min_k at scale 1 -- 0.95..1.1 keeps the ties
+    # without reports between subnormal sums (714) and all zero (827) and those with reports straddling the lower edge
+    scale = np.array([g.uniform(0.5, 2.0), g.uniform(0.95, 1.1) if mask == "ones" else g.uniform(0.7, 1.5)])
+    st = (st[0] * scale[:, None],) + tuple(st[1:])
+    env = {}
+    if K <= 8:
+        fmt = str(g.choice(["sparse", "sparse", "dense"]))
+        env["VMR_FORMAT"] = fmt
+        if fmt == "sparse":
+            r = g.rand()
+            if r < 0.35:
+                env["VMR_TWO_PASS"] = "1"
+                for name in ("VMR_NO_LEVEL0", "VMR_NO_X0", "VMR_NO_LV0R"):
+                    if g.rand() < 0.2:
+                        env[name] = "1"
+            elif r < 0.6:
+                env.update({"VMR_TWO_PASS": "0", "VMR_YT": str(int(g.randint(0, 3))), "VMR_HC": str(int(g.randint(0, 3)))})
+            if K == 2 and g.rand() < 0.3:
+                env["VMR_NO_LPD"] = "1"
+            if g.rand() < 0.3:
+                env["VMR_TPB"] = str(int(g.choice([64, 128, 256, 512])))
+    names = ("VMR_FORMAT", "VMR_TWO_PASS", "VMR_YT", "VMR_HC", "VMR_NO_LEVEL0", "VMR_NO_X0", "VMR_NO_LV0R", "VMR_NO_LPD", "VMR_TPB")
+    old = {k: os.environ.get(k) for k in names}
+    for k in names:
+        os.environ.pop(k, None)
+    os.environ.update(env)
+    use_coo = bool(g.rand() < 0.3) and env.get("VMR_FORMAT") != "dense"
+    desc = f"case {case}: range K{K} mask={mask} {kind} seed={seed} scale={scale.round(3).tolist()} env={env}" + (" [coo]" if use_coo else "")
+    try:
+        a, mag = u.log_rho(X, R, st, magnitude=True)
+        band, rho_np, S = u.bands(a)
+        d_zero, d_max, dec = u.edge_distances(a, rho_np)
+        if d_zero <= 1e-6 or d_max <= 1e-6 or dec <= 1.0:   # last bits of exp would decide a tie's band: not a case (the conditions
+            print(desc, f"-> skipped: a tie at an edge ({d_zero:.2g}, {d_max:.2g}, {dec:.2g})", flush=True)   # of tests/test_exp_range_host.py)
+            return None
+        c = u.coo_oracle(X, R, K, pri, st)
+        if use_coo:
+            sx = np.nonzero(X)
+            eng = CaviEngine.from_coo(sx, X[sx], X.shape, R=np.nonzero(R), K=K, mutuality=True, device=0)
+        else:
+            eng = CaviEngine(X, R, K=K, mutuality=True, device=0)
+        eng.set_priors(*pri)
+        eng.set_state(*st)
+        eng.sub_step(_lib.STEP_RHO)
+        c.update_rho()
+        ok = True
+        try:
+            u.assert_rho(eng.get_state(rho=True)["rho"], c.rho, band, S, K, what="rho", mag=mag)
+        except AssertionError as ex:
+            ok = False
+            print(desc, "->", str(ex).strip().splitlines()[0], flush=True)
+        for step, upd, names_ in ((_lib.STEP_NU, c.update_nu, ("nu_shp",)), (_lib.STEP_GAMMA, c.update_gamma, ("gamma_shp", "gamma_rte")),
+                                  (_lib.STEP_PHI, c.update_phi, ("phi_shp", "phi_rte"))):
+            eng.sub_step(step)
+            upd()
+            got = eng.get_state(rho=False)
+            for n in names_:
+                a, b = np.asarray(got[n], dtype=float), np.asarray(getattr(c, n), dtype=float)
+                fin = np.isfinite(b)
+                if not np.array_equal(np.isnan(a), np.isnan(b)) or not np.allclose(a[fin], b[fin], rtol=1e-9, atol=0.0):
+                    ok = False
+                    print(desc, f"-> {n} mismatch", flush=True)
+        counts = [int((band == b).sum()) for b in range(5)]
+        fmt_used = eng.data_format()[0]
+        eng.close()
+        if ok:
+            print(desc, "->", fmt_used, dict(zip(u.BAND_NAMES, counts)), "ok", flush=True)
+        return ok
+    finally:
+        for k, v in old.items():
+            os.environ.pop(k, None)
+            if v is not None:
+                os.environ[k] = v
+
+
 def main():
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 40
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 0
     wide = len(sys.argv) > 3 and sys.argv[3] == "wide"
     long_ = len(sys.argv) > 3 and sys.argv[3] == "long"
+    range_ = len(sys.argv) > 3 and sys.argv[3] == "range"
     g = np.random.RandomState(seed)
     t0 = time.time()
-    bad = sum(0 if one(i, g, wide, long_) else 1 for i in range(n))
-    print(f"{n} cases, {bad} failed, {time.time() - t0:.0f} s", flush=True)
+    res = [(one_range(i, g) if range_ else one(i, g, wide, long_)) for i in range(n)]
+    bad = sum(1 for r in res if r is not None and not r)
+    print(f"{n} cases, {bad} failed, {sum(1 for r in res if r is None)} skipped, {time.time() - t0:.0f} s", flush=True)
     sys.exit(1 if bad else 0)
 
 

@@ -127,9 +127,10 @@ __device__ __forceinline__ void sweep_body(const SlArgs& a, const Geo& g, const 
   for (int k = 0; k < K; ++k) { Ela[k] = a.par[o.E_la + l * K + k]; Gla[k] = a.par[o.G_la + l * K + k]; Lla[k] = a.par[o.l_la + l * K + k]; if (LV0 || LV0R) gz = gz || Gla[k] == 0.0; }
   const double eps = g.eps;
   // fixed point of the deterministic mode: v * 2^sh rounded to nearest through the 1.5 * 2^52 trick (|v| 2^sh < 2^51: the host caps
-  // det_sh at 40 and det_shr at 34 -- counts hold 11 bits, ELBO terms 16 -- and keeps DET_SH_A = 30 for sums of rho)
-  const double sc_h = DET ? __builtin_amdgcn_ldexp(1.0, g.det_sh) : 0.0, sc_r = DET ? __builtin_amdgcn_ldexp(1.0, g.det_shr) : 0.0;
-  const double sc_a = DET ? __builtin_amdgcn_ldexp(1.0, DET_SH_A) : 0.0;
+  // det_sh at 40 -- counts hold 11 bits -- and det_sha at 42 for sums of rho: a wave's 64 values at once; the ELBO terms take the
+  // exact conversion, det_fx, so that det_shr may go beyond the 34 the trick would allow them)
+  const double sc_h = DET ? __builtin_amdgcn_ldexp(1.0, g.det_sh) : 0.0;
+  const double sc_a = DET ? __builtin_amdgcn_ldexp(1.0, g.det_sha) : 0.0;
   auto fxm = [](double v, double scale) SL_INL -> unsigned long long {
     return (unsigned long long)(__double_as_longlong(fma(v, scale, 6755399441055744.0)) - 0x4338000000000000ll);
   };
@@ -419,7 +420,7 @@ __device__ __forceinline__ void sweep_body(const SlArgs& a, const Geo& g, const 
 #pragma unroll
         for (int u = 0; u < LG; ++u) if (j0 + u < NP) {
           const double term = (double)SL_X(e[j0 + u]) * log_tab(in_[u], lt);
-          if (DET) ie_log += fxm(term, sc_r); else e_log += term;
+          if (DET) ie_log += det_fx(term, g.det_shr); else e_log += term;
         }
         __builtin_amdgcn_sched_barrier(0);   // (keeps the scheduler from hoisting every group's table reads and chains to the top: spills)
       }
@@ -684,7 +685,7 @@ __device__ __forceinline__ void sweep_body(const SlArgs& a, const Geo& g, const 
               asm volatile("" ::: "memory");
             }
           }
-          if (ELBO) { const double term = (double)x * log_tab(elbo_inner(c, er), lt); if (DET) ie_log += fxm(term, sc_r); else e_log += term; }
+          if (ELBO) { const double term = (double)x * log_tab(elbo_inner(c, er), lt); if (DET) ie_log += det_fx(term, g.det_shr); else e_log += term; }
         }, Rw);
         if (LV0 && a.h0s && a.do_hist == 1 && act) {
 #pragma unroll

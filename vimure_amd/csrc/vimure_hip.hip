@@ -2081,8 +2081,8 @@ __global__ __launch_bounds__(256) void k_det_fold(unsigned long long* __restrict
     if (u == 0ull) continue;
     d[q] = 0ull;
     if (q < L * nH) { const size_t l = q / nH, i = q - l * nH; Hg[l * NH * nH + i] += det_back(u, g.det_sh); }
-    else if (q < L * nH + L * nA) { const size_t r = q - L * nH, l = r / nA, i = r - l * nA; slotA[l * NSLOT * nA + i] += det_back(u, DET_SH_A); }
-    else if (q < L * nH + L * nA + L * K) { const size_t r = q - L * nH - L * nA, l = r / K, k = r - l * K; slotF[l * NSLOT * K + k] += det_back(u, DET_SH_A); }
+    else if (q < L * nH + L * nA) { const size_t r = q - L * nH, l = r / nA, i = r - l * nA; slotA[l * NSLOT * nA + i] += det_back(u, g.det_sha); }
+    else if (q < L * nH + L * nA + L * K) { const size_t r = q - L * nH - L * nA, l = r / K, k = r - l * K; slotF[l * NSLOT * K + k] += det_back(u, g.det_sha); }
     else { const size_t r = q - L * nH - L * nA - L * K; slotR[r] += det_back(u, g.det_shr); }
   }
 }
@@ -2632,7 +2632,7 @@ static int sl_finish(vmr_ctx* h) {
 
 // VMR_DETERMINISTIC=1: the fixed-point scales (Geo::det_sh, det_shr) from the sum of all counts.  xbits: bits of the largest count
 // a single add into H can carry -- the sweep kernels convert such a term with the 1.5 * 2^52 trick, which holds |v| 2^sh < 2^51.
-static int det_scales(vmr_ctx* h, int xbits) {
+static int det_scales(vmr_ctx* h, int xbits, int shr_max) {
   Geo& g = h->g;
   unsigned long long sx = 0;
   CK(hipMemcpyAsync(&sx, h->sumx, 8, hipMemcpyDeviceToHost, h->stream));
@@ -2643,7 +2643,10 @@ static int det_scales(vmr_ctx* h, int xbits) {
   const unsigned long long eb = 64ull * (sx + (unsigned long long)g.L * g.N * g.N * g.K);
   int rbits = 1;
   while (rbits < 62 && (eb >> rbits) != 0ull) ++rbits;
-  g.det_shr = std::min(34, std::max(0, 61 - rbits));   // (<= 34: ELBO terms up to 2047 * |log eps| < 2^17)
+  // Up to 34 the scale leaves room for eb itself (34: a term converted by the 1.5 * 2^52 trick, ELBO terms up to 2047 * |log eps| < 2^17).
+  // eb is no bound on what a partial can hold -- sum over ties of rho T E[lambda] grows with E[theta] -- so a finer scale (shr_max,
+  // where the terms are converted exactly) is taken only while 2^63 / 2^det_shr stays above 64 eb = 4096 (sum x + L N^2 K).
+  g.det_shr = std::max(std::min(34, std::max(0, 61 - rbits)), std::min(shr_max, 57 - rbits));
   return VMR_OK;
 }
 
@@ -2690,10 +2693,10 @@ static int create_tail(vmr_ctx* h, const hipDeviceProp_t& prop) {
       CK(hipStreamSynchronize(h->stream));
       int xbits = 1;
       while (xbits < 32 && (xm >> xbits) != 0u) ++xbits;
-      int rc = det_scales(h, xbits);
+      int rc = det_scales(h, xbits, 34);
       if (rc) return rc;
       // sums of rho: a 64-bit cell (or a lane's sum) holds at most N^2 ties' worth; 2^-50 at most (the conversion trick, rho <= 1).
-      // (The specialised kernels' fixed 2^-30 moved a K = 12 fit with many nearly empty categories 5e-8 from the default mode.)
+      // (A fixed 2^-30 moved a K = 12 fit with many nearly empty categories 5e-8 from the default mode.)
       const unsigned long long T_ = (unsigned long long)g.N * g.N;
       int tbits = 1;
       while (tbits < 62 && (T_ >> tbits) != 0ull) ++tbits;
@@ -2843,8 +2846,15 @@ static int create_tail(vmr_ctx* h, const hipDeviceProp_t& prop) {
     // VMR_DETERMINISTIC=1 (sorted report lists only): see SlArgs::det.  The fixed point of the count-weighted sums leaves
     // room for the sum of all counts.
     if (!h->sparse) return fail(nullptr, VMR_EINVAL, "VMR_DETERMINISTIC=1 needs the report lists (a sparse tensor with M <= 8192, counts <= 2047)");
-    int rc = det_scales(h, 11);   // (packed entries: counts up to 2047)
+    int rc = det_scales(h, 11, 45);   // (packed entries: counts up to 2047; the ELBO terms are converted exactly, whatever their size)
     if (rc) return rc;
+    // sums of rho: a 64-bit cell holds at most N^2 ties' worth, and one conversion a wave's 64 values (64 rho 2^42 < 2^51 up to rho = 4).
+    // (A fixed 2^-30 left gamma_rte 1.3e-9 from the reference where most rows of rho are all zero and a category's few tiny values
+    // meet a large E[lambda]: tests/test_hip_exp_range.py.)
+    const unsigned long long T_ = (unsigned long long)g.N * g.N;
+    int tbits = 1;
+    while (tbits < 62 && (T_ >> tbits) != 0ull) ++tbits;
+    g.det_sha = std::min(42, 62 - tbits);
     const size_t nd = (size_t)L * g.Y * g.Mp * K + (size_t)L * g.W * 64 * K + (size_t)L * K + 5;
     CK(hipMalloc(&h->det_buf, nd * 8));
     CK(hipMemsetAsync(h->det_buf, 0, nd * 8, h->stream));

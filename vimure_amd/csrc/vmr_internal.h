@@ -61,18 +61,17 @@ struct Geo {
   double eps;
   int det;      // VMR_DETERMINISTIC=1: bit-reproducible sweeps (one wave per workgroup, fixed step shares, integer cross-workgroup sums)
   int det_sh;   // ... whose fixed point for count-weighted sums (H, the nu share) is 2^-det_sh: sum x of the dataset < 2^(62 - det_sh)
-  int det_shr;  // ... and 2^-det_shr for the ELBO partials (bounded by 64 (sum x + ties K))
+  int det_shr;  // ... and 2^-det_shr for the ELBO partials (det_scales; at most 45, 34 on the general kernels)
   int gen;      // the general kernels (sweep_gen.hip): K > KMAX, or entries too wide for the packed format.  H is then ONE copy
                 // [L][Y][Mp][K] holding every category (no constant C, no deficits), nu and the mask sums go through k_fin_rho / the pass
   int farl;     // report lists, one pass per sweep although not every level of F / H fits in LDS: the reports of the levels beyond
                 // (y >= hc = yt; a few per cent) are ALSO kept as a compact list (vmr_ctx::far_pos / far_ent); the pass takes their
                 // factors by formula and leaves their statistics to k_far_hist, which follows it
   int wide;     // entries in two words (vmr_ctx::EX): counts beyond 2047 or (max count + 1) * Mp beyond 2^20 table rows
-  int det_sha;  // VMR_DETERMINISTIC=1 on the general kernels: sums of rho over ties in 2^-det_sha (N^2 2^det_sha <= 2^62, at most 2^-50)
+  int det_sha;  // VMR_DETERMINISTIC=1: sums of rho over ties in 2^-det_sha (N^2 2^det_sha <= 2^62; at most 2^-50 on the general kernels,
+                // 2^-42 on the specialised ones, which convert a wave's sum of 64 values in one go)
 };
-// fixed point of the deterministic mode: count-weighted sums 2^-g.det_sh; ELBO partials 2^-g.det_shr; sums of rho over ties (< 2^31 ties)
-// 2^-30 on the specialised kernels, 2^-g.det_sha on the general ones
-#define DET_SH_A 30
+// fixed point of the deterministic mode: count-weighted sums 2^-g.det_sh; ELBO partials 2^-g.det_shr; sums of rho over ties 2^-g.det_sha
 #define DET_SH2 30   // general kernels: the ELBO partials' second word is 2^-(det_shr + DET_SH2) (sweep_gen.hip, gen_fx2)
 __device__ __forceinline__ unsigned long long det_fx(double v, int sh) { return (unsigned long long)__double2ll_rn(ldexp(v, sh)); }
 __device__ __forceinline__ double det_back(unsigned long long u, int sh) { return ldexp((double)(long long)u, -sh); }
