@@ -72,7 +72,7 @@ enum {
  * Environment, read here: VMR_DETERMINISTIC=1 makes the handle's sweeps bit-reproducible run to run (the reference's
  * single-threaded NumPy, model.py:623-660, is): every sum whose order varies from run to run is a 64-bit integer sum in fixed
  * point.  It covers every handle on report lists, the specialised kernels (K <= 8, packed entries) and the general ones (any K,
- * two-word entries) alike; handles on dense tiles return VMR_EINVAL, and vmr_sub_step returns VMR_ESTATE on such a handle.
+ * two-word entries) alike, whether a partial mask is held as reporter lists or as words; handles on dense tiles return VMR_EINVAL, and vmr_sub_step returns VMR_ESTATE on such a handle.
  * Cost: DESIGN.md §3c.
  */
 int vmr_create(vmr_handle* out, int device, int L, int N, int M, int K, int mutuality,
@@ -189,7 +189,12 @@ int vmr_sweep_local_dev(vmr_handle h, int want_elbo, double* out3_dev);
 int vmr_commit_nu_dev(vmr_handle h, const double* nu_partial_total_dev);
 void* vmr_stream(vmr_handle h);
 
-/* One update of a sweep (test hook for step-level parity with model.py:643-656). */
+/* One update of a sweep (test hook for step-level parity with model.py:643-656).  GAMMA, RHO and NU may come in any order, each is
+ * the reference's update from the current state with exp(E[log nu]) of the current nu.  VMR_STEP_PHI commits phi's rate as the
+ * finalize of VMR_STEP_GAMMA prepares it (one pass over the mask sums serves gamma's rate and phi's): it returns VMR_ESTATE unless
+ * a VMR_STEP_GAMMA ran since rho last changed (vmr_set_state, VMR_STEP_RHO, any sweep); VMR_STEP_NU in between is fine, and a second
+ * VMR_STEP_PHI is the reference's update once more.  Without mutuality VMR_STEP_GAMMA commits gamma AND phi and VMR_STEP_PHI does
+ * nothing.  Not available with VMR_DETERMINISTIC=1 (VMR_ESTATE). */
 int vmr_sub_step(vmr_handle h, int which);
 
 /* Copy the posteriors to the host: what `_update_optimal_parameters` snapshots
@@ -202,7 +207,9 @@ int vmr_get_state(vmr_handle h, double* gamma_shp, double* gamma_rte, double* ph
  * to the host after every realisation; vmr_restore makes the snapshot the current state again, so that
  * vmr_get_state / vmr_get_geometric read the best realisation once, at the end of `fit`.  Asynchronous on the
  * handle's stream.  The snapshot does not hold the log prior of its realisation: after vmr_restore the state can be read
- * (vmr_get_*, vmr_readout, vmr_sample) but the sweeping entry points return VMR_ESTATE until the next vmr_set_state. */
+ * (vmr_get_*, vmr_readout, vmr_sample) but the sweeping entry points (vmr_commit_nu and vmr_commit_nu_dev among them) return
+ * VMR_ESTATE until the next vmr_set_state.  The priors are the handle's, not the snapshot's: vmr_restore leaves what the last
+ * vmr_set_priors set.  A snapshot outlives vmr_set_state. */
 int vmr_snapshot(vmr_handle h);
 int vmr_restore(vmr_handle h);
 

@@ -30,3 +30,12 @@ def stats_np(Ys, Y_ref=None):
             out["deg_out"][s, l] = (Y > 0).sum(axis=1)
             out["deg_in"][s, l] = (Y > 0).sum(axis=0)
     return out
+
+
+def expected_np(rho):
+    """What `CaviEngine.expected_stats()` returns for rho [L,N,N,K], with p_ij = sum_{k>=1} rho_ijk: float64 [L] arrays."""
+    rho = np.asarray(rho, dtype=np.float64)
+    K = rho.shape[-1]
+    p = rho[..., 1:].sum(-1)
+    return {"edges": p.sum(axis=(1, 2)), "weight": (rho * np.arange(K)).sum(axis=(1, 2, 3)),
+            "mutual": np.einsum("lij,lji->l", p, p), "edges_var": (p * (1.0 - p)).sum(axis=(1, 2))}

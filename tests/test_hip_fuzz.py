@@ -35,3 +35,13 @@ def test_random_cases_where_the_exponentials_leave_the_range(seed):
     res = [one_range(i, g) for i in range(20)]
     assert not [i for i, r in enumerate(res) if r is not None and not r]
     assert res.count(None) == 0, "a drawn case has a tie at an edge and was skipped: 20 cases are to run"
+
+
+@pytest.mark.parametrize("seed", [11])
+def test_random_call_sequences_on_random_handles(seed):
+    """The `seq` family: six sequences of 20 to 40 calls (tests/call_sequence_util.py) on handles of random kinds with N, M and K
+    perturbed within the kind's family, every call against the host model."""
+    from tools.fuzz_parity import one_seq
+    g = np.random.RandomState(seed)
+    bad = [i for i in range(6) if not one_seq(i, g)]
+    assert not bad, bad

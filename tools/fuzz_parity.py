@@ -1,10 +1,13 @@
 #!/usr/bin/env python3
 """Randomised parity sweep (GPU box): random shapes, K, mutuality, mask kinds, count ranges and engine shapes against the
-coordinate-list oracle -- three sweeps with the ELBO each, state compared at the end.  `python tools/fuzz_parity.py [n] [seed] [wide|long|range]`.
+coordinate-list oracle -- three sweeps with the ELBO each, state compared at the end.  `python tools/fuzz_parity.py [n] [seed] [wide|long|range|seq]`.
 long: many reports per tie with mirrored counts (the sweep's general body, ties sorted by the second key, level-0 rounds), two passes
 and far lists forced at random.
 range: the rho update where the reference's raw exponentials leave the range of a double (tests/exp_range_util.py: all-zero rows,
-subnormal sums, NaN rows) with random K, mask kind, engine shape and layer scales -- one rho update from the drawn state, tie by tie."""
+subnormal sums, NaN rows) with random K, mask kind, engine shape and layer scales -- one rho update from the drawn state, tie by tie.
+seq: a random legal sequence of engine calls (tests/call_sequence_util.py: set_state, step, sub-steps, elbo, sweep_local + commit_nu,
+fit_loop, snapshot, restore, refused calls, readers) on a handle of a random kind with N, M and K perturbed within the kind's family,
+every call against the host model."""
 import os
 import sys
 import time
@@ -239,15 +242,49 @@ def one_range(case, g):
                 os.environ[k] = v
 
 
+def one_seq(case, g):
+    """Handle kind, shape perturbation and a sequence of 20 to 40 operations at random; True / False."""
+    from tests import call_sequence_util as u
+    kind = str(g.choice(list(u.KINDS)))
+    spec = u.KINDS[kind]
+    n0, m0 = u.SHAPES[spec["data"]]
+    N = n0 + int(g.randint(-6, 7))
+    M = N if spec["data"] == "self" else m0 + int(g.randint(-5, 6))      # (lists_two_pass draws M on both sides of 64, one mask word and two)
+    K = spec["K"] if spec["K"] in (2, 9) else int(g.choice([3, 4, 5]))
+    K = int(g.choice([9, 12, 16])) if spec["K"] == 9 else K
+    seed, n_ops = int(g.randint(1 << 20)), int(g.randint(20, 41))
+    X, R = u.build_data(spec["data"], seed=seed, N=N, M=M)
+    ops = u.draw_sequence(seed, kind, n_ops=n_ops)
+    desc = f"case {case}: seq {kind} N{N} M{M} K{K} seed={seed} ops={n_ops}"
+    old = {k: os.environ.get(k) for k in u.SWITCHES}
+    for k in old:
+        os.environ.pop(k, None)
+    os.environ.update(spec["env"])
+    try:
+        try:
+            u.run_sequence(kind, ops, X, R, K=K, label=desc)
+        except AssertionError as ex:
+            print(desc, "->", str(ex).strip().splitlines()[0][:400], flush=True)
+            return False
+        print(desc, "-> ok", flush=True)
+        return True
+    finally:
+        for k, v in old.items():
+            os.environ.pop(k, None)
+            if v is not None:
+                os.environ[k] = v
+
+
 def main():
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 40
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 0
     wide = len(sys.argv) > 3 and sys.argv[3] == "wide"
     long_ = len(sys.argv) > 3 and sys.argv[3] == "long"
     range_ = len(sys.argv) > 3 and sys.argv[3] == "range"
+    seq = len(sys.argv) > 3 and sys.argv[3] == "seq"
     g = np.random.RandomState(seed)
     t0 = time.time()
-    res = [(one_range(i, g) if range_ else one(i, g, wide, long_)) for i in range(n)]
+    res = [(one_seq(i, g) if seq else one_range(i, g) if range_ else one(i, g, wide, long_)) for i in range(n)]
     bad = sum(1 for r in res if r is not None and not r)
     print(f"{n} cases, {bad} failed, {sum(1 for r in res if r is None)} skipped, {time.time() - t0:.0f} s", flush=True)
     sys.exit(1 if bad else 0)

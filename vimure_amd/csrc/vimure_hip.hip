@@ -510,10 +510,13 @@ __global__ void k_derive_all(double* par, Geo g) {
 // the R-row words and rho.  Rows whose words are all ones only feed a per-lane sum (one v_add_f64
 // per k and 64 ties); every other row is broadcast with v_readlane and added under EXEC = its bits
 // (lane <-> reporter).
-template <int K, int NC>
+// DET (Geo::det): a wave's sums -- ties in a fixed order, so the same bits every run -- go as fixed-point integers (det_sha) into
+// the shadow of slotA's slot 0 (detA, vmr_ctx::det_buf), where the order of the adds does not matter; det_fold makes them doubles.
+template <int K, int NC, bool DET>
 __global__ __launch_bounds__(TPB) void k_gamma_mask(const uint64_t* __restrict__ Rb, const double* __restrict__ rho,
                                                     const uint8_t* __restrict__ rcls, double* __restrict__ slotA,
-                                                    int skip_full, const unsigned* __restrict__ perm /* rho by sorted position, or null */, Geo g) {
+                                                    int skip_full, const unsigned* __restrict__ perm /* rho by sorted position, or null */, Geo g,
+                                                    unsigned long long* __restrict__ detA) {
   __shared__ double sacc[NC * 64 * K];
   const int l = blockIdx.x / g.Gm, gb = blockIdx.x - l * g.Gm;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -592,6 +595,15 @@ __global__ __launch_bounds__(TPB) void k_gamma_mask(const uint64_t* __restrict__
 #pragma unroll
       for (int c = 0; c < NC; ++c)
         if (c < nc && (cg + c) * 64 + lane < g.M) acc[c][k] += u;
+    }
+    if (DET) {
+      unsigned long long* outd = detA + ((size_t)l * Wp + cg * 64) * K;
+#pragma unroll
+      for (int c = 0; c < NC; ++c)
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+          if (c < nc && acc[c][k] != 0.0) atomicAdd(&outd[(c * 64 + lane) * K + k], det_fx(acc[c][k], g.det_sha));
+      continue;
     }
     // combine the 4 waves in LDS, then one global atomic per (m,k) and workgroup
     for (int q = threadIdx.x; q < NC * 64 * K; q += TPB) sacc[q] = 0.0;
@@ -2161,6 +2173,7 @@ static int launch_hist(vmr_ctx* h, int nu = -1) {
 
 static int launch_gamma(vmr_ctx* h, bool with_phi) {
   const Geo& g = h->g;
+  h->prte_valid = !with_phi;   // (a gamma finalize on its own leaves phi's rate pending; in a sweep the rho pass follows)
   if (g.gen) return gen_gamma(h, with_phi);
   if (h->sparse && !h->h_valid) {   // report lists: the statistics pass also sums rho over the all-ones mask rows (slotF)
     int rc = launch_hist(h);
@@ -2193,11 +2206,25 @@ static int launch_gamma(vmr_ctx* h, bool with_phi) {
   } else if (!skip_full || h->n_partial > 0) {
     Prof p(h, VMR_KERNEL_GAMMA_MASK, ms);
     dim3 grid(g.L * g.Gm), blk(TPB);
+    // (deterministic handles are on report lists: their statistics are valid here, so ms is the handle's stream and det_fold follows in order)
+    unsigned long long* detA = g.det ? h->det_buf + (size_t)g.L * g.Y * g.Mp * g.K : nullptr;
+#define GMASK(NC_)                                                                                                                              \
+  do {                                                                                                                                          \
+    if (g.det) { DISPATCH_K(g.K, hipLaunchKernelGGL((k_gamma_mask<KK, NC_, true>), grid, blk, 0, ms, h->Rb, h->rho, h->rcls, h->slotA, skip_full, h->perm, g, detA)); } \
+    else { DISPATCH_K(g.K, hipLaunchKernelGGL((k_gamma_mask<KK, NC_, false>), grid, blk, 0, ms, h->Rb, h->rho, h->rcls, h->slotA, skip_full, h->perm, g, detA)); }    \
+  } while (0)
     switch (g.W >= 4 ? 4 : g.W) {
-      case 1: DISPATCH_K(g.K, hipLaunchKernelGGL((k_gamma_mask<KK, 1>), grid, blk, 0, ms, h->Rb, h->rho, h->rcls, h->slotA, skip_full, h->perm, g)); break;
-      case 2: DISPATCH_K(g.K, hipLaunchKernelGGL((k_gamma_mask<KK, 2>), grid, blk, 0, ms, h->Rb, h->rho, h->rcls, h->slotA, skip_full, h->perm, g)); break;
-      case 3: DISPATCH_K(g.K, hipLaunchKernelGGL((k_gamma_mask<KK, 3>), grid, blk, 0, ms, h->Rb, h->rho, h->rcls, h->slotA, skip_full, h->perm, g)); break;
-      default: DISPATCH_K(g.K, hipLaunchKernelGGL((k_gamma_mask<KK, 4>), grid, blk, 0, ms, h->Rb, h->rho, h->rcls, h->slotA, skip_full, h->perm, g)); break;
+      case 1: GMASK(1); break;
+      case 2: GMASK(2); break;
+      case 3: GMASK(3); break;
+      default: GMASK(4); break;
+    }
+#undef GMASK
+    if (g.det) {
+      if (ms != h->stream) return fail(h, VMR_ESTATE, "deterministic mask sums beside a statistics pass");
+      HIPCHK(h, hipGetLastError());
+      int rcd = det_fold(h);
+      if (rcd) return rcd;
     }
   }
   if (ms != h->stream) {
@@ -2246,6 +2273,7 @@ static int launch_phi(vmr_ctx* h) {
 // store = false (mode 0 on report lists in one pass only): the pass uses its new rho without writing it (vmr_ctx::rho_stale)
 static int launch_rho(vmr_ctx* h, int mode, bool commit_nu, bool raw_nu = false, bool store = true) {
   const Geo& g = h->g;
+  if (mode != 2) h->prte_valid = false;   // a new rho: the pending rate of phi is another rho's
   if (g.gen) return gen_rho(h, mode, commit_nu, raw_nu, [](vmr_ctx* hh, int do_nu, int do_elbo, int skip_nu) { return launch_fin_rho(hh, do_nu, do_elbo, skip_nu); });
   if (h->sparse && g.farl && h->elbo_split && mode == 1) {
     // An ELBO sweep of a handle whose fused variant would drop an LDS level: the plain update pass (with the far reports' kernel and
@@ -3478,6 +3506,7 @@ int vmr_set_state(vmr_handle h, const double* gamma_shp, const double* gamma_rte
   h->f_valid = false;
   h->a_valid = false;
   h->h_zero = false; h->a_zero = false;   // (whatever an earlier, possibly failed, sweep left behind)
+  h->prte_valid = false;
   if (h->h0s) HIPCHK(h, hipMemsetAsync(h->h0s, 0, (size_t)h->g.L * NSLOT * h->g.K * 8, h->stream));   // (the slots, not the constants behind them)
   if (h->gen_s1) HIPCHK(h, hipMemsetAsync(h->gen_s1, 0, (size_t)h->g.L * (h->g.Mp + h->g.K) * 8, h->stream));
   return VMR_OK;
@@ -3593,6 +3622,7 @@ int vmr_step(vmr_handle h, int n_iters, double* elbo_out) {
 }
 static int step_n(vmr_ctx* h, int n_iters, double* elbo_out, bool store_last) {
   HIPCHK(h, hipSetDevice(h->device));
+  if (n_iters > 0) h->prte_valid = false;   // (a replayed graph runs no launch helper: the sweeps change rho all the same)
   int rc;
   int it = 0;
   const int plain = elbo_out ? n_iters - 1 : n_iters;   // sweeps without an ELBO
@@ -3605,6 +3635,7 @@ static int step_n(vmr_ctx* h, int n_iters, double* elbo_out, bool store_last) {
       if (graph_for(h, n, !(ends && store_last), &ge) != VMR_OK) break;   // capture failed: the eager loop below takes over
       HIPCHK(h, hipGraphLaunch(ge->ex, h->stream));
       state_set(h, ge->sig1);
+      h->prte_valid = false;
       it += n;
     }
   }
@@ -3868,7 +3899,7 @@ int vmr_fit_loop_batch(vmr_handle* hs, int n, int max_iter, double tol, int deci
     hipLaunchKernelGGL(k_fin_gamma_b, dim3(bt.ngb), dim3(FIN_TPB), bt.fsm, st, bt.fu, bt.gmap, bt.fg);
     const int pm = (mode == 0 && lazy_rho) ? 4 : mode;
     int r = pass(h0, st, pm, allfull, bt.su[mode], bt.smap[mode], bt.nb[mode], bt.tpb[mode], bt.smem[mode]);
-    for (int u : act) hs[u]->rho_stale = pm == 4;
+    for (int u : act) { hs[u]->rho_stale = pm == 4; hs[u]->prte_valid = false; }
     if (r) return r;
     if (mode == 1) hipLaunchKernelGGL(k_fin_rho_b, dim3(bt.nrb), dim3(TPB), 0, st, bt.fu, bt.rmap);
     HIPCHK(h0, hipGetLastError());
@@ -3967,6 +3998,7 @@ int vmr_sweep_local(vmr_handle h, int want_elbo, double* out3) {
 int vmr_commit_nu(vmr_handle h, double nu_partial_total) {
   if (!h) return VMR_EINVAL;
   if (!h->have_state) return fail(h, VMR_ESTATE, "vmr_set_state must be called before vmr_commit_nu");
+  if (h->restored) return fail(h, VMR_ESTATE, "vmr_commit_nu after vmr_restore: the restored state is read-only until the next vmr_set_state");
   HIPCHK(h, hipSetDevice(h->device));
   hipLaunchKernelGGL(k_commit_nu, dim3(1), dim3(64), 0, h->stream, h->par, nu_partial_total, (const double*)nullptr, h->g);
   HIPCHK(h, hipGetLastError());
@@ -3990,6 +4022,7 @@ int vmr_sweep_local_dev(vmr_handle h, int want_elbo, double* out3_dev) {
 int vmr_commit_nu_dev(vmr_handle h, const double* nu_partial_total_dev) {
   if (!h || !nu_partial_total_dev) return VMR_EINVAL;
   if (!h->have_state) return fail(h, VMR_ESTATE, "vmr_set_state must be called before vmr_commit_nu_dev");
+  if (h->restored) return fail(h, VMR_ESTATE, "vmr_commit_nu_dev after vmr_restore: the restored state is read-only until the next vmr_set_state");
   HIPCHK(h, hipSetDevice(h->device));
   hipLaunchKernelGGL(k_commit_nu, dim3(1), dim3(64), 0, h->stream, h->par, 0.0, nu_partial_total_dev, h->g);
   HIPCHK(h, hipGetLastError());
@@ -4007,7 +4040,12 @@ int vmr_sub_step(vmr_handle h, int which) {
   { const int rce = ensure_rho(h); if (rce) return rce; }
   switch (which) {
     case VMR_STEP_GAMMA: return launch_gamma(h, false);
-    case VMR_STEP_PHI: return launch_phi(h);
+    case VMR_STEP_PHI:
+      // phi's rate is finished by the gamma finalize (one pass over the mask sums for both): without one since the last change of
+      // rho there is none to commit -- silently committing the last one gave a rate of another rho, or of another realisation
+      if (h->g.mut && !h->prte_valid)
+        return fail(h, VMR_ESTATE, "VMR_STEP_PHI commits the rate that VMR_STEP_GAMMA prepares: no VMR_STEP_GAMMA since rho last changed");
+      return launch_phi(h);
     // the rho pass also rebuilds the statistics H the nu update reads; nu is committed by the NU sub-step
     case VMR_STEP_RHO: return launch_rho(h, 0, false);
     case VMR_STEP_NU: {
@@ -4100,8 +4138,14 @@ int vmr_restore(vmr_handle h) {
   HIPCHK(h, hipSetDevice(h->device));
   const Geo& g = h->g;
   HIPCHK(h, hipMemcpyAsync(h->rho, h->rho_snap, (size_t)g.L * g.N * g.N * g.K * 8, hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(h->par, h->par_snap, h->par_doubles * 8, hipMemcpyDeviceToDevice, h->stream));
-  h->h_valid = false; h->f_valid = false; h->a_valid = false; h->h_zero = false;
+  // the posteriors and what is derived from them, NOT the priors: those are the handle's (a vmr_set_priors since the snapshot holds)
+  {
+    const ParOff o = par_off(g.L, g.Mp, g.K);
+    const size_t rng[3][2] = {{o.g_shp, o.a_la}, {o.p_shp, o.sc}, {o.sc + SC_NU_SHP, o.total}};
+    for (const auto& r : rng)
+      HIPCHK(h, hipMemcpyAsync(h->par + r[0], h->par_snap + r[0], (r[1] - r[0]) * 8, hipMemcpyDeviceToDevice, h->stream));
+  }
+  h->h_valid = false; h->f_valid = false; h->a_valid = false; h->h_zero = false; h->prte_valid = false;
   h->restored = true;   // the log prior on the device is the LAST realisation's: reading is fine, sweeping is not
   h->rho_stale = false;
   HIPCHK(h, hipMemsetAsync(h->slotF, 0, (size_t)g.L * NSLOT * g.K * 8, h->stream));

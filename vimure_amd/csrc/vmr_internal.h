@@ -185,6 +185,7 @@ struct vmr_ctx {
   bool a_zero = true;          // slotA is known to be all zero
   bool h_reduced = false;      // the NH copies of H are folded into copy 0 (what the finalize kernels read)
   bool h_zero = false;         // k_fin_gamma consumed H and slotF: both are all zero, ready for the rho pass
+  bool prte_valid = false;     // p_rte_pend is phi's rate of the current rho and theta (the last launch was a STEP_GAMMA finalize): what STEP_PHI commits
   bool fin_attr = false, ml_attr = false;
   unsigned long long* npartial = nullptr;   // rows of R that are neither empty nor all ones
   unsigned long long n_partial = 0;
