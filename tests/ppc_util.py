@@ -14,13 +14,18 @@ def load_ppc(case):
 
 def mean_poisson_np(X, R, rho, G_theta, G_lambda, G_nu, mutuality):
     """(subs, vals) over the support of R (every entry when R is None), lexicographic order:
-    vals = sum_k rho[l,i,j,k] (G_theta[l,m] G_lambda[l,k] + G_nu XT[l,i,j,m]), XT = X[l,j,i,m] with mutuality, else 0."""
+    vals = sum_k rho[l,i,j,k] (G_theta[l,m] G_lambda[l,k] + G_nu XT[l,i,j,m]), XT = X[l,j,i,m] with mutuality, else 0.
+    The sum runs over k ascending from 0.0 in elementwise operations, every product and every sum rounded on its own: the order
+    the device states, so that its values can be held to these bit for bit (an einsum's order and fusing vary with the build)."""
     X = np.asarray(X)
     R = np.ones(X.shape, bool) if R is None else (np.asarray(R) != 0)
     l, i, j, m = np.nonzero(R)
     xt = X[l, j, i, m].astype(np.float64) if mutuality else np.zeros(len(l))
-    pm = G_theta[l, m][:, None] * G_lambda[l, :] + G_nu * xt[:, None]
-    return (l, i, j, m), np.einsum("Ik,Ik->I", rho[l, i, j, :], pm)
+    nx = G_nu * xt
+    vals = np.zeros(len(l))
+    for k in range(rho.shape[-1]):
+        vals = vals + rho[l, i, j, k] * (G_theta[l, m] * G_lambda[l, k] + nx)
+    return (l, i, j, m), vals
 
 
 def dense_of(subs, vals, shape):

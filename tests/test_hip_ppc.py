@@ -124,6 +124,11 @@ def _check_restatement(eng, X, R, st, mut, layer=None):
     s_dev, v_dev = eng.mean_poisson()
     assert np.array_equal(np.stack(s_dev).astype(np.int64), np.stack(subs))
     np.testing.assert_allclose(v_dev, vals, rtol=1e-13, atol=0)
+    # bit for bit where the inputs are the same bits: the restatement's G are scipy's, the device's its own (an ulp apart at
+    # most), so the device's score is held to the restatement evaluated at the device's own G
+    gth, gla, gnu = eng.get_geometric()[:3]
+    vals_dev_g = mean_poisson_np(X, R, eng.get_state()["rho"], gth, gla, float(gnu), mut)[1]
+    assert np.array_equal(v_dev, vals_dev_g), int((v_dev != vals_dev_g).sum())
     from vimure_amd.utils import calculate_AUC
     mp = dense_of(subs, vals, X.shape)
     auc = eng.report_auc()[0]
@@ -152,6 +157,30 @@ def test_wide_coo_handle_and_two_word_entries():
     for mut in (True, False):
         eng = _engine_for(X, R, K, mut, st, coo=True)
         try:
+            _check_restatement(eng, X, R, st, mut)
+        finally:
+            eng.close()
+
+
+def test_mask_lists_with_m_past_one_group(monkeypatch):
+    """M = 70: a group is 64 lanes, so an all-ones row takes a full round and a round of six; the listed rows hold the
+    reporters either side of the group's edge (63, 64) and the last one (69); one row is empty.  (Report lists: a handle of
+    dense tiles keeps its partial rows as mask words.)"""
+    monkeypatch.setenv("VMR_FORMAT", "sparse")
+    g = np.random.RandomState(11)
+    L, N, M, K = 1, 12, 70, 3
+    R = np.zeros((L, N, N, M), np.uint8)
+    ii, jj = np.meshgrid(np.arange(N), np.arange(N), indexing="ij")
+    for m in (ii, jj, 63 + 0 * ii, 64 + 0 * ii, 69 + 0 * ii):
+        R[0, ii, jj, m] = 1
+    R[0, (ii + jj) % 5 == 0] = 1                                     # all-ones rows
+    R[0, 2, 7] = 0                                                   # an empty row
+    X = np.where(g.rand(L, N, N, M) < 0.2, g.randint(1, 6, (L, N, N, M)), 0).astype(np.int32)   # reports outside the mask too
+    st = _random_state(g, L, N, M, K)
+    for mut in (True, False):
+        eng = _engine_for(X, R, K, mut, st)
+        try:
+            assert eng.data_format()[0] == "sparse" and eng.mask_format()[0] == "lists"
             _check_restatement(eng, X, R, st, mut)
         finally:
             eng.close()

@@ -65,7 +65,9 @@ def make_engine(L, N, M, K, seed):
     from vimure_amd import CaviEngine
     from vimure_amd.synthetic import standard_sbm
     net = standard_sbm(N=N, M=M, L=L, K=2, avg_degree=10.0, eta=0.5, seed=seed, device="cuda")
-    nz = torch.nonzero(net.X)
+    # (layer by layer: torch.nonzero fails on the 3.2e9 elements of config 3 at once)
+    nz = torch.cat([torch.cat([torch.full((len(z), 1), l, dtype=z.dtype, device=z.device), z], 1)
+                    for l, z in ((l, torch.nonzero(net.X[l])) for l in range(L))])
     xs = tuple(nz[:, q].cpu().numpy().astype(np.int64) for q in range(4))
     xv = net.X[nz[:, 0], nz[:, 1], nz[:, 2], nz[:, 3]].cpu().numpy().astype(np.int64)
     eng = CaviEngine(net.X, None, K=K, mutuality=True)

@@ -11,9 +11,7 @@
 //              its ego's and alter's own reports up (ppc_x), sizes its mask row, and writes the structure-of-arrays outputs.
 // Only rows take the second kernel's extra reads: a few per cent of the ties.  No sum crosses lanes in floating point and nothing is
 // an atomic: the table is bit-identical from run to run.
-#include "vmr_internal.h"
-#include "ppc_layer.h"
-#include "rho_row.h"
+#include "read_side.h"
 
 namespace {
 
@@ -43,25 +41,6 @@ struct EtOut {
 };
 #define ET_NOUT 14
 static const size_t et_width[ET_NOUT] = {4, 4, 4, 1, 8, 8, 4, 8, 4, 4, 4, 1, 4, 8};
-
-// the byte vmr_readout writes for a tie (k_readout, vimure_hip.hip)
-__device__ __forceinline__ unsigned et_y(const double* __restrict__ r, int K, int method, double threshold) {
-  if (method == VMR_READ_THRESHOLD) return r[1] >= threshold ? 1u : 0u;
-  return rho_row_argmax(r, K);   // first maximum, as np.argmax
-}
-
-__device__ __forceinline__ const double* et_rho(const PpcLayer& p, size_t t) { return p.rho + (p.inv ? (size_t)p.inv[t] : t) * p.K; }
-
-// reporters the mask keeps for a tie
-__device__ __forceinline__ unsigned et_mask_size(const PpcLayer& p, size_t t) {
-  const int c = p.cls[t];
-  if (c == 1) return (unsigned)p.M;
-  if (c != 2) return 0u;
-  if (p.rq) return p.rq[t + 1] - p.rq[t];
-  unsigned s = 0;
-  for (int w = 0; w < p.W; ++w) s += (unsigned)__popcll(p.Rb[t * p.W + w]);
-  return s;
-}
 
 // per tie: the reports reduced, the read-out, the record.  rec has T + 1 entries; entry T is zero (the scan then ends in the row count)
 __global__ __launch_bounds__(256) void k_et_tie(PpcLayer p, int G, int method, double threshold, int select, EtRec* __restrict__ rec) {
@@ -99,7 +78,7 @@ __global__ __launch_bounds__(256) void k_et_tie(PpcLayer p, int G, int method, d
       tot += (unsigned long long)__shfl_xor((long long)tot, o, 64);
     }
     if (gl == 0) {
-      const unsigned y = et_y(et_rho(p, t), p.K, method, threshold);
+      const unsigned y = rho_row_readout(tie_rho(p, t), p.K, method, threshold);
       const bool row = ((select & VMR_EDGE_REPORTED) && cnt > 0u) || ((select & VMR_EDGE_INFERRED) && y > 0u);
       EtRec r;
       r.total = tot; r.n_rep = cnt; r.yf = y | (row ? ET_FLAG : 0u);
@@ -130,32 +109,14 @@ __global__ __launch_bounds__(256) void k_et_rows(PpcLayer p, const EtRec* __rest
     if (o.prob || o.mean) {
       // prob: the adds of vmr_expected_stats (k ascending); mean: every product and sum rounded on its own, k ascending
       double pr, mn;
-      rho_row_prob_mean(et_rho(p, t), p.K, pr, mn);
+      rho_row_prob_mean(tie_rho(p, t), p.K, pr, mn);
       if (o.prob) o.prob[at] = pr;
       if (o.mean) o.mean[at] = mn;
     }
-    if (o.n_mask) o.n_mask[at] = et_mask_size(p, t);
+    if (o.n_mask) o.n_mask[at] = mask_row_size(p, t, p.cls[t]);
     if (o.ego) o.ego[at] = (i < (size_t)p.M && r.n_rep) ? ppc_x(p, t, (unsigned)i) : 0u;
     if (o.alter) o.alter[at] = (j < (size_t)p.M && r.n_rep) ? ppc_x(p, t, (unsigned)j) : 0u;
   }
-}
-
-static unsigned grid_for(size_t n, size_t per, size_t cap) { return (unsigned)std::max<size_t>(1, std::min<size_t>(cap, (n + per - 1) / per)); }
-
-static int lanes_for(size_t longest) {
-  int G = 1;
-  while (G < 64 && (size_t)G < longest) G <<= 1;
-  return G;
-}
-
-// lanes per tie, as group_lanes of ppc.hip sizes them -- up to the row's reporters -- but no more than the row gives work to: dense
-// tiles one lane per 16-byte chunk, report lists twice the mean row of the index (a longer row takes more rounds)
-static int et_lanes(const vmr_ctx* h) {
-  const Geo& g = h->g;
-  if (!h->sparse) return lanes_for((size_t)g.Mp / 16);
-  const size_t ties = (size_t)g.L * g.N * g.N;
-  const size_t mean2 = ties ? (size_t)((2 * h->nnz + ties - 1) / ties) : 1;
-  return lanes_for(std::min<size_t>((size_t)g.M, std::max<size_t>(1, mean2)));
 }
 
 static int et_check(vmr_ctx* h, int method, int select, int layer, const char* fn) {
@@ -182,7 +143,8 @@ static int et_layer(vmr_ctx* h, Tmp& tm, int l, int method, double threshold, in
   size_t tb = 0;
   if ((rc = tm.get(&rec, (T + 1) * sizeof(EtRec), "the ties' records")) || (rc = tm.get(&off, (T + 1) * 4, "the rows' offsets"))) return rc;
   *rec_out = rec; *off_out = off;
-  const int G = et_lanes(h);
+  // lanes per tie: no more than the row gives work to -- dense tiles one lane per 16-byte chunk, report lists index_lanes
+  const int G = h->sparse ? index_lanes(h) : pow2_lanes((size_t)h->g.Mp / 16);
   hipLaunchKernelGGL(k_et_tie, dim3(grid_for((T + 1) * G, 256, 65536)), dim3(256), 0, h->stream, lp.p, G, method, threshold, select, rec);
   HIPCHK(h, hipGetLastError());
   hipcub::TransformInputIterator<unsigned, EtFlag, const EtRec*> flags(rec, EtFlag());

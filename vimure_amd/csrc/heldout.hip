@@ -16,13 +16,10 @@
 //                The mean is added in ascending k all the same (the products travel to every lane by shuffles).
 // Both write logp and mean per entry and reduce four doubles and four counts per workgroup: a workgroup owns HO_CHUNK
 // consecutive entries of the segment, a thread adds its entries in order, the waves fold by shuffles, the workgroup by
-// block_sum_n, and k_ho_finish adds a layer's per-workgroup partials in a fixed order.  The tree's shape depends on the segment
+// block_sum_n, and k_lik_finish adds a layer's per-workgroup partials in a fixed order.  The tree's shape depends on the segment
 // length alone; there is no floating-point atomic and no ticket: the results are bit-identical from run to run.
 // lgamma(x + 1): a table of the host's lgamma for x < HO_LGT, Stirling's series beyond (the library's device lgamma costs scratch).
 // An entry whose subscripts are out of range or whose counts are negative sets a flag, reads nothing and adds nothing.
-#include "vmr_internal.h"
-#include "ppc_layer.h"
-#include "rho_row.h"
 #include "report_lik.h"
 
 namespace {
@@ -31,14 +28,12 @@ namespace {
 #define HO_CHUNK 1024   // entries of a workgroup
 #define HO_G 16         // lanes of an entry's group (K > KMAX)
 
-// flag bits
-#define HO_BAD_NAN 1
+// flag bits (LIK_BAD_NAN is bit 1)
 #define HO_BAD_SUB 4
 #define HO_BAD_NEG 8
 #define HO_BAD_LAYER 16
 
-typedef unsigned long long u64;
-static_assert(VMR_HO_NSUM == VMR_HO_NCOUNT, "HoAcc is cleared by one loop");
+static_assert(VMR_HO_NSUM == LIK_N && VMR_HO_NCOUNT == LIK_N && HO_TPB == LIK_TPB, "LikAcc, k_lik_finish");
 
 struct HoIn {
   const int32_t *el, *ei, *ej, *em, *ex, *ext;   // ext may be null: no mirrored count
@@ -48,11 +43,6 @@ struct HoOut {
   double *logp, *mean;     // [n], either may be null
   double* part;            // [workgroups of the layer][VMR_HO_NSUM]
   u64* cpart;              // [workgroups of the layer][VMR_HO_NCOUNT]
-};
-
-struct HoAcc {
-  double s[VMR_HO_NSUM];
-  u64 c[VMR_HO_NCOUNT];
 };
 
 // The subscripts of entry e, checked: false (and a flag) where the entry may not be read.
@@ -68,46 +58,6 @@ __device__ __forceinline__ bool ho_entry(const PpcLayer& p, const HoIn& in, size
   return f == 0;
 }
 
-__device__ __forceinline__ void ho_take(HoAcc& a, double lp, double mn, int x, bool in_mask, int* __restrict__ bad) {
-  if (lp != lp || mn != mn) atomicOr(bad, HO_BAD_NAN);
-  const double xd = (double)x, d = xd - mn;
-  if (lp == -INFINITY) a.c[2] += 1ull; else a.s[0] += lp;
-  a.s[1] += d * d;
-  a.s[2] += xd;
-  a.s[3] += mn;
-  a.c[0] += 1ull;
-  a.c[1] += x > 0 ? 1ull : 0ull;
-  a.c[3] += in_mask ? 1ull : 0ull;
-}
-
-__device__ __forceinline__ u64 ho_block_sum_u(u64 v, u64* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += (u64)__shfl_xor((long long)v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  u64 r = 0;
-  if (threadIdx.x == 0)
-    for (unsigned w = 0; w < (blockDim.x >> 6); ++w) r += red[w];
-  return r;
-}
-
-// the workgroup's partials (every thread calls it)
-__device__ __forceinline__ void ho_flush(const HoAcc& a, const HoOut& o, double* red, u64* redu) {
-#pragma unroll
-  for (int c = 0; c < VMR_HO_NSUM; ++c) {
-    const double t = block_sum_n(a.s[c], red);
-    if (threadIdx.x == 0) o.part[(size_t)blockIdx.x * VMR_HO_NSUM + c] = t;
-  }
-#pragma unroll
-  for (int c = 0; c < VMR_HO_NCOUNT; ++c) {
-    const u64 t = ho_block_sum_u(a.c[c], redu);
-    if (threadIdx.x == 0) o.cpart[(size_t)blockIdx.x * VMR_HO_NCOUNT + c] = t;
-  }
-}
-
-__device__ __forceinline__ const double* ho_row(const PpcLayer& p, size_t t) { return p.rho + (p.inv ? (size_t)p.inv[t] : t) * p.K; }
-
 // K <= KMAX: a lane per entry of the segment [s0, s0 + ns).  th [M], la [K]: the layer's rows of the caller's tables.
 template <bool K2>
 __global__ __launch_bounds__(HO_TPB) void k_ho_lane(PpcLayer p, HoIn in, size_t s0, size_t ns, const double* __restrict__ th,
@@ -115,10 +65,7 @@ __global__ __launch_bounds__(HO_TPB) void k_ho_lane(PpcLayer p, HoIn in, size_t 
                                                     int* __restrict__ bad) {
   __shared__ double red[16];
   __shared__ u64 redu[16];
-  const int K = K2 ? 2 : p.K;
-  HoAcc a;
-#pragma unroll
-  for (int c = 0; c < VMR_HO_NSUM; ++c) { a.s[c] = 0.0; a.c[c] = 0ull; }
+  LikAcc a;
   const size_t base = (size_t)blockIdx.x * HO_CHUNK;
   for (int rd = 0; rd < HO_CHUNK / HO_TPB; ++rd) {
     const size_t q = base + (size_t)rd * HO_TPB + threadIdx.x;
@@ -128,40 +75,15 @@ __global__ __launch_bounds__(HO_TPB) void k_ho_lane(PpcLayer p, HoIn in, size_t 
     double lp = 0.0, mn = 0.0;
     if (ho_entry(p, in, e, i, j, m, x, xt, bad)) {
       const size_t t = (size_t)i * p.N + j;
-      const double* row = ho_row(p, t);
-      double r[KMAX], b[KMAX];
-      if (K2) {
-        const double2 v = *reinterpret_cast<const double2*>(row);   // (rho is 256-byte aligned, a row of two doubles 16-byte)
-        r[0] = v.x; r[1] = v.y;
-      } else {
-#pragma unroll
-        for (int k = 0; k < KMAX; ++k) if (k < K) r[k] = row[k];
-      }
-      const double thm = th[m], exy = eta * (double)xt, xd = (double)x;
-      double mx = -INFINITY;
-      bool nan_seen = false;
-#pragma unroll
-      for (int k = 0; k < KMAX; ++k)
-        if (k < K) {
-          const double mu = ho_rate(thm, la[k], exy);
-          mn = ho_add(mn, ho_mul(r[k], mu));
-          b[k] = ho_term(r[k], mu, xd, x > 0);
-          nan_seen = nan_seen || b[k] != b[k];
-          if (b[k] > mx) mx = b[k];
-        }
-      double s = 0.0;
-#pragma unroll
-      for (int k = 0; k < KMAX; ++k)
-        if (k < K && b[k] > -INFINITY) s += exp(b[k] - mx);
-      if (nan_seen) s = __builtin_nan("");
-      lp = ho_logp(mx, s, ho_lgam1((unsigned)x, lgt));
+      const double* row = tie_rho(p, t);
+      lik_eval_lane<(K2 ? 2 : 0)>(p.K, row, th[m], la, eta, x, xt, lgt, lp, mn);
       const bool inm = row_has(mask_row(p.cls, p.Rb, p.rq, p.Rm, p.W, t), (unsigned)m);
-      ho_take(a, lp, mn, x, inm, bad);
+      LIK_TAKE(a, lp, mn, x, inm, bad);
     }
     if (o.logp) o.logp[e] = lp;
     if (o.mean) o.mean[e] = mn;
   }
-  ho_flush(a, o, red, redu);
+  lik_flush(a, o.part, o.cpart, red, redu);
 }
 
 // K > KMAX: HO_G lanes per entry
@@ -171,9 +93,7 @@ __global__ __launch_bounds__(HO_TPB) void k_ho_group(PpcLayer p, HoIn in, size_t
   __shared__ double red[16];
   __shared__ u64 redu[16];
   const int K = p.K, lane = threadIdx.x & 63, gl = lane & (HO_G - 1), g0 = lane - gl;
-  HoAcc a;
-#pragma unroll
-  for (int c = 0; c < VMR_HO_NSUM; ++c) { a.s[c] = 0.0; a.c[c] = 0ull; }
+  LikAcc a;
   const size_t base = (size_t)blockIdx.x * HO_CHUNK;
   const int gpb = HO_TPB / HO_G;
   for (int rd = 0; rd < HO_CHUNK / gpb; ++rd) {
@@ -185,7 +105,7 @@ __global__ __launch_bounds__(HO_TPB) void k_ho_group(PpcLayer p, HoIn in, size_t
     const bool ok = ho_entry(p, in, e, i, j, m, x, xt, gl == 0 ? bad : nullptr);
     if (ok) {
       const size_t t = (size_t)i * p.N + j;
-      const double* row = ho_row(p, t);
+      const double* row = tie_rho(p, t);
       const double thm = th[m], exy = eta * (double)xt, xd = (double)x;
       double mx = -INFINITY, s = 0.0;
       for (int k0 = 0; k0 < K; k0 += HO_G) {
@@ -209,7 +129,7 @@ __global__ __launch_bounds__(HO_TPB) void k_ho_group(PpcLayer p, HoIn in, size_t
       lp = ho_logp(mx, s, ho_lgam1((unsigned)x, lgt));
       if (gl == 0) {
         const bool inm = row_has(mask_row(p.cls, p.Rb, p.rq, p.Rm, p.W, t), (unsigned)m);
-        ho_take(a, lp, mn, x, inm, bad);
+        LIK_TAKE(a, lp, mn, x, inm, bad);
       }
     }
     if (gl == 0) {
@@ -217,26 +137,7 @@ __global__ __launch_bounds__(HO_TPB) void k_ho_group(PpcLayer p, HoIn in, size_t
       if (o.mean) o.mean[e] = mn;
     }
   }
-  ho_flush(a, o, red, redu);
-}
-
-// second stage: one workgroup adds a layer's nb partials, column by column, in a fixed order
-__global__ __launch_bounds__(HO_TPB) void k_ho_finish(const double* __restrict__ part, const u64* __restrict__ cpart, size_t nb,
-                                                      double* __restrict__ sums, u64* __restrict__ counts) {
-  __shared__ double red[16];
-  __shared__ u64 redu[16];
-  for (int c = 0; c < VMR_HO_NSUM; ++c) {
-    double v = 0.0;
-    for (size_t b = threadIdx.x; b < nb; b += HO_TPB) v += part[b * VMR_HO_NSUM + c];
-    const double t = block_sum_n(v, red);
-    if (threadIdx.x == 0) sums[c] = t;
-  }
-  for (int c = 0; c < VMR_HO_NCOUNT; ++c) {
-    u64 v = 0;
-    for (size_t b = threadIdx.x; b < nb; b += HO_TPB) v += cpart[b * VMR_HO_NCOUNT + c];
-    const u64 t = ho_block_sum_u(v, redu);
-    if (threadIdx.x == 0) counts[c] = t;
-  }
+  lik_flush(a, o.part, o.cpart, red, redu);
 }
 
 // el in [0, L) and non-decreasing; seg[l] = the first entry of a layer >= l (seg[L] = n).  Every seg entry is written exactly once
@@ -257,12 +158,6 @@ __global__ __launch_bounds__(HO_TPB) void k_ho_check(const int32_t* __restrict__
   }
 }
 
-static bool ho_table_ok(const double* v, size_t n) {
-  for (size_t q = 0; q < n; ++q)
-    if (!(v[q] >= 0.0 && v[q] <= 1.79769313486231570815e308)) return false;
-  return true;
-}
-
 }  // namespace
 
 extern "C" int vmr_heldout_loglik(vmr_handle h, uint64_t n, const int32_t* el, const int32_t* ei, const int32_t* ej, const int32_t* em,
@@ -275,9 +170,9 @@ extern "C" int vmr_heldout_loglik(vmr_handle h, uint64_t n, const int32_t* el, c
   if (!theta || !lambda) return fail(h, VMR_EINVAL, "vmr_heldout_loglik: theta or lambda is NULL");
   const Geo& g = h->g;
   const int L = g.L, M = g.M, K = g.K;
-  if (!ho_table_ok(theta, (size_t)L * M)) return fail(h, VMR_EINVAL, "vmr_heldout_loglik: theta must be finite and non-negative");
-  if (!ho_table_ok(lambda, (size_t)L * K)) return fail(h, VMR_EINVAL, "vmr_heldout_loglik: lambda must be finite and non-negative");
-  if (!ho_table_ok(&eta, 1)) return fail(h, VMR_EINVAL, "vmr_heldout_loglik: eta must be finite and non-negative");
+  if (!table_nonneg(theta, (size_t)L * M)) return fail(h, VMR_EINVAL, "vmr_heldout_loglik: theta must be finite and non-negative");
+  if (!table_nonneg(lambda, (size_t)L * K)) return fail(h, VMR_EINVAL, "vmr_heldout_loglik: lambda must be finite and non-negative");
+  if (!table_nonneg(&eta, 1)) return fail(h, VMR_EINVAL, "vmr_heldout_loglik: eta must be finite and non-negative");
   if (!h->have_state) return fail(h, VMR_ESTATE, "vmr_set_state must be called before vmr_heldout_loglik");
   const size_t T = (size_t)g.N * g.N;
   if (T >= 0x7fffffffull) return fail(h, VMR_EINVAL, "vmr_heldout_loglik: 2^31 ties or more in one layer");
@@ -354,7 +249,7 @@ extern "C" int vmr_heldout_loglik(vmr_handle h, uint64_t n, const int32_t* el, c
     else if (K <= KMAX) hipLaunchKernelGGL(k_ho_lane<false>, dim3((unsigned)nb), dim3(HO_TPB), 0, h->stream, lp.p, in, s0, ns, th_l, la_l, eta, lgt, o, bad);
     else hipLaunchKernelGGL(k_ho_group, dim3((unsigned)nb), dim3(HO_TPB), 0, h->stream, lp.p, in, s0, ns, th_l, la_l, eta, lgt, o, bad);
     HIPCHK(h, hipGetLastError());
-    hipLaunchKernelGGL(k_ho_finish, dim3(1), dim3(HO_TPB), 0, h->stream, (const double*)o.part, (const u64*)o.cpart, nb,
+    hipLaunchKernelGGL(k_lik_finish, dim3(1), dim3(HO_TPB), 0, h->stream, (const double*)o.part, (const u64*)o.cpart, nb,
                        sums_d + (size_t)l * VMR_HO_NSUM, counts_d + (size_t)l * VMR_HO_NCOUNT);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -371,6 +266,6 @@ extern "C" int vmr_heldout_loglik(vmr_handle h, uint64_t n, const int32_t* el, c
   if (sums) HIPCHK(h, hipMemcpyAsync(sums, sums_d, (size_t)L * VMR_HO_NSUM * 8, hipMemcpyDeviceToHost, h->stream));
   if (counts) HIPCHK(h, hipMemcpyAsync(counts, counts_d, (size_t)L * VMR_HO_NCOUNT * 8, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (b & HO_BAD_NAN) return fail(h, VMR_ENAN, "vmr_heldout_loglik: a logp or a mean is NaN");
+  if (b & LIK_BAD_NAN) return fail(h, VMR_ENAN, "vmr_heldout_loglik: a logp or a mean is NaN");
   return VMR_OK;
 }

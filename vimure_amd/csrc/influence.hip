@@ -4,23 +4,18 @@
 //
 // The CAVI update of a tie's row is additive over the reporters of its mask: log rho_k = logpr_k + sum_m c_mk + const.  Dividing
 // reporter m's factor exp(c_mk) out of the current row and normalising again gives the row the update would have produced without
-// that reporter's word -- closed form, no refit.  The walk is k_rs_walk's (report_scores.hip); only the arithmetic per element and
-// what is reduced are new:
-//   k_inf_walk<.., FILL = false>  the count pass.  A group of G lanes per tie takes the tie's support reporters in ascending m, G at
-//                 a time: x, xt, the tie's rho row, the leave-one-out row q, and from it prob_loo, tv and the readout of q.
-//                 Every element goes into its reporter's six integer bins (n_scope, lost, gained, flagged, and tv and the shift
-//                 prob_loo - prob in fixed point) and into the histogram of tv -- LDS bins, flushed once per workgroup by integer
-//                 atomics; global integer atomics where they do not fit -- a flagged element into the tie's flagged count cnt[t].
-//   (scan)        exclusive 64-bit sum of cnt: a tie's first row.
-//   k_inf_walk<.., FILL = true>   the fill pass, only when rows are asked for and only over ties that hold one: the same walk, a
-//                 flagged element written at its tie's offset plus its ballot rank inside the group -- lexicographic order, no atomics.
+// that reporter's word -- closed form, no refit.  The walk and its count-and-fill driver are the shared ones (read_side.h:
+// support_walk, walk_count_fill); the arithmetic per element and what is reduced are this unit's:
+//   k_inf_walk<.., FILL = false>  the count pass.  Per tie prob and the readout of its row; per support element the leave-one-out
+//                 row q, and from it prob_loo, tv and the readout of q.  Every element goes into its reporter's six integer bins
+//                 (n_scope, lost, gained, flagged, and tv and the shift prob_loo - prob in fixed point) and into the histogram of
+//                 tv -- LDS bins, flushed once per workgroup by integer atomics; global integer atomics where they do not fit.
+//   k_inf_walk<.., FILL = true>   the fill pass: prob, prob_loo and tv of the flagged elements beside the walk's six integer columns.
 // Determinism: every accumulator is a 64-bit integer; the two sums are signed fixed point in 2^-(61 - b), b = ceil(log2 N^2) (the
 // route of reporter_table.hip).  Integer adds commute; there is no floating-point atomic and no ticket.
 // K = 2 and K <= KMAX keep the row and the exponents in registers; K > KMAX streams the row three times (maximum, sum, values)
 // and forms every exponent again each time by the same operations, so the three variants give the same bits.
-#include "vmr_internal.h"
-#include "ppc_layer.h"
-#include "rho_row.h"
+#include "read_side.h"
 
 namespace {
 
@@ -29,12 +24,8 @@ namespace {
 #define INF_NB 6              // bins per reporter: n_scope, lost, gained, flagged, sum tv, sum shift (fixed point)
 #define INF_LDS_MAX (128u << 10)   // dynamic LDS of the count pass at most (gfx950: 160 KB per workgroup)
 
-// flag bits
-#define INF_BAD_NAN 1
-#define INF_BAD_WALK 2
-#define INF_BAD_RANGE 4
+#define INF_BAD_RANGE 4       // flag bit, beside the walk's
 
-typedef unsigned long long u64;
 static_assert(VMR_INF_NCOUNT == 4 && VMR_INF_NSUM == 2, "the bins of k_inf_walk");
 
 struct InfArgs {
@@ -160,16 +151,9 @@ __device__ __forceinline__ InfVal inf_eval_wide(int K, const double* __restrict_
   return o;
 }
 
-// c = #{tau : edges[tau] <= s} (rs_bin of report_scores.hip); a NaN lands in bin 0 (the call then ends in VMR_ENAN)
-__device__ __forceinline__ int inf_bin(const double* __restrict__ edges, int n, double s) {
-  int a = 0, b = n;
-  while (a < b) { const int c = a + ((b - a) >> 1); if (edges[c] <= s) a = c + 1; else b = c; }
-  return a;
-}
-
 // v, |v| <= 2, as a signed multiple of 2^-sh; NaN and values out of range are flagged and add nothing
 __device__ __forceinline__ u64 inf_fx(double v, int sh, int* __restrict__ bad) {
-  if (!(fabs(v) <= 2.0)) { atomicOr(bad, v != v ? INF_BAD_NAN : INF_BAD_RANGE); return 0ull; }
+  if (!(fabs(v) <= 2.0)) { atomicOr(bad, v != v ? WALK_BAD_NAN : INF_BAD_RANGE); return 0ull; }
   return det_fx(v, sh);
 }
 
@@ -177,63 +161,31 @@ __device__ __forceinline__ u64 inf_fx(double v, int sh, int* __restrict__ bad) {
 template <int KC, bool FILL>
 __global__ __launch_bounds__(INF_TPB) void k_inf_walk(PpcLayer p, int G, InfArgs a) {
   extern __shared__ u64 inf_lds[];   // count pass: [M][INF_NB] reporters' bins (bins_lds), then [n_edges + 1][2] histogram (hist_lds)
-  u64* const lds_rep = inf_lds;
-  u64* const lds_hist = inf_lds + (a.bins_lds ? (size_t)INF_NB * p.M : 0);
   const int n_hist = a.hist ? 2 * (a.n_edges + 1) : 0, n_rep = INF_NB * p.M;
-  if (!FILL) {
-    const int n_lds = (a.bins_lds ? n_rep : 0) + (a.hist_lds ? n_hist : 0);
-    for (int q = threadIdx.x; q < n_lds; q += INF_TPB) inf_lds[q] = 0ull;
-    __syncthreads();
-  }
-  u64* const o_rep = a.bins_lds ? lds_rep : a.bins;
-  u64* const o_hist = a.hist_lds ? lds_hist : a.hist;
-  const int lane = threadIdx.x & 63, gl = lane & (G - 1), g0 = lane - gl;
-  const u64 gmask = (G == 64 ? ~0ull : ((1ull << G) - 1ull)) << g0, lt = (1ull << lane) - 1ull;
-  const size_t gpb = INF_TPB / G;
-  const bool words = p.rq == nullptr;
-  const size_t t_lim = ((size_t)blockIdx.x + 1) * gpb * INF_SLOTS, t_end = t_lim < p.T ? t_lim : p.T;
-  for (size_t t = (size_t)blockIdx.x * gpb * INF_SLOTS + threadIdx.x / G; t < t_end; t += gpb) {   // (uniform over the group)
-    const int c = p.cls[t];
-    u64 o_t = 0;
-    if (FILL) {
-      o_t = a.cnt[t];
-      if (c == 0 || a.cnt[t + 1] == o_t) continue;   // no row of this tie
-    } else if (c == 0) {
-      continue;                                      // (cnt comes zeroed)
-    }
-    const bool listed = c == 2 && !words, bits = c == 2 && words;
-    const unsigned nc = listed ? p.rq[t + 1] - p.rq[t] : (unsigned)p.M;
-    const unsigned short* lst = listed ? p.Rm + p.rq[t] : nullptr;
-    const size_t i = t / p.N, j = t - i * p.N, tm = j * p.N + i;
-    const double* row = p.rho + (p.inv ? (size_t)p.inv[t] : t) * p.K;
-    // what the tie's own row gives, once per tie: prob and the byte of vmr_readout
-    double prob, mean_unused;
-    rho_row_prob_mean(row, p.K, prob, mean_unused);
-    const unsigned y = a.method == VMR_READ_THRESHOLD ? (row[1] >= a.threshold ? 1u : 0u) : rho_row_argmax(row, p.K);
-    u64 jf = 0;
-    for (unsigned c0 = 0; c0 < nc; c0 += (unsigned)G) {
-      const unsigned q = c0 + (unsigned)gl;
-      const unsigned m = listed ? (q < nc ? (unsigned)lst[q] : 0u) : q;
-      const bool in = q < nc && m < (unsigned)p.M && (!bits || ((p.Rb[t * p.W + (m >> 6)] >> (m & 63)) & 1ull));
-      bool flag = false;
-      int x = 0, xt = 0;
-      InfVal v;
-      v.prob_loo = 0.0; v.tv = 0.0; v.y = 0u;
-      if (in) {
-        x = (int)ppc_x(p, t, m);
-        if (p.mut) xt = (int)ppc_x(p, tm, m);
+  const WalkBins o = walk_bins<FILL>(inf_lds, n_rep, n_hist, a.bins_lds, a.hist_lds, a.bins, a.hist, INF_TPB);
+  double prob = 0.0;
+  unsigned y = 0u;
+  InfVal v;
+  support_walk<FILL, INF_TPB, INF_SLOTS>(
+      p, G, a,
+      [&](const double* row) {   // what the tie's own row gives, once per tie: prob and the byte of vmr_readout
+        double mean_unused;
+        rho_row_prob_mean(row, p.K, prob, mean_unused);
+        y = rho_row_readout(row, p.K, a.method, a.threshold);
+      },
+      [&](const double* row, unsigned m, int x, int xt) {
         if (KC >= 0) v = inf_eval_lane<(KC > 0 ? KC : 0)>(p.K, row, a, m, x, xt);
         else v = inf_eval_wide(p.K, row, a, m, x, xt);
         const bool lost = y > 0u && v.y == 0u, gained = y == 0u && v.y > 0u;
-        flag = (lost && (a.select & VMR_INF_LOST)) || (gained && (a.select & VMR_INF_GAINED)) || v.tv >= a.min_tv;
+        const bool flag = (lost && (a.select & VMR_INF_LOST)) || (gained && (a.select & VMR_INF_GAINED)) || v.tv >= a.min_tv;
         if (!FILL) {
           double shift;
           {
 #pragma clang fp contract(off)
             shift = v.prob_loo - prob;
           }
-          if (prob != prob || v.prob_loo != v.prob_loo || v.tv != v.tv) atomicOr(a.bad, INF_BAD_NAN);
-          u64* b = o_rep + (size_t)m * INF_NB;
+          if (prob != prob || v.prob_loo != v.prob_loo || v.tv != v.tv) atomicOr(a.bad, WALK_BAD_NAN);
+          u64* b = o.rep + (size_t)m * INF_NB;
           atomicAdd(b, 1ull);
           if (lost) atomicAdd(b + 1, 1ull);
           if (gained) atomicAdd(b + 2, 1ull);
@@ -241,76 +193,22 @@ __global__ __launch_bounds__(INF_TPB) void k_inf_walk(PpcLayer p, int G, InfArgs
           const u64 ft = inf_fx(v.tv, a.sh, a.bad), fs = inf_fx(shift, a.sh, a.bad);
           if (ft) atomicAdd(b + 4, ft);
           if (fs) atomicAdd(b + 5, fs);
-          if (o_hist) atomicAdd(o_hist + 2 * (size_t)inf_bin(a.edges, a.n_edges, v.tv) + (x > 0 ? 0 : 1), 1ull);
+          if (o.hist) atomicAdd(o.hist + 2 * (size_t)edge_bin(a.edges, a.n_edges, v.tv) + (x > 0 ? 0 : 1), 1ull);
         }
-      }
-      const u64 bf = __ballot(flag) & gmask;
-      if (FILL && flag) {
-        const u64 at = o_t + jf + (u64)__popcll(bf & lt);
-        if (at >= a.lim) {
-          atomicOr(a.bad, INF_BAD_WALK);   // (the count pass and the fill pass disagree: never written out of bounds)
-        } else {
-          if (a.sl) a.sl[at] = p.l;
-          if (a.si) a.si[at] = (int32_t)i;
-          if (a.sj) a.sj[at] = (int32_t)j;
-          if (a.sm) a.sm[at] = (int32_t)m;
-          if (a.x) a.x[at] = x;
-          if (a.xt) a.xt[at] = xt;
-          if (a.prob) a.prob[at] = prob;
-          if (a.prob_loo) a.prob_loo[at] = v.prob_loo;
-          if (a.tv) a.tv[at] = v.tv;
-        }
-      }
-      jf += (u64)__popcll(bf);
-    }
-    if (!FILL && gl == 0) a.cnt[t] = jf;
-  }
+        return flag;
+      },
+      [&](u64 at) {
+        if (a.prob) a.prob[at] = prob;
+        if (a.prob_loo) a.prob_loo[at] = v.prob_loo;
+        if (a.tv) a.tv[at] = v.tv;
+      });
   if (FILL) return;
-  __syncthreads();
-  if (a.bins_lds)
-    for (int q = threadIdx.x; q < n_rep; q += INF_TPB) { const u64 u = lds_rep[q]; if (u) atomicAdd(a.bins + q, u); }
-  if (a.hist_lds)
-    for (int q = threadIdx.x; q < n_hist; q += INF_TPB) { const u64 u = lds_hist[q]; if (u) atomicAdd(a.hist + q, u); }
-}
-
-static bool inf_nonneg(const double* v, size_t n) {
-  for (size_t q = 0; q < n; ++q)
-    if (!(v[q] >= 0.0 && v[q] <= 1.79769313486231570815e308)) return false;
-  return true;
-}
-
-static bool inf_finite(const double* v, size_t n) {
-  for (size_t q = 0; q < n; ++q)
-    if (!(v[q] >= -1.79769313486231570815e308 && v[q] <= 1.79769313486231570815e308)) return false;
-  return true;
-}
-
-// lanes per tie: a support row holds up to M reporters (rs_lanes of report_scores.hip)
-static int inf_lanes(const vmr_ctx* h) {
-  int G = 1;
-  while (G < 64 && G < h->g.M) G <<= 1;
-  return G;
-}
-
-// smallest b with 2^b >= v
-static int inf_bits(unsigned long long v) {
-  int b = 0;
-  while (b < 63 && (1ull << b) < v) ++b;
-  return b;
+  walk_bins_flush(inf_lds, n_rep, n_hist, a.bins_lds, a.hist_lds, a.bins, a.hist, INF_TPB);
 }
 
 template <bool FILL>
 static int inf_launch(vmr_ctx* h, const PpcLayer& p, int G, const InfArgs& a, unsigned nb, size_t smem) {
-  const int K = p.K;
-  auto go = [&](auto kern) -> int {
-    if (smem > 48 * 1024) HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    hipLaunchKernelGGL(kern, dim3(nb), dim3(INF_TPB), smem, h->stream, p, G, a);
-    HIPCHK(h, hipGetLastError());
-    return VMR_OK;
-  };
-  if (K == 2) return go(k_inf_walk<2, FILL>);
-  if (K <= KMAX) return go(k_inf_walk<0, FILL>);
-  return go(k_inf_walk<-1, FILL>);
+  return launch_by_k(h, p.K, nb, INF_TPB, smem, [](auto kc) { return k_inf_walk<decltype(kc)::value, FILL>; }, p, G, a);
 }
 
 struct InfTables {
@@ -327,22 +225,17 @@ static int inf_run(vmr_ctx* h, const char* fn, int layer, const InfTables& tb, i
   if (!tb.e_theta || !tb.elog_theta || !tb.e_lambda || !tb.elog_lambda) return bad_arg("e_theta, elog_theta, e_lambda or elog_lambda is NULL");
   const Geo& g = h->g;
   const int L = g.L, M = g.M, K = g.K;
-  if (!inf_nonneg(tb.e_theta, (size_t)L * M)) return bad_arg("e_theta must be finite and non-negative");
-  if (!inf_nonneg(tb.e_lambda, (size_t)L * K)) return bad_arg("e_lambda must be finite and non-negative");
-  if (!inf_finite(tb.elog_theta, (size_t)L * M)) return bad_arg("elog_theta must be finite");
-  if (!inf_finite(tb.elog_lambda, (size_t)L * K)) return bad_arg("elog_lambda must be finite");
-  if (!inf_nonneg(&tb.g_nu, 1)) return bad_arg("g_nu must be finite and non-negative");
+  if (!table_nonneg(tb.e_theta, (size_t)L * M)) return bad_arg("e_theta must be finite and non-negative");
+  if (!table_nonneg(tb.e_lambda, (size_t)L * K)) return bad_arg("e_lambda must be finite and non-negative");
+  if (!table_finite(tb.elog_theta, (size_t)L * M)) return bad_arg("elog_theta must be finite");
+  if (!table_finite(tb.elog_lambda, (size_t)L * K)) return bad_arg("elog_lambda must be finite");
+  if (!table_nonneg(&tb.g_nu, 1)) return bad_arg("g_nu must be finite and non-negative");
   if (method != VMR_READ_RHO_MAX && method != VMR_READ_THRESHOLD)
     return bad_arg("the method must be VMR_READ_RHO_MAX or VMR_READ_THRESHOLD (a readout of categories)");
   if (select < 0 || select > 3) return bad_arg("select must be a combination of VMR_INF_LOST and VMR_INF_GAINED (0..3)");
   if (!(min_tv >= 0.0)) return bad_arg("min_tv must lie in [0, +inf]");
   if (layer >= L) return bad_arg("layer out of range");
-  if (n_edges < 0 || n_edges > VMR_INF_MAX_EDGES) return bad_arg("n_edges must lie in [0, VMR_INF_MAX_EDGES]");
-  if (hist && n_edges > 0 && !edges) return bad_arg("hist is asked for and edges is NULL");
-  if (hist)
-    for (int q = 0; q < n_edges; ++q)
-      if (!(edges[q] >= -1.79769313486231570815e308 && edges[q] <= 1.79769313486231570815e308) || (q && edges[q] < edges[q - 1]))
-        return bad_arg("the edges must be finite and non-decreasing");
+  if (const char* why = hist_refusal(hist, n_edges, VMR_INF_MAX_EDGES, "n_edges must lie in [0, VMR_INF_MAX_EDGES]", edges)) return bad_arg(why);
   if (!h->have_state) return fail(h, VMR_ESTATE, (std::string("vmr_set_state must be called before ") + fn).c_str());
   const size_t T = (size_t)g.N * g.N;
   if (T >= 0x7fffffffull) return bad_arg("2^31 ties or more in one layer");
@@ -367,134 +260,62 @@ static int inf_run(vmr_ctx* h, const char* fn, int layer, const InfTables& tb, i
       pl[k] = exp(el); pl[K + k] = el; pl[2 * (size_t)K + k] = tb.e_lambda[(size_t)l * K + k];
     }
   }
-  if (!inf_finite(par_h.data(), o_ed)) return bad_arg("exp(elog_theta) or exp(elog_lambda) overflows");
+  if (!table_finite(par_h.data(), o_ed)) return bad_arg("exp(elog_theta) or exp(elog_lambda) overflows");
   if (n_edges) memcpy(par_h.data() + o_ed, edges, (size_t)n_edges * 8);
 
-  const int G = inf_lanes(h);
-  const size_t per = (size_t)(INF_TPB / G) * INF_SLOTS;
-  const unsigned nb = (unsigned)((T + per - 1) / per);
-  const size_t n_hist = hist ? 2 * ((size_t)n_edges + 1) : 0, n_rep = (size_t)INF_NB * M;
-  const bool rep_lds = M <= PR_HIST_M;
-  const bool hist_lds = hist && ((rep_lds ? n_rep : 0) + n_hist) * 8 <= INF_LDS_MAX;
-  const size_t smem = ((rep_lds ? n_rep : 0) + (hist_lds ? n_hist : 0)) * 8;
-  const int sh = 61 - inf_bits((unsigned long long)T);   // |term| <= 2, at most N^2 of them per reporter: below 2^62
+  const size_t n_rep = (size_t)INF_NB * M;
+  const WalkShape ws = walk_shape(h, INF_TPB, INF_SLOTS, hist != nullptr, n_edges, n_rep, INF_LDS_MAX);
+  const int G = ws.G;
+  const unsigned nb = ws.nb;
+  const size_t n_hist = ws.n_hist, smem = ws.smem;
+  const int sh = 61 - ceil_log2((u64)T);   // |term| <= 2, at most N^2 of them per reporter: below 2^62
 
   Tmp tm(h);
-  int rc;
-  int* bad = nullptr;
+  int rc, b = 0;
   double* par_d = nullptr;
-  u64 *hist_d = nullptr, *rep_d = nullptr, *cnt = nullptr, *off = nullptr;
-  void* ts = nullptr;
-  size_t tbytes = 0;
-  if ((rc = tm.get(&bad, 4, "a flag")) || (rc = tm.get(&par_d, n_par * 8, "the parameter tables")) ||
-      (rc = tm.get(&hist_d, (size_t)Lq * n_hist * 8, "the histogram")) || (rc = tm.get(&rep_d, (size_t)Lq * n_rep * 8, "the reporters' bins")) ||
-      (rc = tm.get(&cnt, (T + 1) * 8, "the ties' flagged counts")))
-    return rc;
-  if (rows) {   // a tie's first row, every layer's: kept until the capacity is checked against all of them
-    if ((rc = tm.get(&off, (size_t)Lq * (T + 1) * 8, "the ties' row offsets"))) return rc;
-    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tbytes, cnt, off, (int)(T + 1), h->stream));
-    if ((rc = tm.get(&ts, tbytes, "the scan of the flagged counts"))) return rc;
-  }
-  HIPCHK(h, hipMemcpyAsync(par_d, par_h.data(), n_par * 8, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemsetAsync(bad, 0, 4, h->stream));
-  if (n_hist) HIPCHK(h, hipMemsetAsync(hist_d, 0, (size_t)Lq * n_hist * 8, h->stream));
-  HIPCHK(h, hipMemsetAsync(rep_d, 0, (size_t)Lq * n_rep * 8, h->stream));
-
+  u64 *hist_d = nullptr, *rep_d = nullptr;
+  std::vector<u64> rep_h((size_t)Lq * n_rep);
   InfArgs a;
   memset(&a, 0, sizeof a);
+  if ((rc = tm.get(&a.bad, 4, "a flag")) || (rc = tm.get(&par_d, n_par * 8, "the parameter tables")) ||
+      (rc = tm.get(&hist_d, (size_t)Lq * n_hist * 8, "the histogram")) || (rc = tm.get(&rep_d, (size_t)Lq * n_rep * 8, "the reporters' bins")))
+    return rc;
+  HIPCHK(h, hipMemcpyAsync(par_d, par_h.data(), n_par * 8, hipMemcpyHostToDevice, h->stream));
+  if (n_hist) HIPCHK(h, hipMemsetAsync(hist_d, 0, (size_t)Lq * n_hist * 8, h->stream));
+  HIPCHK(h, hipMemsetAsync(rep_d, 0, (size_t)Lq * n_rep * 8, h->stream));
+  a.edges = hist ? par_d + o_ed : nullptr;
   a.gnu = g.mut ? tb.g_nu : 0.0;
   a.threshold = threshold; a.min_tv = min_tv; a.method = method; a.select = select; a.n_edges = n_edges; a.sh = sh;
-  a.edges = hist ? par_d + o_ed : nullptr;
-  a.hist_lds = hist_lds; a.bins_lds = rep_lds;
-  a.bad = bad;
+  a.hist_lds = ws.hist_lds; a.bins_lds = ws.rep_lds;
   auto tables = [&](int l) {
     a.gth = par_d + (size_t)l * 3 * M; a.elt = a.gth + M; a.eth = a.elt + M;
     a.gla = par_d + o_la + (size_t)l * 3 * K; a.ell = a.gla + K; a.ela = a.ell + K;
   };
-
-  // the count pass, layer by layer
-  for (int l = l0; l < l1; ++l) {
-    LayerPrep lp;
-    if ((rc = ppc_prep_layer(h, tm, l, false, true, lp, true, false))) return rc;
-    tables(l);
-    a.hist = hist ? hist_d + (size_t)(l - l0) * n_hist : nullptr;
-    a.bins = rep_d + (size_t)(l - l0) * n_rep;
-    a.cnt = cnt;
-    HIPCHK(h, hipMemsetAsync(cnt, 0, (T + 1) * 8, h->stream));
-    if ((rc = inf_launch<false>(h, lp.p, G, a, nb, smem))) return rc;
-    if (rows) HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(ts, tbytes, cnt, off + (size_t)(l - l0) * (T + 1), (int)(T + 1), h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    ppc_release_layer(tm, lp);
-  }
-  std::vector<u64> rep_h((size_t)Lq * n_rep);
-  int b = 0;
-  HIPCHK(h, hipMemcpyAsync(rep_h.data(), rep_d, rep_h.size() * 8, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(&b, bad, 4, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  std::vector<u64> flagged((size_t)Lq, 0ull);
-  u64 total = 0;
-  for (int q = 0; q < Lq; ++q) {
-    for (int m = 0; m < M; ++m) flagged[q] += rep_h[((size_t)q * M + m) * INF_NB + 3];
-    total += flagged[q];
-  }
-  if (b & INF_BAD_NAN) return fail(h, VMR_ENAN, (std::string(fn) + ": a leave-one-out value is NaN").c_str());
-  if (b & INF_BAD_RANGE)
-    return fail(h, VMR_EINVAL, (std::string(fn) + ": a row of rho sums to more than 2 (the fixed point of the sums is sized for normalised rows)").c_str());
-  if (n_out) *n_out = total;
-  if (rows && n < total) {
-    char msg[200];
-    snprintf(msg, sizeof msg, "%s: the table holds %llu rows, %llu elements are flagged", fn, (unsigned long long)n, (unsigned long long)total);
-    return fail(h, VMR_EINVAL, msg);
-  }
-
-  // the fill pass: the layers that hold a row
-  if (rows && total) {
-    u64 base = 0;
-    for (int l = l0; l < l1; ++l) {
-      const u64 nl = flagged[l - l0];
-      if (!nl) continue;
-      LayerPrep lp;
-      if ((rc = ppc_prep_layer(h, tm, l, false, true, lp, true, false))) return rc;
-      tables(l);
-      a.hist = nullptr; a.bins = nullptr; a.edges = nullptr; a.n_edges = 0; a.hist_lds = 0; a.bins_lds = 0;
-      a.cnt = off + (size_t)(l - l0) * (T + 1);
-      a.lim = nl;
-      int32_t* d32[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-      double* d64[3] = {nullptr, nullptr, nullptr};
-      int32_t* st32 = nullptr;
-      double* st64 = nullptr;
-      if (out_on_device) {
-        for (int q = 0; q < 6; ++q) d32[q] = sub[q] ? sub[q] + base : nullptr;
-        for (int q = 0; q < 3; ++q) d64[q] = dbl[q] ? dbl[q] + base : nullptr;
-      } else {   // host outputs: the layer's rows through device staging
-        int n32 = 0, n64 = 0;
-        for (int q = 0; q < 6; ++q) n32 += sub[q] != nullptr;
-        for (int q = 0; q < 3; ++q) n64 += dbl[q] != nullptr;
-        if ((n32 && (rc = tm.get(&st32, (size_t)n32 * nl * 4, "the staging of the rows"))) ||
-            (n64 && (rc = tm.get(&st64, (size_t)n64 * nl * 8, "the staging of the rows"))))
-          return rc;
-        for (int q = 0, u = 0; q < 6; ++q) if (sub[q]) d32[q] = st32 + (size_t)(u++) * nl;
-        for (int q = 0, u = 0; q < 3; ++q) if (dbl[q]) d64[q] = st64 + (size_t)(u++) * nl;
-      }
-      a.sl = d32[0]; a.si = d32[1]; a.sj = d32[2]; a.sm = d32[3]; a.x = d32[4]; a.xt = d32[5];
-      a.prob = d64[0]; a.prob_loo = d64[1]; a.tv = d64[2];
-      if ((rc = inf_launch<true>(h, lp.p, G, a, nb, 0))) return rc;
-      if (!out_on_device) {
-        for (int q = 0; q < 6; ++q)
-          if (sub[q]) HIPCHK(h, hipMemcpyAsync(sub[q] + base, d32[q], (size_t)nl * 4, hipMemcpyDeviceToHost, h->stream));
-        for (int q = 0; q < 3; ++q)
-          if (dbl[q]) HIPCHK(h, hipMemcpyAsync(dbl[q] + base, d64[q], (size_t)nl * 8, hipMemcpyDeviceToHost, h->stream));
-      }
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-      if (st32) tm.release(st32);
-      if (st64) tm.release(st64);
-      ppc_release_layer(tm, lp);
-      base += nl;
-    }
-    HIPCHK(h, hipMemcpyAsync(&b, bad, 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (b & INF_BAD_WALK) return fail(h, VMR_EHIP, (std::string(fn) + ": the count pass and the fill pass disagree").c_str());
-  }
+  const WalkTable w = {rows, n, sub, dbl, 3, out_on_device, n_out};
+  rc = walk_count_fill(
+      h, fn, tm, l0, l1, w, a, b,
+      [&](int l, const PpcLayer& p) -> int {
+        tables(l);
+        a.hist = hist ? hist_d + (size_t)(l - l0) * n_hist : nullptr;
+        a.bins = rep_d + (size_t)(l - l0) * n_rep;
+        return inf_launch<false>(h, p, G, a, nb, smem);
+      },
+      [&](u64* flagged) -> int {
+        HIPCHK(h, hipMemcpy(rep_h.data(), rep_d, rep_h.size() * 8, hipMemcpyDeviceToHost));
+        for (int q = 0; q < Lq; ++q)
+          for (int m = 0; m < M; ++m) flagged[q] += rep_h[((size_t)q * M + m) * INF_NB + 3];
+        if (b & WALK_BAD_NAN) return fail(h, VMR_ENAN, (std::string(fn) + ": a leave-one-out value is NaN").c_str());
+        if (b & INF_BAD_RANGE)
+          return fail(h, VMR_EINVAL, (std::string(fn) + ": a row of rho sums to more than 2 (the fixed point of the sums is sized for normalised rows)").c_str());
+        return VMR_OK;
+      },
+      [&](int l, const PpcLayer& p, double* const* d64) -> int {
+        tables(l);
+        a.hist = nullptr; a.bins = nullptr; a.edges = nullptr; a.n_edges = 0; a.hist_lds = 0; a.bins_lds = 0;
+        a.prob = d64[0]; a.prob_loo = d64[1]; a.tv = d64[2];
+        return inf_launch<true>(h, p, G, a, nb, 0);
+      });
+  if (rc) return rc;
   if (hist) HIPCHK(h, hipMemcpyAsync(hist, hist_d, (size_t)Lq * n_hist * 8, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   for (size_t r = 0; r < (size_t)Lq * M; ++r) {

@@ -19,8 +19,7 @@
 // uint64 keys), the negatives' come in chunks of ties sized to free memory and hipcub's int item count; each chunk is sorted (a
 // wave's binary searches then share cache lines) and every negative adds 2 #(pos > s) + #(pos = s), summed in uint64 -- exact,
 // order-free, the same from run to run.
-#include "vmr_internal.h"
-#include "ppc_layer.h"
+#include "read_side.h"
 
 namespace {
 
@@ -31,27 +30,18 @@ namespace {
 
 // the score in the reference's order and roundings: PoissonMean_k = theta_m lambda_k + nu XT, then sum_k rho_k PoissonMean_k,
 // k ascending, every product and sum rounded on its own (no contraction to FMA: the AUC counts exact ties, and a value one ulp
-// off the reference's would split a tie it has)
+// off the reference's would split a tie it has).  The pragma is what holds the compiler to that: __dmul_rn / __dadd_rn are inlined
+// header code and were contracted to v_fma_f64 / v_fmac_f64 all the same (rho_row.h's convention and its reason).
 __device__ __forceinline__ double ppc_score(const PpcLayer& p, const double* __restrict__ r, unsigned m, unsigned xt) {
-  const double gt = p.gth[m], nx = __dmul_rn(*p.gnu, (double)xt);
+#pragma clang fp contract(off)
+  const double gt = p.gth[m], nx = *p.gnu * (double)xt;
   double s = 0.0;
-  for (int k = 0; k < p.K; ++k) s = __dadd_rn(s, __dmul_rn(r[k], __dadd_rn(__dmul_rn(gt, p.gla[k]), nx)));
-  return s;
-}
-
-// order-preserving key of a double (-0 as +0): equal keys <=> equal values
-__device__ __forceinline__ unsigned long long ppc_okey(double v) {
-  const unsigned long long u = (unsigned long long)__double_as_longlong(v + 0.0);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-
-// support size of a tie's mask row
-__device__ __forceinline__ unsigned ppc_row_size(const PpcLayer& p, size_t t, int c) {
-  if (c == 1) return (unsigned)p.M;
-  if (c != 2) return 0u;
-  if (p.rq) return p.rq[t + 1] - p.rq[t];
-  unsigned s = 0;
-  for (int w = 0; w < p.W; ++w) s += (unsigned)__popcll(p.Rb[t * p.W + w]);
+  for (int k = 0; k < p.K; ++k) {
+    const double a = gt * p.gla[k];
+    const double mu = a + nx;
+    const double t = r[k] * mu;
+    s = s + t;
+  }
   return s;
 }
 
@@ -60,7 +50,7 @@ __global__ __launch_bounds__(256) void k_ppc_count(PpcLayer p, unsigned long lon
   for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t <= p.T; t += (size_t)gridDim.x * 256) {
     if (t == p.T) { sup[t] = 0; if (pc) pc[t] = 0; continue; }
     const int c = p.cls[t];
-    sup[t] = ppc_row_size(p, t, c);
+    sup[t] = mask_row_size(p, t, c);
     if (!pc) continue;
     unsigned long long n = 0;
     if (c != 0) {
@@ -117,7 +107,8 @@ __global__ __launch_bounds__(256) void k_ppc_inv(const unsigned* __restrict__ pe
   }
 }
 
-// The walk: a group of G lanes per tie of [t0, t1) takes the tie's support reporters in ascending m, G at a time.
+// The walk: a group of G lanes per tie of [t0, t1) takes the tie's support reporters in ascending m, G at a time (the per-tie
+// set-up and the per-lane reporter of read_side.h's support walk; the loop is its own: a window of ties, grid-stride, two ranks).
 //   WRITE: subs (any pointer may be null) and vals at off[t] + rank - obase
 //   POS:   keys of the positives at poff[t] + positive rank - obase
 //   NEG:   keys of the negatives at off[t] - poff[t] + negative rank - obase
@@ -127,35 +118,28 @@ __global__ __launch_bounds__(256) void k_ppc_walk(PpcLayer p, int G, size_t t0, 
                                                   int32_t* __restrict__ sl,
                                                   int32_t* __restrict__ si, int32_t* __restrict__ sj, int32_t* __restrict__ sm,
                                                   double* __restrict__ vals, unsigned long long* __restrict__ keys, int* __restrict__ bad) {
-  const int lane = threadIdx.x & 63, gl = lane & (G - 1), g0 = lane - gl;
-  const unsigned long long gmask = (G == 64 ? ~0ull : ((1ull << G) - 1ull)) << g0, lt = (1ull << lane) - 1ull;
+  const WalkGroup g = walk_group(G);
   const size_t gpb = 256 / G, ngr = (size_t)gridDim.x * gpb;
-  const bool words = p.rq == nullptr;
   for (size_t t = t0 + (size_t)blockIdx.x * gpb + threadIdx.x / G; t < t1; t += ngr) {   // (uniform over the group)
     const int c = p.cls[t];
     if (c == 0) continue;
-    const bool listed = c == 2 && !words, bits = c == 2 && words;
-    const unsigned nc = listed ? p.rq[t + 1] - p.rq[t] : (unsigned)p.M;
-    const unsigned short* lst = listed ? p.Rm + p.rq[t] : nullptr;
-    const size_t i = t / p.N, j = t - i * p.N, tm = j * p.N + i;
-    const double* r = p.rho + (p.inv ? (size_t)p.inv[t] : t) * p.K;
+    const WalkTie w = walk_tie(p, t, c);
     unsigned long long js = 0, jp = 0;
     const unsigned long long o_all = off[t], o_pos = (MODE == PPC_MODE_WRITE) ? 0ull : poff[t];
-    for (unsigned c0 = 0; c0 < nc; c0 += (unsigned)G) {
-      const unsigned q = c0 + (unsigned)gl;
-      const unsigned m = listed ? (q < nc ? (unsigned)lst[q] : 0u) : q;
-      const bool in = q < nc && (!bits || ((p.Rb[t * p.W + (m >> 6)] >> (m & 63)) & 1ull));
+    for (unsigned c0 = 0; c0 < w.nc; c0 += (unsigned)G) {
+      unsigned m;
+      const bool in = walk_reporter(p, w, t, c0 + (unsigned)g.gl, m);
       unsigned x = 0, xt = 0;
       if (in) {
         if (MODE != PPC_MODE_WRITE) x = ppc_x(p, t, m);
-        if (p.mut) xt = ppc_x(p, tm, m);
+        if (p.mut) xt = ppc_x(p, w.tm, m);
       }
       const bool pos = in && x != 0u;
-      const unsigned long long bs = __ballot(in) & gmask, bp = __ballot(pos) & gmask;
-      const unsigned long long rk = js + (unsigned long long)__popcll(bs & lt), rp = jp + (unsigned long long)__popcll(bp & lt);
+      const unsigned long long bs = __ballot(in) & g.gmask, bp = __ballot(pos) & g.gmask;
+      const unsigned long long rk = js + (unsigned long long)__popcll(bs & g.lt), rp = jp + (unsigned long long)__popcll(bp & g.lt);
       const bool take = in && (MODE == PPC_MODE_WRITE || (MODE == PPC_MODE_POS) == pos);
       if (take) {
-        const double v = ppc_score(p, r, m, xt);
+        const double v = ppc_score(p, w.row, m, xt);
         if (v != v) atomicOr(bad, 1);
         const unsigned long long at = MODE == PPC_MODE_WRITE ? o_all + rk - obase
                                     : MODE == PPC_MODE_POS ? o_pos + rp - obase : (o_all - o_pos) + (rk - rp) - obase;
@@ -164,11 +148,11 @@ __global__ __launch_bounds__(256) void k_ppc_walk(PpcLayer p, int G, size_t t0, 
         } else if (MODE == PPC_MODE_WRITE) {
           vals[at] = v;
           if (sl) sl[at] = p.l;
-          if (si) si[at] = (int32_t)i;
-          if (sj) sj[at] = (int32_t)j;
+          if (si) si[at] = (int32_t)w.i;
+          if (sj) sj[at] = (int32_t)w.j;
           if (sm) sm[at] = (int32_t)m;
         } else {
-          keys[at] = ppc_okey(v);
+          keys[at] = order_key(v);
         }
       }
       js += (unsigned long long)__popcll(bs);
@@ -190,8 +174,7 @@ __global__ __launch_bounds__(256) void k_ppc_rank(const unsigned long long* __re
     while (u < e) { const unsigned long long c = u + ((e - u) >> 1); if (pos[c] <= s) u = c + 1; else e = c; }
     v += 2ull * (P - u) + (u - a);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += (unsigned long long)__shfl_xor((long long)v, o, 64);
+  v = wave_sum_ull(v);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -199,11 +182,6 @@ __global__ __launch_bounds__(256) void k_ppc_rank(const unsigned long long* __re
     if (s) atomicAdd(acc, s);
   }
 }
-
-// ------------------------------------------------------------------------------------------
-// host side
-// ------------------------------------------------------------------------------------------
-static unsigned grid_for(size_t n, size_t per = 256, size_t cap = 16384) { return (unsigned)std::max<size_t>(1, std::min<size_t>(cap, (n + per - 1) / per)); }
 
 }  // namespace
 
@@ -304,13 +282,6 @@ void ppc_release_layer(Tmp& tm, LayerPrep& lp) {
 
 namespace {
 
-// lanes per tie: a support row holds up to M reporters
-static int group_lanes(const vmr_ctx* h) {
-  int G = 1;
-  while (G < 64 && G < h->g.M) G <<= 1;
-  return G;
-}
-
 // the last tie t1 in (t0, T] with f(t1) - f(t0) <= cap, where f(t) = a[t] - (b ? b[t] : 0) (a row never exceeds M <= cap)
 static int cut_ties(vmr_ctx* h, const unsigned long long* a, const unsigned long long* b, size_t t0, size_t T, unsigned long long cap, size_t* t1) {
   auto f = [&](size_t t, unsigned long long* v) {
@@ -386,7 +357,7 @@ extern "C" int vmr_mean_poisson(vmr_handle h, int layer, uint64_t n, int32_t* sl
   int* bad = nullptr;
   if ((rc = tm.get(&bad, 4, "a flag"))) return rc;
   HIPCHK(h, hipMemsetAsync(bad, 0, 4, h->stream));
-  const int G = group_lanes(h);
+  const int G = pow2_lanes((size_t)h->g.M);
   const size_t T = (size_t)h->g.N * h->g.N;
   unsigned long long base = 0;   // output index of the layer's first value
   for (int l = l0; l < l1; ++l) {
@@ -440,7 +411,7 @@ extern "C" int vmr_report_auc(vmr_handle h, int layer, double* auc, uint64_t* n_
   if (rc) return rc;
   const int l0 = layer < 0 ? 0 : layer, l1 = layer < 0 ? h->g.L : layer + 1;
   const size_t T = (size_t)h->g.N * h->g.N;
-  const int G = group_lanes(h);
+  const int G = pow2_lanes((size_t)h->g.M);
   Tmp tm(h);
   // sizes: positives and support of every layer
   std::vector<unsigned long long> P_l(h->g.L, 0), S_l(h->g.L, 0);

@@ -18,8 +18,7 @@
 // k_obs: a group per ORDERED tie over the tie's own reports -- the dense row, or the tie's entries of the tie-major index of
 // ppc.hip (value x << 1 | R) -- `mutual` looks the mirror report up (dense: the mirror row; lists: binary search in the mirror
 // tie's entries).  A support element without a report adds nothing to any statistic, so the report lists are walked, not S.
-#include "vmr_internal.h"
-#include "ppc_layer.h"
+#include "read_side.h"
 #include "report_draw.h"
 
 namespace {
@@ -46,18 +45,12 @@ __device__ __forceinline__ void flush_stats(unsigned long long (&v)[VMR_PPC_NSTA
                                             unsigned long long* __restrict__ counts, unsigned long long* __restrict__ byrep) {
 #pragma unroll
   for (int k = 0; k < VMR_PPC_NSTAT; ++k) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v[k] += (unsigned long long)__shfl_xor((long long)v[k], o, 64);
+    v[k] = wave_sum_ull(v[k]);
     if ((threadIdx.x & 63) == 0 && v[k]) atomicAdd(&tot[k], v[k]);
   }
   __syncthreads();
   if (threadIdx.x < VMR_PPC_NSTAT && tot[threadIdx.x]) atomicAdd(counts + threadIdx.x, tot[threadIdx.x]);
-  if (HIST && byrep) {
-    for (int q = threadIdx.x; q < 2 * M; q += 256) {
-      const unsigned long long u = hist[q];
-      if (u) atomicAdd(byrep + q, u);
-    }
-  }
+  if (HIST && byrep) flush_bins(hist, byrep, 2 * M, 256);
 }
 
 template <bool HIST>
@@ -73,8 +66,7 @@ __global__ __launch_bounds__(256, 2) void k_rep(RepArgs a) {
   extern __shared__ unsigned long long hist[];   // HIST: [M][2]
   __shared__ unsigned long long tot[VMR_PPC_NSTAT];
   const int l = blockIdx.y, r = blockIdx.z, G = a.G;
-  const int lane = threadIdx.x & 63, gl = lane & (G - 1), g0 = lane - gl;
-  const unsigned long long gmask = (G == 64 ? ~0ull : ((1ull << G) - 1ull)) << g0;
+  const WalkGroup g = walk_group(G);
   const size_t T = (size_t)a.N * a.N, gpb = 256 / G, rl = (size_t)r * a.L + l;
   if (threadIdx.x < VMR_PPC_NSTAT) tot[threadIdx.x] = 0ull;
   if (HIST && a.byrep) for (int q = threadIdx.x; q < 2 * a.M; q += 256) hist[q] = 0ull;
@@ -103,7 +95,7 @@ __global__ __launch_bounds__(256, 2) void k_rep(RepArgs a) {
     const unsigned nc = range ? (unsigned)a.M : A.n + B.n;
     unsigned ca = 0, cb = 0;   // positives of tie (i,j) and of tie (j,i)
     for (unsigned c0 = 0; c0 < nc; c0 += (unsigned)G) {
-      const unsigned q = c0 + (unsigned)gl;
+      const unsigned q = c0 + (unsigned)g.gl;
       bool inA = false, inB = false;
       unsigned m = 0;
       if (q < nc) {
@@ -127,10 +119,10 @@ __global__ __launch_bounds__(256, 2) void k_rep(RepArgs a) {
         if (np == 2u) v[3] += 2ull;
         if (byrep) add_reporter<HIST>(hist, byrep, m, np, tt);
       }
-      ca += (unsigned)__popcll(__ballot(pa) & gmask);
-      cb += (unsigned)__popcll(__ballot(pb) & gmask);
+      ca += (unsigned)__popcll(__ballot(pa) & g.gmask);
+      cb += (unsigned)__popcll(__ballot(pb) & g.gmask);
     }
-    if (gl == 0) {
+    if (g.gl == 0) {
       v[4] += (ca > 0u) + (cb > 0u);
       v[5] += (ca > 1u) + (cb > 1u);
     }
@@ -143,14 +135,12 @@ template <bool HIST>
 __global__ __launch_bounds__(256) void k_obs(PpcLayer p, int G, unsigned long long* __restrict__ counts, unsigned long long* __restrict__ byrep) {
   extern __shared__ unsigned long long hist[];
   __shared__ unsigned long long tot[VMR_PPC_NSTAT];
-  const int lane = threadIdx.x & 63, gl = lane & (G - 1), g0 = lane - gl;
-  const unsigned long long gmask = (G == 64 ? ~0ull : ((1ull << G) - 1ull)) << g0;
+  const WalkGroup g = walk_group(G);
   const size_t gpb = 256 / G;
   if (threadIdx.x < VMR_PPC_NSTAT) tot[threadIdx.x] = 0ull;
   if (HIST && byrep) for (int q = threadIdx.x; q < 2 * p.M; q += 256) hist[q] = 0ull;
   __syncthreads();
   unsigned long long v[VMR_PPC_NSTAT] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
-  const unsigned long long mmask = (1ull << p.mb) - 1ull;
   const size_t t_lim = ((size_t)blockIdx.x + 1) * gpb * PR_SLOTS, t_end = t_lim < p.T ? t_lim : p.T;
   for (size_t t = (size_t)blockIdx.x * gpb * PR_SLOTS + threadIdx.x / G; t < t_end; t += gpb) {
     const MaskRow A = mask_row(p.cls, p.Rb, p.rq, p.Rm, p.W, t);
@@ -163,28 +153,9 @@ __global__ __launch_bounds__(256) void k_obs(PpcLayer p, int G, unsigned long lo
     if (i != j) B = mask_row(p.cls, p.Rb, p.rq, p.Rm, p.W, tm);
     unsigned ca = 0;
     for (unsigned c0 = 0; c0 < nc; c0 += (unsigned)G) {
-      const unsigned q = c0 + (unsigned)gl;
-      unsigned x = 0, m = 0;
-      bool mut = false;
-      if (q < nc) {
-        if (p.X) {
-          m = q;
-          x = p.X[t * p.Mp + m];
-          if (x && !row_has(A, m)) x = 0;
-          mut = x && B.c != 0 && p.X[tm * p.Mp + m] != 0 && row_has(B, m);
-        } else {
-          const unsigned w = p.iv[e0 + q];
-          m = (unsigned)(p.ik[e0 + q] & mmask);
-          x = (w & 1u) ? (w >> 1) : 0u;
-          if (x && B.c != 0) {   // the mirror tie's entry of reporter m: its count, its R bit
-            unsigned lo = p.ip[tm], hi = p.ip[tm + 1];
-            const unsigned end = hi;
-            const unsigned long long key = ((unsigned long long)tm << p.mb) | m;
-            while (lo < hi) { const unsigned c = lo + ((hi - lo) >> 1); if (p.ik[c] < key) lo = c + 1; else hi = c; }
-            mut = lo < end && p.ik[lo] == key && (p.iv[lo] & 1u) && (p.iv[lo] >> 1) != 0u;
-          }
-        }
-      }
+      const TieReport rp = tie_report(p, A, t, e0, nc, c0 + (unsigned)g.gl);
+      const unsigned x = rp.in ? rp.x : 0u, m = rp.m;   // a count outside the mask is no report
+      const bool mut = x && B.c != 0 && mirror_reported(p, B, tm, m);
       const bool pos = x > 0u;
       if (pos) {
         v[0] += 1ull;
@@ -193,26 +164,14 @@ __global__ __launch_bounds__(256) void k_obs(PpcLayer p, int G, unsigned long lo
         if (mut) v[3] += 1ull;
         if (byrep) add_reporter<HIST>(hist, byrep, m, 1u, (unsigned long long)x);
       }
-      ca += (unsigned)__popcll(__ballot(pos) & gmask);
+      ca += (unsigned)__popcll(__ballot(pos) & g.gmask);
     }
-    if (gl == 0) {
+    if (g.gl == 0) {
       v[4] += ca > 0u;
       v[5] += ca > 1u;
     }
   }
   flush_stats<HIST>(v, tot, hist, p.M, counts, byrep);
-}
-
-// lanes per tie: the longest support a group walks
-static int lanes_for(unsigned longest) {
-  int G = 1;
-  while (G < 64 && (unsigned)G < longest) G <<= 1;
-  return G;
-}
-
-static unsigned blocks_for(size_t T, int G) {
-  const size_t per = (size_t)(256 / G) * PR_SLOTS;
-  return (unsigned)((T + per - 1) / per);
 }
 
 }  // namespace
@@ -227,10 +186,8 @@ extern "C" int vmr_ppc_replicates(vmr_handle h, int n_rep, uint64_t seed_y, uint
   const size_t T = (size_t)g.N * g.N, ties = (size_t)g.L * T, LM = (size_t)g.L * g.M, LK = (size_t)g.L * g.K;
   for (int r = 0; r < n_rep; ++r)
     if (!(eta[r] >= 0.0 && eta[r] < 1.0)) return fail(h, VMR_EINVAL, "The mutuality parameter has to be in [0, 1)!");
-  for (size_t q = 0; q < (size_t)n_rep * LM; ++q)
-    if (!(theta[q] >= 0.0 && theta[q] <= 1.79769313486231570815e308)) return fail(h, VMR_EINVAL, "vmr_ppc_replicates: theta must be finite and non-negative");
-  for (size_t q = 0; q < (size_t)n_rep * LK; ++q)
-    if (!(lambda[q] >= 0.0 && lambda[q] <= 1.79769313486231570815e308)) return fail(h, VMR_EINVAL, "vmr_ppc_replicates: lambda must be finite and non-negative");
+  if (!table_nonneg(theta, (size_t)n_rep * LM)) return fail(h, VMR_EINVAL, "vmr_ppc_replicates: theta must be finite and non-negative");
+  if (!table_nonneg(lambda, (size_t)n_rep * LK)) return fail(h, VMR_EINVAL, "vmr_ppc_replicates: lambda must be finite and non-negative");
   if (!h->have_state) return fail(h, VMR_ESTATE, "vmr_set_state must be called before vmr_ppc_replicates");
   HIPCHK(h, hipSetDevice(h->device));
   { const int rce = ensure_rho_ext(h); if (rce) return rce; }
@@ -262,10 +219,10 @@ extern "C" int vmr_ppc_replicates(vmr_handle h, int n_rep, uint64_t seed_y, uint
   a.cls = h->rcls; a.Rb = h->Rb; a.rq = h->rq; a.Rm = h->Rm; a.rbase = h->rbase;
   a.Y = Y; a.theta = thd; a.lambda = lad; a.eta = etd; a.counts = cd; a.byrep = bd;
   // rows of a handle with mask lists are all ones, empty or listed: a pair's support is two lists at most, unless a row is all ones
-  a.G = lanes_for((h->rq && !h->all_full && 2u * h->rm_maxrow < (unsigned)g.M) ? 2u * h->rm_maxrow : (unsigned)g.M);
+  a.G = pow2_lanes((h->rq && !h->all_full && 2u * h->rm_maxrow < (unsigned)g.M) ? 2u * h->rm_maxrow : (unsigned)g.M);
   const bool hist = by_reporter && g.M <= PR_HIST_M;
   const size_t smem = hist ? (size_t)g.M * 16 : 0;
-  const dim3 grid(blocks_for(T, a.G), (unsigned)g.L);
+  const dim3 grid(walk_blocks(T, 256, a.G, PR_SLOTS), (unsigned)g.L);
   for (size_t s0 = 0; s0 < (size_t)n_rep; s0 += C) {
     const size_t c = std::min<size_t>(C, (size_t)n_rep - s0);
     HIPCHK(h, hipMemcpyAsync(thd, theta + s0 * LM, c * LM * 8, hipMemcpyHostToDevice, h->stream));
@@ -300,15 +257,15 @@ extern "C" int vmr_ppc_observed(vmr_handle h, uint64_t* counts, uint64_t* by_rep
   if (by_reporter && (rc = tm.get(&bd, LM * 16, "the observed statistics by reporter"))) return rc;
   HIPCHK(h, hipMemsetAsync(cd, 0, (size_t)g.L * VMR_PPC_NSTAT * 8, h->stream));
   if (bd) HIPCHK(h, hipMemsetAsync(bd, 0, LM * 16, h->stream));
-  const int G = lanes_for((unsigned)g.M);
+  const int G = pow2_lanes((unsigned)g.M);
   const bool hist = by_reporter && g.M <= PR_HIST_M;
   const size_t smem = hist ? (size_t)g.M * 16 : 0;
   for (int l = 0; l < g.L; ++l) {
     LayerPrep lp;
     if ((rc = ppc_prep_layer(h, tm, l, false, false, lp, true))) return rc;
     unsigned long long* bl = bd ? bd + (size_t)l * g.M * 2 : nullptr;
-    if (hist) hipLaunchKernelGGL(k_obs<true>, dim3(blocks_for(T, G)), dim3(256), smem, h->stream, lp.p, G, cd + (size_t)l * VMR_PPC_NSTAT, bl);
-    else hipLaunchKernelGGL(k_obs<false>, dim3(blocks_for(T, G)), dim3(256), 0, h->stream, lp.p, G, cd + (size_t)l * VMR_PPC_NSTAT, bl);
+    if (hist) hipLaunchKernelGGL(k_obs<true>, dim3(walk_blocks(T, 256, G, PR_SLOTS)), dim3(256), smem, h->stream, lp.p, G, cd + (size_t)l * VMR_PPC_NSTAT, bl);
+    else hipLaunchKernelGGL(k_obs<false>, dim3(walk_blocks(T, 256, G, PR_SLOTS)), dim3(256), 0, h->stream, lp.p, G, cd + (size_t)l * VMR_PPC_NSTAT, bl);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));
     ppc_release_layer(tm, lp);

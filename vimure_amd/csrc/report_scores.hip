@@ -3,26 +3,19 @@
 //
 // The per-report counterpart of vmr_reporter_table: which (l,i,j,m) hold a count, or a zero, that the fitted model finds
 // improbable.  The likelihood is vmr_heldout_loglik's (report_lik.h: the same device functions), evaluated not over a list the
-// caller writes down (24 B per entry) but over the support itself, walked as k_ppc_walk (ppc.hip) walks it; only integer
-// histograms, a few sums and the rows worth reading leave the pass.
-//   k_rs_walk<.., FILL = false>   the count pass.  A group of G lanes per tie takes the tie's support reporters in ascending m, G at
-//                 a time: x from the dense row or the tie-major index, xt from the mirror tie's, the tie's rho row, logp and mean.
-//                 Every element goes into the histogram of s = -logp (LDS bins, flushed once per workgroup by integer atomics;
-//                 global integer atomics where they do not fit), into the lane's four sums and four counts; a flagged element
-//                 into its reporter's bin and into the tie's flagged count cnt[t].
-//   (scan)        exclusive 64-bit sum of cnt: a tie's first row.
-//   k_rs_walk<.., FILL = true>    the fill pass, only when rows are asked for and only over ties that hold one: the same walk, a
-//                 flagged element written at its tie's offset plus its ballot rank inside the group -- lexicographic order, no atomics.
-//   k_rs_finish   adds a layer's per-workgroup partial sums and counts in index order.
+// caller writes down (24 B per entry) but over the support itself, by the support walk and its count-and-fill driver
+// (read_side.h: support_walk, walk_count_fill); only integer histograms, a few sums and the rows worth reading leave the pass.
+//   k_rs_walk<.., FILL = false>   the count pass.  Per support element: logp and mean; every element goes into the histogram of
+//                 s = -logp (LDS bins, flushed once per workgroup by integer atomics; global integer atomics where they do not
+//                 fit), into the lane's four sums and four counts (LikAcc); a flagged element into its reporter's bin.
+//   k_rs_walk<.., FILL = true>    the fill pass: logp and mean of the flagged elements beside the walk's six integer columns.
+//   k_lik_finish  adds a layer's per-workgroup partial sums and counts in index order.
 // Determinism: a workgroup owns a fixed contiguous range of RS_SLOTS ties per group; a lane adds its elements in walk order, the
-// waves fold by shuffles, the workgroup in LDS, k_rs_finish in index order: the tree depends on T and G alone.  Everything else
+// waves fold by shuffles, the workgroup in LDS, k_lik_finish in index order: the tree depends on T and G alone.  Everything else
 // is an integer.  No floating-point atomic, no ticket: all outputs are bit-identical from run to run.
-// K <= KMAX: the statements of k_ho_lane (heldout.hip).  K > KMAX: a lane plays the HO_G lanes of k_ho_group one after another --
+// K <= KMAX: lik_eval_lane, as k_ho_lane (heldout.hip).  K > KMAX: a lane plays the HO_G lanes of k_ho_group one after another --
 // category k into pair k mod HO_G in ascending k, then the pairs folded by the butterfly as lane 0 of the group sees it -- the
 // same operations on the same operands, so the same bits.
-#include "vmr_internal.h"
-#include "ppc_layer.h"
-#include "rho_row.h"
 #include "report_lik.h"
 
 namespace {
@@ -32,12 +25,7 @@ namespace {
 #define RS_G 16              // HO_G of heldout.hip: the pairs a row of K > KMAX categories is folded through
 #define RS_LDS_MAX (128u << 10)   // dynamic LDS of the count pass at most (gfx950: 160 KB per workgroup)
 
-// flag bits
-#define RS_BAD_NAN 1
-#define RS_BAD_WALK 2
-
-typedef unsigned long long u64;
-static_assert(VMR_RS_NSUM == 4 && VMR_RS_NCOUNT == 4, "RsAcc, k_rs_finish");
+static_assert(VMR_RS_NSUM == LIK_N && VMR_RS_NCOUNT == LIK_N && RS_TPB == LIK_TPB, "LikAcc, k_lik_finish");
 
 struct RsArgs {
   const double *th, *la, *lgt;   // theta [M] and lambda [K] of the layer, lgamma(x + 1) [HO_LGT]
@@ -56,45 +44,6 @@ struct RsArgs {
   double *logp, *mean;
   int* bad;
 };
-
-struct RsAcc {
-  double s[VMR_RS_NSUM];
-  u64 c[VMR_RS_NCOUNT];
-};
-
-// logp and mean of one element: K <= KMAX, the row in registers (k_ho_lane's statements)
-template <int KC>
-__device__ __forceinline__ void rs_eval_lane(int Kp, const double* __restrict__ row, double thm, const double* __restrict__ la, double eta,
-                                             int x, int xt, const double* __restrict__ lgt, double& lp, double& mn) {
-  const int K = KC ? KC : Kp;
-  double r[KMAX], b[KMAX];
-  if (KC == 2) {
-    const double2 v = *reinterpret_cast<const double2*>(row);   // (rho is 256-byte aligned, a row of two doubles 16-byte)
-    r[0] = v.x; r[1] = v.y;
-  } else {
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k) if (k < K) r[k] = row[k];
-  }
-  const double exy = eta * (double)xt, xd = (double)x;
-  double mx = -INFINITY;
-  bool nan_seen = false;
-  mn = 0.0;
-#pragma unroll
-  for (int k = 0; k < KMAX; ++k)
-    if (k < K) {
-      const double mu = ho_rate(thm, la[k], exy);
-      mn = ho_add(mn, ho_mul(r[k], mu));
-      b[k] = ho_term(r[k], mu, xd, x > 0);
-      nan_seen = nan_seen || b[k] != b[k];
-      if (b[k] > mx) mx = b[k];
-    }
-  double s = 0.0;
-#pragma unroll
-  for (int k = 0; k < KMAX; ++k)
-    if (k < K && b[k] > -INFINITY) s += exp(b[k] - mx);
-  if (nan_seen) s = __builtin_nan("");
-  lp = ho_logp(mx, s, ho_lgam1((unsigned)x, lgt));
-}
 
 // K > KMAX: the RS_G running pairs of k_ho_group, kept by one lane, folded as its lane 0 folds them
 __device__ __forceinline__ void rs_eval_wide(int K, const double* __restrict__ row, double thm, const double* __restrict__ la, double eta,
@@ -126,175 +75,43 @@ __device__ __forceinline__ void rs_eval_wide(int K, const double* __restrict__ r
   lp = ho_logp(mx[0], s[0], ho_lgam1((unsigned)x, lgt));
 }
 
-__device__ __forceinline__ u64 rs_block_sum_u(u64 v, u64* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += (u64)__shfl_xor((long long)v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  u64 r = 0;
-  if (threadIdx.x == 0)
-    for (unsigned w = 0; w < (blockDim.x >> 6); ++w) r += red[w];
-  return r;
-}
-
-// c = #{tau : edges[tau] <= s}; a NaN lands in bin 0 (the call then ends in VMR_ENAN)
-__device__ __forceinline__ int rs_bin(const double* __restrict__ edges, int n, double s) {
-  int a = 0, b = n;
-  while (a < b) { const int c = a + ((b - a) >> 1); if (edges[c] <= s) a = c + 1; else b = c; }
-  return a;
-}
-
 // The walk over the ties [blockIdx.x * gpb * RS_SLOTS, ..) of one layer; KC: 2, 0 (any K <= KMAX) or -1 (K > KMAX).
 template <int KC, bool FILL>
 __global__ __launch_bounds__(RS_TPB) void k_rs_walk(PpcLayer p, int G, RsArgs a) {
   extern __shared__ u64 rs_lds[];   // count pass: [M][2] reporters' bins (byrep_lds), then [n_edges + 1][2] histogram (hist_lds)
   __shared__ double red[16];
   __shared__ u64 redu[16];
-  u64* const lds_rep = rs_lds;
-  u64* const lds_hist = rs_lds + (a.byrep_lds ? 2 * (size_t)p.M : 0);
-  const int n_hist = 2 * (a.n_edges + 1);
-  if (!FILL) {
-    const int n_lds = (a.byrep_lds ? 2 * p.M : 0) + (a.hist_lds ? n_hist : 0);
-    for (int q = threadIdx.x; q < n_lds; q += RS_TPB) rs_lds[q] = 0ull;
-    __syncthreads();
-  }
-  u64* const o_rep = a.byrep_lds ? lds_rep : a.byrep;
-  u64* const o_hist = a.hist_lds ? lds_hist : a.hist;
-  const int lane = threadIdx.x & 63, gl = lane & (G - 1), g0 = lane - gl;
-  const u64 gmask = (G == 64 ? ~0ull : ((1ull << G) - 1ull)) << g0, lt = (1ull << lane) - 1ull;
-  const size_t gpb = RS_TPB / G;
-  const bool words = p.rq == nullptr;
-  RsAcc acc;
-#pragma unroll
-  for (int c = 0; c < VMR_RS_NSUM; ++c) { acc.s[c] = 0.0; acc.c[c] = 0ull; }
-  const size_t t_lim = ((size_t)blockIdx.x + 1) * gpb * RS_SLOTS, t_end = t_lim < p.T ? t_lim : p.T;
-  for (size_t t = (size_t)blockIdx.x * gpb * RS_SLOTS + threadIdx.x / G; t < t_end; t += gpb) {   // (uniform over the group)
-    const int c = p.cls[t];
-    u64 o_t = 0;
-    if (FILL) {
-      o_t = a.cnt[t];
-      if (c == 0 || a.cnt[t + 1] == o_t) continue;   // no row of this tie
-    } else if (c == 0) {
-      continue;                                      // (cnt comes zeroed)
-    }
-    const bool listed = c == 2 && !words, bits = c == 2 && words;
-    const unsigned nc = listed ? p.rq[t + 1] - p.rq[t] : (unsigned)p.M;
-    const unsigned short* lst = listed ? p.Rm + p.rq[t] : nullptr;
-    const size_t i = t / p.N, j = t - i * p.N, tm = j * p.N + i;
-    const double* row = p.rho + (p.inv ? (size_t)p.inv[t] : t) * p.K;
-    u64 jf = 0;
-    for (unsigned c0 = 0; c0 < nc; c0 += (unsigned)G) {
-      const unsigned q = c0 + (unsigned)gl;
-      const unsigned m = listed ? (q < nc ? (unsigned)lst[q] : 0u) : q;
-      const bool in = q < nc && m < (unsigned)p.M && (!bits || ((p.Rb[t * p.W + (m >> 6)] >> (m & 63)) & 1ull));
-      bool flag = false;
-      int x = 0, xt = 0;
-      double lp = 0.0, mn = 0.0;
-      if (in) {
-        x = (int)ppc_x(p, t, m);
-        if (p.mut) xt = (int)ppc_x(p, tm, m);
-        if (KC >= 0) rs_eval_lane<(KC > 0 ? KC : 0)>(p.K, row, a.th[m], a.la, a.eta, x, xt, a.lgt, lp, mn);
+  const int n_hist = 2 * (a.n_edges + 1), n_rep = 2 * p.M;
+  const WalkBins o = walk_bins<FILL>(rs_lds, n_rep, n_hist, a.byrep_lds, a.hist_lds, a.byrep, a.hist, RS_TPB);
+  LikAcc acc;
+  double lp = 0.0, mn = 0.0;
+  support_walk<FILL, RS_TPB, RS_SLOTS>(
+      p, G, a, [](const double*) {},
+      [&](const double* row, unsigned m, int x, int xt) {
+        if (KC >= 0) lik_eval_lane<(KC > 0 ? KC : 0)>(p.K, row, a.th[m], a.la, a.eta, x, xt, a.lgt, lp, mn);
         else rs_eval_wide(p.K, row, a.th[m], a.la, a.eta, x, xt, a.lgt, lp, mn);
         const double s = -lp;
         const int cl = x > 0 ? 0 : 1;   // a report, an omission
-        flag = (a.select & (cl == 0 ? VMR_RS_REPORTS : VMR_RS_OMISSIONS)) != 0 && s >= a.threshold;
+        const bool flag = (a.select & (cl == 0 ? VMR_RS_REPORTS : VMR_RS_OMISSIONS)) != 0 && s >= a.threshold;
         if (!FILL) {
-          if (lp != lp || mn != mn) atomicOr(a.bad, RS_BAD_NAN);
-          const double xd = (double)x, d = xd - mn;
-          if (lp == -INFINITY) acc.c[2] += 1ull; else acc.s[0] += lp;
-          acc.s[1] += d * d;
-          acc.s[2] += xd;
-          acc.s[3] += mn;
-          acc.c[0] += 1ull;
-          acc.c[1] += x > 0 ? 1ull : 0ull;
-          acc.c[3] += flag ? 1ull : 0ull;
-          if (o_hist) atomicAdd(o_hist + 2 * (size_t)rs_bin(a.edges, a.n_edges, s) + cl, 1ull);
-          if (flag && o_rep) atomicAdd(o_rep + 2 * (size_t)m + cl, 1ull);
+          LIK_TAKE(acc, lp, mn, x, flag, a.bad);
+          if (o.hist) atomicAdd(o.hist + 2 * (size_t)edge_bin(a.edges, a.n_edges, s) + cl, 1ull);
+          if (flag && o.rep) atomicAdd(o.rep + 2 * (size_t)m + cl, 1ull);
         }
-      }
-      const u64 bf = __ballot(flag) & gmask;
-      if (FILL && flag) {
-        const u64 at = o_t + jf + (u64)__popcll(bf & lt);
-        if (at >= a.lim) {
-          atomicOr(a.bad, RS_BAD_WALK);   // (the count pass and the fill pass disagree: never written out of bounds)
-        } else {
-          if (a.sl) a.sl[at] = p.l;
-          if (a.si) a.si[at] = (int32_t)i;
-          if (a.sj) a.sj[at] = (int32_t)j;
-          if (a.sm) a.sm[at] = (int32_t)m;
-          if (a.x) a.x[at] = x;
-          if (a.xt) a.xt[at] = xt;
-          if (a.logp) a.logp[at] = lp;
-          if (a.mean) a.mean[at] = mn;
-        }
-      }
-      jf += (u64)__popcll(bf);
-    }
-    if (!FILL && gl == 0) a.cnt[t] = jf;
-  }
+        return flag;
+      },
+      [&](u64 at) {
+        if (a.logp) a.logp[at] = lp;
+        if (a.mean) a.mean[at] = mn;
+      });
   if (FILL) return;
-#pragma unroll
-  for (int c = 0; c < VMR_RS_NSUM; ++c) {
-    const double v = block_sum_n(acc.s[c], red);
-    if (threadIdx.x == 0) a.part[(size_t)blockIdx.x * VMR_RS_NSUM + c] = v;
-  }
-#pragma unroll
-  for (int c = 0; c < VMR_RS_NCOUNT; ++c) {
-    const u64 v = rs_block_sum_u(acc.c[c], redu);
-    if (threadIdx.x == 0) a.cpart[(size_t)blockIdx.x * VMR_RS_NCOUNT + c] = v;
-  }
-  __syncthreads();
-  if (a.byrep_lds)
-    for (int q = threadIdx.x; q < 2 * p.M; q += RS_TPB) { const u64 u = lds_rep[q]; if (u) atomicAdd(a.byrep + q, u); }
-  if (a.hist_lds)
-    for (int q = threadIdx.x; q < n_hist; q += RS_TPB) { const u64 u = lds_hist[q]; if (u) atomicAdd(a.hist + q, u); }
-}
-
-// one workgroup adds a layer's nb partials, column by column, in index order
-__global__ __launch_bounds__(RS_TPB) void k_rs_finish(const double* __restrict__ part, const u64* __restrict__ cpart, size_t nb,
-                                                      double* __restrict__ sums, u64* __restrict__ counts) {
-  __shared__ double red[16];
-  __shared__ u64 redu[16];
-  for (int c = 0; c < VMR_RS_NSUM; ++c) {
-    double v = 0.0;
-    for (size_t b = threadIdx.x; b < nb; b += RS_TPB) v += part[b * VMR_RS_NSUM + c];
-    const double t = block_sum_n(v, red);
-    if (threadIdx.x == 0) sums[c] = t;
-  }
-  for (int c = 0; c < VMR_RS_NCOUNT; ++c) {
-    u64 v = 0;
-    for (size_t b = threadIdx.x; b < nb; b += RS_TPB) v += cpart[b * VMR_RS_NCOUNT + c];
-    const u64 t = rs_block_sum_u(v, redu);
-    if (threadIdx.x == 0) counts[c] = t;
-  }
-}
-
-static bool rs_table_ok(const double* v, size_t n) {
-  for (size_t q = 0; q < n; ++q)
-    if (!(v[q] >= 0.0 && v[q] <= 1.79769313486231570815e308)) return false;
-  return true;
-}
-
-// lanes per tie: a support row holds up to M reporters (group_lanes of ppc.hip)
-static int rs_lanes(const vmr_ctx* h) {
-  int G = 1;
-  while (G < 64 && G < h->g.M) G <<= 1;
-  return G;
+  lik_flush(acc, a.part, a.cpart, red, redu);
+  walk_bins_flush(rs_lds, n_rep, n_hist, a.byrep_lds, a.hist_lds, a.byrep, a.hist, RS_TPB);
 }
 
 template <bool FILL>
 static int rs_launch(vmr_ctx* h, const PpcLayer& p, int G, const RsArgs& a, unsigned nb, size_t smem) {
-  const int K = p.K;
-  auto go = [&](auto kern) -> int {
-    if (smem > 48 * 1024) HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    hipLaunchKernelGGL(kern, dim3(nb), dim3(RS_TPB), smem, h->stream, p, G, a);
-    HIPCHK(h, hipGetLastError());
-    return VMR_OK;
-  };
-  if (K == 2) return go(k_rs_walk<2, FILL>);
-  if (K <= KMAX) return go(k_rs_walk<0, FILL>);
-  return go(k_rs_walk<-1, FILL>);
+  return launch_by_k(h, p.K, nb, RS_TPB, smem, [](auto kc) { return k_rs_walk<decltype(kc)::value, FILL>; }, p, G, a);
 }
 
 // What both entry points share.  rows: the table is asked for (n its capacity); n_out: the row count, or null.
@@ -305,18 +122,13 @@ static int rs_run(vmr_ctx* h, const char* fn, int layer, const double* theta, co
   if (!theta || !lambda) return bad_arg("theta or lambda is NULL");
   const Geo& g = h->g;
   const int L = g.L, M = g.M, K = g.K;
-  if (!rs_table_ok(theta, (size_t)L * M)) return bad_arg("theta must be finite and non-negative");
-  if (!rs_table_ok(lambda, (size_t)L * K)) return bad_arg("lambda must be finite and non-negative");
-  if (!rs_table_ok(&eta, 1)) return bad_arg("eta must be finite and non-negative");
+  if (!table_nonneg(theta, (size_t)L * M)) return bad_arg("theta must be finite and non-negative");
+  if (!table_nonneg(lambda, (size_t)L * K)) return bad_arg("lambda must be finite and non-negative");
+  if (!table_nonneg(&eta, 1)) return bad_arg("eta must be finite and non-negative");
   if (select < 1 || select > 3) return bad_arg("select must be VMR_RS_REPORTS, VMR_RS_OMISSIONS or both (1, 2 or 3)");
   if (threshold != threshold || threshold == -INFINITY) return bad_arg("the threshold must be finite or +inf");
   if (layer >= L) return bad_arg("layer out of range");
-  if (n_edges < 0 || n_edges > VMR_RS_MAX_EDGES) return bad_arg("n_edges must lie in [0, VMR_RS_MAX_EDGES]");
-  if (hist && n_edges > 0 && !edges) return bad_arg("hist is asked for and edges is NULL");
-  if (hist)
-    for (int q = 0; q < n_edges; ++q)
-      if (!(edges[q] >= -1.79769313486231570815e308 && edges[q] <= 1.79769313486231570815e308) || (q && edges[q] < edges[q - 1]))
-        return bad_arg("the edges must be finite and non-decreasing");
+  if (const char* why = hist_refusal(hist, n_edges, VMR_RS_MAX_EDGES, "n_edges must lie in [0, VMR_RS_MAX_EDGES]", edges)) return bad_arg(why);
   if (!h->have_state) return fail(h, VMR_ESTATE, (std::string("vmr_set_state must be called before ") + fn).c_str());
   const size_t T = (size_t)g.N * g.N;
   if (T >= 0x7fffffffull) return bad_arg("2^31 ties or more in one layer");
@@ -333,133 +145,69 @@ static int rs_run(vmr_ctx* h, const char* fn, int layer, const double* theta, co
   ho_lgt_fill(par_h.data() + o_lg);
   if (n_edges) memcpy(par_h.data() + o_ed, edges, (size_t)n_edges * 8);
 
-  const int G = rs_lanes(h);
-  const size_t per = (size_t)(RS_TPB / G) * RS_SLOTS;
-  const unsigned nb = (unsigned)((T + per - 1) / per);
-  const size_t n_hist = hist ? 2 * ((size_t)n_edges + 1) : 0, n_rep = by_reporter ? 2 * (size_t)M : 0;
-  const bool rep_lds = by_reporter && M <= PR_HIST_M;
-  const bool hist_lds = hist && ((rep_lds ? n_rep : 0) + n_hist) * 8 <= RS_LDS_MAX;
-  const size_t smem = ((rep_lds ? n_rep : 0) + (hist_lds ? n_hist : 0)) * 8;
+  const size_t n_rep = by_reporter ? 2 * (size_t)M : 0;
+  const WalkShape ws = walk_shape(h, RS_TPB, RS_SLOTS, hist != nullptr, n_edges, n_rep, RS_LDS_MAX);
+  const int G = ws.G;
+  const unsigned nb = ws.nb;
+  const size_t n_hist = ws.n_hist, smem = ws.smem;
 
   Tmp tm(h);
-  int rc;
-  int* bad = nullptr;
+  int rc, b = 0;
   double *par_d = nullptr, *part = nullptr, *sums_d = nullptr;
-  u64 *cpart = nullptr, *counts_d = nullptr, *hist_d = nullptr, *rep_d = nullptr, *cnt = nullptr, *off = nullptr;
-  void* ts = nullptr;
-  size_t tb = 0;
-  if ((rc = tm.get(&bad, 4, "a flag")) || (rc = tm.get(&par_d, n_par * 8, "the parameter tables")) ||
-      (rc = tm.get(&part, (size_t)nb * VMR_RS_NSUM * 8, "the partial sums")) || (rc = tm.get(&cpart, (size_t)nb * VMR_RS_NCOUNT * 8, "the partial counts")) ||
-      (rc = tm.get(&sums_d, (size_t)Lq * VMR_RS_NSUM * 8, "the sums")) || (rc = tm.get(&counts_d, (size_t)Lq * VMR_RS_NCOUNT * 8, "the counts")) ||
-      (rc = tm.get(&hist_d, (size_t)Lq * n_hist * 8, "the histogram")) || (rc = tm.get(&rep_d, (size_t)Lq * n_rep * 8, "the reporters' bins")) ||
-      (rc = tm.get(&cnt, (T + 1) * 8, "the ties' flagged counts")))
-    return rc;
-  if (rows) {   // a tie's first row, every layer's: kept until the capacity is checked against all of them
-    if ((rc = tm.get(&off, (size_t)Lq * (T + 1) * 8, "the ties' row offsets"))) return rc;
-    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tb, cnt, off, (int)(T + 1), h->stream));
-    if ((rc = tm.get(&ts, tb, "the scan of the flagged counts"))) return rc;
-  }
-  HIPCHK(h, hipMemcpyAsync(par_d, par_h.data(), n_par * 8, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemsetAsync(bad, 0, 4, h->stream));
-  if (n_hist) HIPCHK(h, hipMemsetAsync(hist_d, 0, (size_t)Lq * n_hist * 8, h->stream));
-  if (n_rep) HIPCHK(h, hipMemsetAsync(rep_d, 0, (size_t)Lq * n_rep * 8, h->stream));
-
+  u64 *cpart = nullptr, *counts_d = nullptr, *hist_d = nullptr, *rep_d = nullptr;
+  std::vector<u64> counts_h((size_t)Lq * VMR_RS_NCOUNT);
   RsArgs a;
   memset(&a, 0, sizeof a);
+  if ((rc = tm.get(&a.bad, 4, "a flag")) || (rc = tm.get(&par_d, n_par * 8, "the parameter tables")) ||
+      (rc = tm.get(&part, (size_t)nb * VMR_RS_NSUM * 8, "the partial sums")) || (rc = tm.get(&cpart, (size_t)nb * VMR_RS_NCOUNT * 8, "the partial counts")) ||
+      (rc = tm.get(&sums_d, (size_t)Lq * VMR_RS_NSUM * 8, "the sums")) || (rc = tm.get(&counts_d, (size_t)Lq * VMR_RS_NCOUNT * 8, "the counts")) ||
+      (rc = tm.get(&hist_d, (size_t)Lq * n_hist * 8, "the histogram")) || (rc = tm.get(&rep_d, (size_t)Lq * n_rep * 8, "the reporters' bins")))
+    return rc;
+  HIPCHK(h, hipMemcpyAsync(par_d, par_h.data(), n_par * 8, hipMemcpyHostToDevice, h->stream));
+  if (n_hist) HIPCHK(h, hipMemsetAsync(hist_d, 0, (size_t)Lq * n_hist * 8, h->stream));
+  if (n_rep) HIPCHK(h, hipMemsetAsync(rep_d, 0, (size_t)Lq * n_rep * 8, h->stream));
   a.lgt = par_d + o_lg;
-  a.eta = eta; a.threshold = threshold; a.select = select; a.n_edges = n_edges;
   a.edges = hist ? par_d + o_ed : nullptr;
-  a.hist_lds = hist_lds; a.byrep_lds = rep_lds;
-  a.part = part; a.cpart = cpart; a.bad = bad;
-
-  // the count pass, layer by layer
-  for (int l = l0; l < l1; ++l) {
-    LayerPrep lp;
-    if ((rc = ppc_prep_layer(h, tm, l, false, true, lp, true, false))) return rc;
+  a.part = part; a.cpart = cpart;
+  a.eta = eta; a.threshold = threshold; a.select = select; a.n_edges = n_edges;
+  a.hist_lds = ws.hist_lds; a.byrep_lds = ws.rep_lds;
+  auto tables = [&](int l) {
     a.th = par_d + (size_t)l * M;
     a.la = par_d + o_la + (size_t)l * K;
-    a.hist = hist ? hist_d + (size_t)(l - l0) * n_hist : nullptr;
-    a.byrep = by_reporter ? rep_d + (size_t)(l - l0) * n_rep : nullptr;
-    a.cnt = cnt;
-    HIPCHK(h, hipMemsetAsync(cnt, 0, (T + 1) * 8, h->stream));
-    if ((rc = rs_launch<false>(h, lp.p, G, a, nb, smem))) return rc;
-    hipLaunchKernelGGL(k_rs_finish, dim3(1), dim3(RS_TPB), 0, h->stream, (const double*)part, (const u64*)cpart, (size_t)nb,
-                       sums_d + (size_t)(l - l0) * VMR_RS_NSUM, counts_d + (size_t)(l - l0) * VMR_RS_NCOUNT);
-    HIPCHK(h, hipGetLastError());
-    if (rows) HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(ts, tb, cnt, off + (size_t)(l - l0) * (T + 1), (int)(T + 1), h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    ppc_release_layer(tm, lp);
-  }
-  std::vector<u64> counts_h((size_t)Lq * VMR_RS_NCOUNT);
-  int b = 0;
-  HIPCHK(h, hipMemcpyAsync(counts_h.data(), counts_d, counts_h.size() * 8, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(&b, bad, 4, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  u64 total = 0;
-  for (int q = 0; q < Lq; ++q) total += counts_h[(size_t)q * VMR_RS_NCOUNT + 3];
-  if (n_out) *n_out = total;
-  if (rows && n < total) {
-    char msg[200];
-    snprintf(msg, sizeof msg, "%s: the table holds %llu rows, %llu elements are flagged", fn, (unsigned long long)n, (unsigned long long)total);
-    return fail(h, VMR_EINVAL, msg);
-  }
-
-  // the fill pass: the layers that hold a row
-  if (rows && total && !(b & RS_BAD_NAN)) {
-    u64 base = 0;
-    for (int l = l0; l < l1; ++l) {
-      const u64 nl = counts_h[(size_t)(l - l0) * VMR_RS_NCOUNT + 3];
-      if (!nl) continue;
-      LayerPrep lp;
-      if ((rc = ppc_prep_layer(h, tm, l, false, true, lp, true, false))) return rc;
-      a.th = par_d + (size_t)l * M;
-      a.la = par_d + o_la + (size_t)l * K;
-      a.hist = nullptr; a.byrep = nullptr; a.edges = nullptr; a.n_edges = 0; a.hist_lds = 0; a.byrep_lds = 0;
-      a.cnt = off + (size_t)(l - l0) * (T + 1);
-      a.lim = nl;
-      int32_t* d32[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-      double* d64[2] = {nullptr, nullptr};
-      double* h64[2] = {logp, mean};
-      int32_t* st32 = nullptr;
-      double* st64 = nullptr;
-      if (out_on_device) {
-        for (int q = 0; q < 6; ++q) d32[q] = sub[q] ? sub[q] + base : nullptr;
-        for (int q = 0; q < 2; ++q) d64[q] = h64[q] ? h64[q] + base : nullptr;
-      } else {   // host outputs: the layer's rows through device staging
-        int n32 = 0, n64 = 0;
-        for (int q = 0; q < 6; ++q) n32 += sub[q] != nullptr;
-        for (int q = 0; q < 2; ++q) n64 += h64[q] != nullptr;
-        if ((n32 && (rc = tm.get(&st32, (size_t)n32 * nl * 4, "the staging of the rows"))) ||
-            (n64 && (rc = tm.get(&st64, (size_t)n64 * nl * 8, "the staging of the rows"))))
-          return rc;
-        for (int q = 0, u = 0; q < 6; ++q) if (sub[q]) d32[q] = st32 + (size_t)(u++) * nl;
-        for (int q = 0, u = 0; q < 2; ++q) if (h64[q]) d64[q] = st64 + (size_t)(u++) * nl;
-      }
-      a.sl = d32[0]; a.si = d32[1]; a.sj = d32[2]; a.sm = d32[3]; a.x = d32[4]; a.xt = d32[5];
-      a.logp = d64[0]; a.mean = d64[1];
-      if ((rc = rs_launch<true>(h, lp.p, G, a, nb, 0))) return rc;
-      if (!out_on_device) {
-        for (int q = 0; q < 6; ++q)
-          if (sub[q]) HIPCHK(h, hipMemcpyAsync(sub[q] + base, d32[q], (size_t)nl * 4, hipMemcpyDeviceToHost, h->stream));
-        for (int q = 0; q < 2; ++q)
-          if (h64[q]) HIPCHK(h, hipMemcpyAsync(h64[q] + base, d64[q], (size_t)nl * 8, hipMemcpyDeviceToHost, h->stream));
-      }
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-      if (st32) tm.release(st32);
-      if (st64) tm.release(st64);
-      ppc_release_layer(tm, lp);
-      base += nl;
-    }
-    HIPCHK(h, hipMemcpyAsync(&b, bad, 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (b & RS_BAD_WALK) return fail(h, VMR_EHIP, (std::string(fn) + ": the count pass and the fill pass disagree").c_str());
-  }
+  };
+  double* const dbl[2] = {logp, mean};
+  const WalkTable w = {rows, n, sub, dbl, 2, out_on_device, n_out};
+  rc = walk_count_fill(
+      h, fn, tm, l0, l1, w, a, b,
+      [&](int l, const PpcLayer& p) -> int {
+        tables(l);
+        a.hist = hist ? hist_d + (size_t)(l - l0) * n_hist : nullptr;
+        a.byrep = by_reporter ? rep_d + (size_t)(l - l0) * n_rep : nullptr;
+        const int rc = rs_launch<false>(h, p, G, a, nb, smem);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_lik_finish, dim3(1), dim3(RS_TPB), 0, h->stream, (const double*)part, (const u64*)cpart, (size_t)nb,
+                           sums_d + (size_t)(l - l0) * VMR_RS_NSUM, counts_d + (size_t)(l - l0) * VMR_RS_NCOUNT);
+        HIPCHK(h, hipGetLastError());
+        return VMR_OK;
+      },
+      [&](u64* flagged) -> int {
+        HIPCHK(h, hipMemcpy(counts_h.data(), counts_d, counts_h.size() * 8, hipMemcpyDeviceToHost));
+        for (int q = 0; q < Lq; ++q) flagged[q] = counts_h[(size_t)q * VMR_RS_NCOUNT + 3];
+        return VMR_OK;
+      },
+      [&](int l, const PpcLayer& p, double* const* d64) -> int {
+        tables(l);
+        a.hist = nullptr; a.byrep = nullptr; a.edges = nullptr; a.n_edges = 0; a.hist_lds = 0; a.byrep_lds = 0;
+        a.logp = d64[0]; a.mean = d64[1];
+        return rs_launch<true>(h, p, G, a, nb, 0);
+      });
+  if (rc) return rc;
   if (hist) HIPCHK(h, hipMemcpyAsync(hist, hist_d, (size_t)Lq * n_hist * 8, hipMemcpyDeviceToHost, h->stream));
   if (by_reporter) HIPCHK(h, hipMemcpyAsync(by_reporter, rep_d, (size_t)Lq * n_rep * 8, hipMemcpyDeviceToHost, h->stream));
   if (sums) HIPCHK(h, hipMemcpyAsync(sums, sums_d, (size_t)Lq * VMR_RS_NSUM * 8, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   if (counts) memcpy(counts, counts_h.data(), counts_h.size() * 8);
-  if (b & RS_BAD_NAN) return fail(h, VMR_ENAN, (std::string(fn) + ": a logp or a mean is NaN").c_str());
+  if (b & WALK_BAD_NAN) return fail(h, VMR_ENAN, (std::string(fn) + ": a logp or a mean is NaN").c_str());
   return VMR_OK;
 }
 

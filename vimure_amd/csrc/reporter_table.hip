@@ -10,7 +10,7 @@
 //                 which leave the workgroup as four integer atomics.  Partial row: its mask words' set bits, or its reporter list,
 //                 into the bins (n_scope, n_inferred, E, Q) of every reporter it holds.
 //   k_rt_reports  a group of G lanes per ordered tie over the tie's reports (the dense row, or the tie's row of the tie-major
-//                 index of ppc.hip), the walk of k_obs (ppc_rep.hip).  A report x > 0 of reporter m inside the mask adds to
+//                 index of ppc.hip), fetched by tie_report (read_side.h) as in k_obs.  A report x > 0 of reporter m inside the mask adds to
 //                 (n_rep, total, hits, H, mutual), outside it to n_out; and, with mutuality, it IS the X^T of the mirror tie: where
 //                 the mirror tie's mask row holds m it adds rs_mirror x to U.  The rho rows of ties with reports are read again here.
 // The host then puts a row together:  n_scope = all-ones n + bin, n_inferred likewise, exp_ties = E, exp_hits = H,
@@ -21,9 +21,7 @@
 // (rt_fixed_point below; a row of rho summing to more than 2 is refused).  Integer adds commute: LDS and global integer atomics
 // in any order give the same bits, and there is no floating-point atomic anywhere.  Bins live in LDS up to PR_HIST_M reporters
 // (flushed once per workgroup), in global memory beyond.
-#include "vmr_internal.h"
-#include "ppc_layer.h"
-#include "rho_row.h"
+#include "read_side.h"
 
 namespace {
 
@@ -31,8 +29,6 @@ namespace {
 #define RT_NTB 4     // bins of the tie pass per reporter: n_scope, n_inferred, E, Q  (and the all-ones scalars of a layer)
 #define RT_NRB 7     // bins of the report pass per reporter: n_rep, total, hits, mutual, n_out, H, U
 #define RT_SLOTS 64  // tie slots a group walks per workgroup (report pass)
-
-typedef unsigned long long u64;
 
 // the fixed point of a call (host-sized) and what the kernels refuse
 struct RtFx {
@@ -50,7 +46,7 @@ __device__ __forceinline__ RtTie rt_tie(const double* __restrict__ r, int K, con
   RtTie o;
   double mean;
   rho_row_prob_mean(r, K, o.prob, mean);
-  o.y = method == VMR_READ_THRESHOLD ? (r[1] >= threshold ? 1u : 0u) : rho_row_argmax(r, K);   // the byte of k_readout
+  o.y = rho_row_readout(r, K, method, threshold);
   double rs = 0.0, q = 0.0;
   for (int k = 0; k < K; ++k) {
     rs += r[k];
@@ -64,20 +60,6 @@ __device__ __forceinline__ RtTie rt_tie(const double* __restrict__ r, int K, con
 __device__ __forceinline__ u64 rt_fx(double v, double lim, int sh, int* __restrict__ bad) {
   if (!(v >= 0.0 && v <= lim)) { atomicOr(bad, v != v ? 1 : 4); return 0ull; }
   return det_fx(v, sh);
-}
-
-__device__ __forceinline__ u64 rt_wave_sum(u64 v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += (u64)__shfl_xor((long long)v, o, 64);
-  return v;
-}
-
-// the workgroup's LDS bins -> global, the non-zero ones
-__device__ __forceinline__ void rt_flush(const u64* hist, u64* __restrict__ bins, int n) {
-  for (int q = threadIdx.x; q < n; q += RT_TPB) {
-    const u64 u = hist[q];
-    if (u) atomicAdd(bins + q, u);
-  }
 }
 
 // The pass over the ties of one layer.  perm: position -> tie of the layer (report lists: rho is stored by sorted position), or null.
@@ -131,12 +113,12 @@ __global__ __launch_bounds__(RT_TPB) void k_rt_ties(PpcLayer p, const unsigned* 
   }
 #pragma unroll
   for (int k = 0; k < RT_NTB; ++k) {
-    c[k] = rt_wave_sum(c[k]);
+    c[k] = wave_sum_ull(c[k]);
     if ((threadIdx.x & 63) == 0 && c[k]) atomicAdd(&tot[k], c[k]);
   }
   __syncthreads();
   if (threadIdx.x < RT_NTB && tot[threadIdx.x]) atomicAdd(scal + threadIdx.x, tot[threadIdx.x]);
-  if (HIST) rt_flush(rt_hist, bins, RT_NTB * p.M);
+  if (HIST) flush_bins(rt_hist, bins, RT_NTB * p.M, RT_TPB);
 }
 
 // The pass over the reports of one layer: a group of G lanes per ordered tie.  bins [M][RT_NRB].
@@ -147,10 +129,8 @@ __global__ __launch_bounds__(RT_TPB) void k_rt_reports(PpcLayer p, int G, RtFx f
   if (HIST) for (int q = threadIdx.x; q < RT_NRB * p.M; q += RT_TPB) rt_hist[q] = 0ull;
   __syncthreads();
   u64* const o = HIST ? rt_hist : bins;
-  const int lane = threadIdx.x & 63, gl = lane & (G - 1), g0 = lane - gl;
-  const u64 gmask = (G == 64 ? ~0ull : ((1ull << G) - 1ull)) << g0;
+  const WalkGroup g = walk_group(G);
   const size_t gpb = RT_TPB / G;
-  const u64 mmask = (1ull << p.mb) - 1ull;
   const size_t t_lim = ((size_t)blockIdx.x + 1) * gpb * RT_SLOTS, t_end = t_lim < p.T ? t_lim : p.T;
   for (size_t t = (size_t)blockIdx.x * gpb * RT_SLOTS + threadIdx.x / G; t < t_end; t += gpb) {   // (uniform over the group)
     const unsigned e0 = p.X ? 0u : p.ip[t], nc = p.X ? (unsigned)p.M : p.ip[t + 1] - e0;
@@ -163,51 +143,28 @@ __global__ __launch_bounds__(RT_TPB) void k_rt_reports(PpcLayer p, int G, RtFx f
     u64 e = 0;
     double rsm = 0.0;
     for (unsigned c0 = 0; c0 < nc; c0 += (unsigned)G) {
-      const unsigned q = c0 + (unsigned)gl;
-      unsigned x = 0, m = 0;
-      bool in = false;
-      if (q < nc) {
-        if (p.X) {
-          m = q;
-          x = p.X[t * p.Mp + m];
-          in = x && row_has(A, m);
-        } else {
-          const unsigned w = p.iv[e0 + q];
-          m = (unsigned)(p.ik[e0 + q] & mmask);
-          x = w >> 1;
-          in = x && (w & 1u);
-        }
-      }
-      if (!(__ballot(x > 0u) & gmask)) continue;   // (uniform over the group)
+      const TieReport rp = tie_report(p, A, t, e0, nc, c0 + (unsigned)g.gl);
+      const unsigned x = rp.x, m = rp.m;
+      if (!(__ballot(x > 0u) & g.gmask)) continue;   // (uniform over the group)
       if (!have) {   // the tie's own row, and the mirror tie's sum: once per tie with a report
-        const RtTie v = rt_tie(p.rho + (p.inv ? (size_t)p.inv[t] : t) * p.K, p.K, nullptr, method, threshold);
+        const RtTie v = rt_tie(tie_rho(p, t), p.K, nullptr, method, threshold);
         y = v.y;
         e = rt_fx(v.prob, 2.0, fx.sh_p, bad);
         if (p.mut) {
           rsm = v.rs;
           if (i != j) {
-            const double* r = p.rho + (p.inv ? (size_t)p.inv[tm] : tm) * p.K;
+            const double* r = tie_rho(p, tm);
             rsm = 0.0;
             for (int k = 0; k < p.K; ++k) rsm += r[k];
           }
-          if (rsm != rsm || rsm > 2.0) { if (gl == 0) atomicOr(bad, rsm != rsm ? 1 : 4); rsm = 0.0; }
+          if (rsm != rsm || rsm > 2.0) { if (g.gl == 0) atomicOr(bad, rsm != rsm ? 1 : 4); rsm = 0.0; }
         }
         have = true;
       }
       if (x == 0u || m >= (unsigned)p.M) continue;
       u64* b = o + (size_t)m * RT_NRB;
-      if (in) {
-        bool mut = false;
-        if (i != j && B.c != 0) {   // the mirror tie's report of reporter m, inside its mask
-          if (p.X) mut = p.X[tm * p.Mp + m] != 0 && row_has(B, m);
-          else {
-            unsigned lo = p.ip[tm], hi = p.ip[tm + 1];
-            const unsigned end = hi;
-            const u64 key = ((u64)tm << p.mb) | m;
-            while (lo < hi) { const unsigned c = lo + ((hi - lo) >> 1); if (p.ik[c] < key) lo = c + 1; else hi = c; }
-            mut = lo < end && p.ik[lo] == key && (p.iv[lo] & 1u) && (p.iv[lo] >> 1) != 0u;
-          }
-        }
+      if (rp.in) {
+        const bool mut = i != j && B.c != 0 && mirror_reported(p, B, tm, m);
         atomicAdd(b, 1ull);
         atomicAdd(b + 1, (u64)x);
         if (y) atomicAdd(b + 2, 1ull);
@@ -223,23 +180,10 @@ __global__ __launch_bounds__(RT_TPB) void k_rt_reports(PpcLayer p, int G, RtFx f
     }
   }
   __syncthreads();
-  if (HIST) rt_flush(rt_hist, bins, RT_NRB * p.M);
+  if (HIST) flush_bins(rt_hist, bins, RT_NRB * p.M, RT_TPB);
 }
 
 static double det_back_host(u64 u, int sh) { return ldexp((double)u, -sh); }
-
-static int rt_lanes(size_t longest) {
-  int G = 1;
-  while (G < 64 && (size_t)G < longest) G <<= 1;
-  return G;
-}
-
-// smallest b with 2^b >= v
-static int rt_bits(unsigned long long v) {
-  int b = 0;
-  while (b < 63 && (1ull << b) < v) ++b;
-  return b;
-}
 
 // The fixed point of a call, from what the host knows.  b = ceil(log2 N^2); e_l: G_lambda <= 2^e_l for every entry; e_x: sum X < 2^e_x.
 //   E, H   terms prob <= 2 (checked), at most N^2 of them                      sh_p = 61 - b
@@ -247,7 +191,7 @@ static int rt_bits(unsigned long long v) {
 //   U      terms rs x with rs <= 2 (checked), all of them together <= 2 sum X   sh_u = 61 - e_x
 // so every sum stays below 2^62.  A term is rounded to nearest: a reporter's sum of n terms is off by n 2^-sh / 2 at most.
 static void rt_fixed_point(size_t T, double gla_max, double sum_x, RtFx& fx, double& lim_u) {
-  const int b = rt_bits((unsigned long long)T);
+  const int b = ceil_log2((u64)T);
   int e_l = 0, e_x = 0;
   (void)frexp(gla_max, &e_l);            // gla_max = f 2^e_l, f in [0.5, 1)
   if (gla_max == 0.0) e_l = -1000;
@@ -282,12 +226,8 @@ extern "C" int vmr_reporter_table(vmr_handle h, int method, double threshold, in
   double gnu = 0.0, sum_x = 0.0, gla_max = 0.0;
   int rc;
   if ((rc = vmr_get_geometric(h, gth.data(), gla.data(), &gnu, nullptr)) || (rc = vmr_data_stats(h, &sum_x, nullptr))) return rc;
-  for (int l = l0; l < l1; ++l)
-    for (int k = 0; k < K; ++k) {
-      const double v = gla[(size_t)l * K + k];
-      if (!(v >= 0.0 && v <= 1.79769313486231570815e308)) return fail(h, VMR_ENAN, "vmr_reporter_table: G_lambda is NaN, infinite or negative");
-      gla_max = std::max(gla_max, v);
-    }
+  if (!table_nonneg(gla.data() + (size_t)l0 * K, (size_t)Lq * K)) return fail(h, VMR_ENAN, "vmr_reporter_table: G_lambda is NaN, infinite or negative");
+  for (size_t q = (size_t)l0 * K; q < (size_t)l1 * K; ++q) gla_max = std::max(gla_max, gla[q]);
   RtFx fx;
   double lim_u = 0.0;
   rt_fixed_point(T, gla_max, sum_x, fx, lim_u);
@@ -311,11 +251,9 @@ extern "C" int vmr_reporter_table(vmr_handle h, int method, double threshold, in
   if (smem_r > 48 * 1024)
     HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k_rt_reports<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_r));
   // lanes per tie of the report pass: dense tiles the whole row; report lists twice the mean row of the index
-  const size_t ties = (size_t)L * T;
-  const int G = h->sparse ? rt_lanes(std::min<size_t>((size_t)M, std::max<size_t>(1, (size_t)((2 * h->nnz + ties - 1) / ties)))) : rt_lanes((size_t)M);
+  const int G = h->sparse ? index_lanes(h) : pow2_lanes((size_t)M);
   const unsigned nb_t = (unsigned)std::max<size_t>(1, std::min<size_t>(2048, (T + RT_TPB - 1) / RT_TPB));
-  const size_t per = (size_t)(RT_TPB / G) * RT_SLOTS;
-  const unsigned nb_r = (unsigned)((T + per - 1) / per);
+  const unsigned nb_r = walk_blocks(T, RT_TPB, G, RT_SLOTS);
   for (int l = l0; l < l1; ++l) {
     LayerPrep lp;
     if ((rc = ppc_prep_layer(h, tm, l, false, true, lp, true, false))) return rc;

@@ -1,5 +1,5 @@
-// rho_row.h -- what the read-side kernels take from one tie's row of rho (edge_table.hip, score_truth.hip): the first maximum and
-// the two ascending sums, written once so that every caller rounds alike.
+// rho_row.h -- what the read-side kernels take from one tie's row of rho: the first maximum, the readout byte and the two
+// ascending sums, written once so that every caller rounds alike.
 #ifndef VMR_RHO_ROW_H
 #define VMR_RHO_ROW_H
 #include "vmr_internal.h"
@@ -10,6 +10,12 @@ __device__ __forceinline__ unsigned rho_row_argmax(const double* __restrict__ r,
   double bv = r[0];
   for (int k = 1; k < K; ++k) if (r[k] > bv) { bv = r[k]; best = k; }
   return (unsigned)best;
+}
+
+// the byte vmr_readout writes for a tie under a readout of categories: the threshold on rho_1, else the first maximum
+__device__ __forceinline__ unsigned rho_row_readout(const double* __restrict__ r, int K, int method, double threshold) {
+  if (method == VMR_READ_THRESHOLD) return r[1] >= threshold ? 1u : 0u;
+  return rho_row_argmax(r, K);
 }
 
 // prob = sum_{k>=1} rho_k and mean = sum_k k rho_k, k ascending, every product and every sum rounded on its own: the compiler may

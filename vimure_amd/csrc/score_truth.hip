@@ -16,19 +16,11 @@
 // The AUC (only when asked for): k_sc_pos compacts the positives' scores of a layer as order-preserving uint64 keys (slots from
 // an integer cursor: the sort that follows makes their order immaterial), hipcub sorts them, and k_sc_rank lets every negative tie
 // binary-search the sorted keys and add 2 #(pos > s) + #(pos = s) -- integers, one 64-bit atomic per workgroup.
-#include "vmr_internal.h"
-#include "ppc_layer.h"
-#include "rho_row.h"
+#include "read_side.h"
 
 namespace {
 
 #define SC_TPB 256
-
-// order-preserving key of a double (-0 as +0): equal keys <=> equal values (ppc.hip's)
-__device__ __forceinline__ unsigned long long sc_okey(double v) {
-  const unsigned long long u = (unsigned long long)__double_as_longlong(v + 0.0);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
 
 struct ScTie {
   double s, mean;
@@ -55,12 +47,6 @@ __device__ __forceinline__ ScTie sc_tie(const double* __restrict__ r, int K, int
     o.a = rho_row_argmax(r, K);
   }
   return o;
-}
-
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += (unsigned long long)__shfl_xor((long long)v, o, 64);
-  return v;
 }
 
 // the tie of position pos of layer l, or T where the tie is left out (the diagonal with skip_diag)
@@ -186,7 +172,7 @@ __global__ __launch_bounds__(SC_TPB) void k_sc_pos(const double* __restrict__ rh
     const ScTie v = sc_tie<K2>(rho + ((size_t)l * T + pos) * K, K, score);
     const unsigned long long at = atomicAdd(cursor, 1ull);
     if (at >= P) { atomicOr(bad, 2); continue; }   // (the count and the walk disagree: never written out of bounds)
-    keys[at] = sc_okey(v.s);
+    keys[at] = order_key(v.s);
   }
 }
 
@@ -204,7 +190,7 @@ __global__ __launch_bounds__(SC_TPB) void k_sc_rank(const double* __restrict__ r
     const size_t t = sc_tie_of(perm, l, pos, T, NS, N, skip_diag);
     if (t >= T || y[(size_t)l * T + t] != 0) continue;
     const ScTie v = sc_tie<K2>(rho + ((size_t)l * T + pos) * K, K, score);
-    const unsigned long long key = sc_okey(v.s);
+    const unsigned long long key = order_key(v.s);
     unsigned long long lo = 0, hi = P;   // first index with pk >= key
     while (lo < hi) {
       const unsigned long long mid = lo + ((hi - lo) >> 1);
@@ -218,13 +204,11 @@ __global__ __launch_bounds__(SC_TPB) void k_sc_rank(const double* __restrict__ r
     }
     mine += 2ull * (P - lo) + (lo - first);
   }
-  mine = wave_sum_u64(mine);
+  mine = wave_sum_ull(mine);
   if ((threadIdx.x & 63) == 0 && mine) atomicAdd(&tot, mine);
   __syncthreads();
   if (threadIdx.x == 0 && tot) atomicAdd(acc, tot);
 }
-
-static unsigned sc_grid(size_t T, size_t cap) { return (unsigned)std::max<size_t>(1, std::min<size_t>(cap, (T + SC_TPB - 1) / SC_TPB)); }
 
 }  // namespace
 
@@ -254,7 +238,7 @@ extern "C" int vmr_score_truth(vmr_handle h, const uint8_t* y_true, int y_true_o
 
   const int nh = hist ? n_thr : 0;            // thresholds the pass uses
   const size_t nbin = (size_t)(nh + 1) * 2;
-  const int nb = (int)sc_grid(T, 1024);       // (of N only: the summation tree is the same on every device)
+  const int nb = (int)grid_for(T, SC_TPB, 1024);      // (of N only: the summation tree is the same on every device)
   const size_t smem = hist ? (size_t)nh * 8 + nbin * 4 : 0;
   Tmp tm(h);
   int rc;
@@ -318,7 +302,7 @@ extern "C" int vmr_score_truth(vmr_handle h, const uint8_t* y_true, int y_true_o
       HIPCHK(h, hipcub::DeviceRadixSort::SortKeys(nullptr, tb, db, (int)Pmax, 0, 64, h->stream));
       if ((rc = tm.get(&ts, tb, "the sort of the positives"))) return rc;
     }
-    const unsigned gridw = sc_grid(T, 8192);
+    const unsigned gridw = grid_for(T, SC_TPB, 8192);
     for (int l = 0; l < L; ++l) {
       const unsigned long long P = conf_h[(size_t)l * VMR_SCORE_NCONF + 4], Q = n_ties - P;
       if (!P || !Q) continue;

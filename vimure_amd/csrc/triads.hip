@@ -23,8 +23,7 @@
 // the workgroup of output tile (I, K) accumulates its 64 x 64 tiles of P P^T, P P and U U over j in registers (4 x 4 per thread,
 // operands in LDS), multiplies them into P_ik, P_ki and U_ik and reduces, together with the tile's elementwise sums.  Per-workgroup
 // partials on a grid that depends on N only, one workgroup per layer to finish in a fixed order -- no floating-point atomics.
-#include "vmr_internal.h"
-#include "ppc_layer.h"   // Tmp
+#include "read_side.h"   // Tmp, wave_sum_ull
 
 namespace {
 
@@ -72,12 +71,6 @@ __global__ __launch_bounds__(256) void k_tri_pack(const uint8_t* __restrict__ Y,
       }
     }
   }
-}
-
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += (unsigned long long)__shfl_xor((long long)v, o, 64);
-  return v;
 }
 
 // One wave per (node i = 4 blockIdx.x + wave, layer, sample); G = 1 << lG lanes per neighbour, 64 / G neighbours per step.
@@ -150,8 +143,8 @@ __global__ __launch_bounds__(256) void k_tri_count(const unsigned long long* __r
         }
       }
     }
-    trans = wave_sum_u64(trans); cyc = wave_sum_u64(cyc); tri2 = wave_sum_u64(tri2);
-    const unsigned long long so = wave_sum_u64(dout), si = wave_sum_u64(din), sm = wave_sum_u64(mut), sd = wave_sum_u64(deg);
+    trans = wave_sum_ull(trans); cyc = wave_sum_ull(cyc); tri2 = wave_sum_ull(tri2);
+    const unsigned long long so = wave_sum_ull(dout), si = wave_sum_ull(din), sm = wave_sum_ull(mut), sd = wave_sum_ull(deg);
     if (lane == 0) {
       const unsigned long long two = si * so - sm, wedges = sd * (sd - (sd ? 1ull : 0ull)) / 2ull;
       if (trans) atomicAdd(&tot[0], trans);
