@@ -309,6 +309,43 @@ int vmr_sample_triads(vmr_handle h, uint64_t seed, int n_samples, int n_trials, 
  * VMR_ESTATE.  Synchronises. */
 int vmr_expected_triads(vmr_handle h, double* out);
 
+/* Mixing by node attribute and overlap between layers of n_samples posterior samples of Y, computed where rho lives -- what a
+ * user otherwise gets from `np.add.at` and boolean products in NumPy on every `sample_inferred_model` draw.  Sample s is exactly
+ * what vmr_sample(h, seed + s, n_trials, ..) writes (seed + s mod 2^64).  group: host int32 [N], group[i] in [0, C), or -1 for a
+ * node that is left out of mix and mutual (it still counts in overlap); skip_diagonal != 0 leaves (i, i) out of all three tables.
+ * Host outputs, any of which may be NULL but not all three:
+ *   mix[s][l][a][b]     #{(i,j) : g_i = a, g_j = b, Y_lij > 0}                                    uint64 [n_samples][L][C][C]
+ *   mutual[s][l][a][b]  #{(i,j) : g_i = a, g_j = b, Y_lij > 0 and Y_lji > 0}, ordered pairs: symmetric in (a, b); a kept
+ *                       self-loop counts once, as in vmr_sample_stats                              uint64 [n_samples][L][C][C]
+ *   overlap[s][l][l']   #{(i,j) : Y_lij > 0 and Y_l'ij > 0}: symmetric, its diagonal is the edge count   uint64 [n_samples][L][L]
+ * group = NULL with C = 0 is allowed when only overlap is asked for.  VMR_EINVAL, with a message that names the argument: C
+ * outside [1, VMR_MIX_CMAX] while mix or mutual is asked for (or group NULL then), a label outside [-1, C), L > VMR_MIX_LMAX with
+ * overlap asked for, n_samples < 1, n_trials < 1, all three outputs NULL.  Before vmr_set_state: VMR_ESTATE.
+ * One workgroup per (strip of 64 rows, sample) walks the strip's tiles with the layers innermost: the L bytes of a tie meet in one
+ * thread (ballots and popcounts give the overlap), the transposed tile goes through LDS (mutual), the counters are integers in
+ * LDS (per row and layer one LDS atomic instruction, lane b adding the row's edges into group b: at most one add per edge),
+ * flushed with 64-bit global integer atomics.  All sums are integer sums: bit-identical from run
+ * to run.  Reads the CURRENT rho (after vmr_restore: the snapshot's) once per chunk of samples; any K, both data formats.  A
+ * chunk (L N^2 bytes per sample plus the tables; half of the free device memory at most, 256 samples at most, VMR_NETSTATS_CHUNK
+ * at most) is freed before return, on every exit path; a single sample that does not fit is refused with VMR_EINVAL.
+ * Synchronises. */
+#define VMR_MIX_CMAX 64   /* groups at most */
+#define VMR_MIX_LMAX 32   /* layers at most when overlap is asked for */
+int vmr_sample_mixing(vmr_handle h, uint64_t seed, int n_samples, int n_trials, const int32_t* group, int C, int skip_diagonal,
+                      uint64_t* mix, uint64_t* mutual, uint64_t* overlap);
+
+/* The same tables in expectation under q(Y) = prod rho, no sampling: with p_lij = sum_{k>=1} rho_lijk (k ascending, the number
+ * of vmr_expected_stats),
+ *   mix[l][a][b]     sum_{g_i = a, g_j = b} p_lij                                                  host double [L][C][C]
+ *   mutual[l][a][b]  sum_{g_i = a, g_j = b} p_lij p_lji; a kept diagonal enters as p_ii^2, as in vmr_expected_stats   [L][C][C]
+ *   overlap[l][l']   sum_ij p_lij p_l'ij for l != l', sum_ij p_lij for l = l'                         host double [L][L]
+ * Distinct ties, and distinct layers, are independent under the mean field, so these are exact expectations of the counts (but
+ * for the kept diagonal of mutual); a ratio of two of them is not the expectation of the ratio.  Doubles summed in a fixed order
+ * -- a wave per row with a fixed shuffle tree per group, then one thread per entry over the rows in ascending i -- on grids that
+ * depend on N, L and C only, no atomics: bit-identical from run to run.  Arguments as for vmr_sample_mixing.  Temporaries: P,
+ * 8 L N^2 bytes, and the rows' sums, 16 L N C + 8 N L^2 bytes; one that does not fit is refused with VMR_EINVAL.  Synchronises. */
+int vmr_expected_mixing(vmr_handle h, const int32_t* group, int C, int skip_diagonal, double* mix, double* mutual, double* overlap);
+
 /* Posterior predictive checks: n_rep replicated datasets drawn from the fitted model over the support of the handle's own R and
  * reduced where they are drawn -- no replicate is ever written -- and the same reduction of the observed data.
  * Replicate r: Y_r is exactly what vmr_sample(h, seed_y + r, n_trials, ..) writes (mod 2^64; the CURRENT rho, after vmr_restore

@@ -15,6 +15,7 @@ READ_RHO_MAX, READ_RHO_MEAN, READ_THRESHOLD = 0, 1, 2
 PPC_NSTAT = 6
 TRIAD_NSTAT = 6
 TRIAD_NAMES = ["transitive", "cyclic", "two_paths", "triangles_u", "wedges_u", "edges_u"]
+MIX_CMAX, MIX_LMAX = 64, 32
 EDGE_REPORTED, EDGE_INFERRED = 1, 2
 SCORE_RHO1, SCORE_PROB = 0, 1
 SCORE_NCONF, SCORE_NSUM, SCORE_MAX_THR = 5, 4, 4096
@@ -69,6 +70,8 @@ SIGNATURES = {
     "vmr_expected_stats": (C.c_int, [C.c_void_p, C.c_void_p]),
     "vmr_sample_triads": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vmr_expected_triads": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "vmr_sample_mixing": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vmr_expected_mixing": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vmr_ppc_replicates": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
     "vmr_ppc_observed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -52,6 +52,12 @@ class TriadArgumentError(EngineError, ValueError):
     not fit in the free device memory."""
 
 
+class MixingArgumentError(EngineError, ValueError):
+    """An argument `sample_mixing` / `expected_mixing` refuse (VMR_EINVAL): C outside [1, 64] with groups given, a label outside
+    [-1, C), more than 32 layers with the overlap asked for, n_samples or n_trials below 1, nothing asked for, temporaries that do
+    not fit in the free device memory."""
+
+
 SCORE_OUTPUTS = ("hist", "conf", "sums", "auc", "auc_pairs")
 INF_SELECT = {"none": 0, "lost": _lib.INF_LOST, "gained": _lib.INF_GAINED, "both": _lib.INF_LOST | _lib.INF_GAINED}
 # columns of the table of `CaviEngine.reporter_influence`, in the order of vmr_reporter_influence's row pointers
@@ -471,6 +477,66 @@ class CaviEngine:
         out = np.zeros((self.L, _lib.TRIAD_NSTAT), np.float64)
         self._check_triads(self.lib.vmr_expected_triads(self._h, out.ctypes.data))
         return {k: out[:, q].copy() for q, k in enumerate(_lib.TRIAD_NAMES)}
+
+    def _mixing_args(self, groups, C):
+        """(codes int32 [N] or None, C) for the mixing calls: C None is the largest code + 1."""
+        if groups is None:
+            return None, 0
+        g = np.asarray(groups)
+        if g.shape != (self.N,) or g.dtype.kind not in "iu":
+            raise ValueError(f"groups must be {self.N} integer codes (-1: the node is left out), got {g.dtype} {g.shape}")
+        g = np.ascontiguousarray(np.clip(g.astype(np.int64), -2, 2 ** 31 - 1), dtype=np.int32)   # (out of range stays out of range)
+        return g, int(g.max(initial=-1)) + 1 if C is None else int(C)
+
+    def _check_mixing(self, rc):
+        if rc == _lib.VMR_EINVAL:
+            raise MixingArgumentError(self.lib.vmr_last_error(self._h).decode())
+        self._check(rc)
+
+    def sample_mixing(self, seed, n_samples, groups=None, C=None, n_trials=1, skip_diagonal=True, overlap=True):
+        """Mixing by node attribute and overlap between layers of n_samples posterior samples, computed on the device
+        (vmr_sample_mixing): sample s is `self.sample(seed + s, n_trials)`.  groups: N integer codes in [0, C), -1 for a node that is
+        left out of `mix` and `mutual` (C None: the largest code + 1); skip_diagonal leaves (i, i) out of every table.  Returns a
+        dict of int64 arrays: with groups `mix` [S, L, C, C], mix[s, l, a, b] = #{(i, j) : g_i = a, g_j = b, Y_lij > 0}, and
+        `mutual`, the same over the ties with Y_lji > 0 too (ordered pairs: symmetric in (a, b), a kept self-loop counts once);
+        with overlap=True `overlap` [S, L, L], #{(i, j) : Y_lij > 0 and Y_l'ij > 0} over all nodes, labelled or not (its diagonal
+        is the edge count).  A refused argument raises `MixingArgumentError` with the library's message."""
+        S = int(n_samples)
+        g, C = self._mixing_args(groups, C)
+        grp = g is not None
+        shape = (max(S, 0), self.L, max(C, 0), max(C, 0))
+        mix = np.zeros(shape, np.uint64) if grp else None
+        mut = np.zeros(shape, np.uint64) if grp else None
+        ov = np.zeros((max(S, 0), self.L, self.L), np.uint64) if overlap else None
+        self._check_mixing(self.lib.vmr_sample_mixing(self._h, int(seed) & (2 ** 64 - 1), S, int(n_trials), g.ctypes.data if grp else None, C,
+                                                      int(bool(skip_diagonal)), mix.ctypes.data if grp else None,
+                                                      mut.ctypes.data if grp else None, ov.ctypes.data if overlap else None))
+        out = {}
+        if grp:
+            out["mix"], out["mutual"] = mix.astype(np.int64), mut.astype(np.int64)
+        if overlap:
+            out["overlap"] = ov.astype(np.int64)
+        return out
+
+    def expected_mixing(self, groups=None, C=None, skip_diagonal=True, overlap=True):
+        """The tables of `sample_mixing` in expectation under q(Y) = prod rho (vmr_expected_mixing), no sampling, with p_lij =
+        sum_{k>=1} rho_lijk: dict of float64 arrays `mix` [L, C, C] sum p_lij and `mutual` sum p_lij p_lji over g_i = a, g_j = b (a
+        kept diagonal enters as p_ii^2), `overlap` [L, L] sum_ij p_lij p_l'ij (sum p_lij on its diagonal).  Expectations of counts:
+        a ratio of two of them is not the expectation of the ratio."""
+        g, C = self._mixing_args(groups, C)
+        grp = g is not None
+        mix = np.zeros((self.L, max(C, 0), max(C, 0)), np.float64) if grp else None
+        mut = np.zeros((self.L, max(C, 0), max(C, 0)), np.float64) if grp else None
+        ov = np.zeros((self.L, self.L), np.float64) if overlap else None
+        self._check_mixing(self.lib.vmr_expected_mixing(self._h, g.ctypes.data if grp else None, C, int(bool(skip_diagonal)),
+                                                        mix.ctypes.data if grp else None, mut.ctypes.data if grp else None,
+                                                        ov.ctypes.data if overlap else None))
+        out = {}
+        if grp:
+            out["mix"], out["mutual"] = mix, mut
+        if overlap:
+            out["overlap"] = ov
+        return out
 
     def sub_step(self, which):
         self._check(self.lib.vmr_sub_step(self._h, int(which)))

@@ -755,6 +755,44 @@ class VimureModel(TransformerMixin, BaseEstimator):
         return NetworkStats(self.N, counts, expected=expected, ref_edges=ref_edges, seed=seed, n_trials=n_trials, triads=tri,
                             expected_triads=exp_tri)
 
+    def posterior_mixing(self, groups=None, n_samples=100, seed=None, n_trials=1, skip_diagonal=True, overlap=True, X=None, R=None):
+        """Who is tied to whom, by group, and how far the layers' ties coincide, over the posterior of the network, computed on
+        the GPU (vmr_sample_mixing, vmr_expected_mixing): n_samples draws of Y from q(Y) -- sample s is
+        `sample_inferred_model(N=n_trials, seed=seed + s, device=True)[0]` -- reduced where rho lives to the mixing matrix
+        mix[s, l, a, b] = #{(i, j) : g_i = a, g_j = b, Y_lij > 0}, its reciprocated part and the overlap between layers
+        #{(i, j) : Y_lij > 0 and Y_l'ij > 0}; only those integers cross PCIe.
+        groups: N labels of any kind in node order (strings, ints; None or NaN: the node is left out of the mixing matrix, not
+        of the overlap), or a dict / pandas Series keyed by node name (the `nodeNames` of a model fitted from an edge list, the
+        node's index otherwise; an unknown name is a ValueError, a node that is not named is left out;
+        `mixing.groups_from_frame` makes one from a node table).  Codes follow `np.unique`'s order, 64 groups at most.
+        groups None: the overlap only.  skip_diagonal leaves the self-loops out of every table.  Returns a `mixing.MixingStats`:
+        the integer tables, assortativity, E-I index, block densities and reciprocities, the layers' Jaccard index, the analytic
+        expectations (`expected`: their ratios are ratios of expectations), `summary()` and `frame()`.  seed None: the fit's.
+        Engine as in `calculate_mean_poisson`."""
+        from .mixing import MixingStats, encode_groups
+        if seed is None:
+            seed = self.seed
+        codes = labels = None
+        if groups is not None:
+            names = getattr(self, "nodeNames", None)
+            if names is not None:
+                names = names.sort_values("id")["name"].tolist()
+            codes, labels = encode_groups(groups, self.N, names)
+            if len(labels) < 1:
+                raise ValueError("groups labels no node")
+        elif not overlap:
+            raise ValueError("nothing to compute: no groups and overlap=False")
+        eng, tmp = self._ppc_engine(X, R)
+        try:
+            C = None if codes is None else len(labels)
+            counts = eng.sample_mixing(seed, n_samples, groups=codes, C=C, n_trials=n_trials, skip_diagonal=skip_diagonal, overlap=overlap)
+            expected = eng.expected_mixing(groups=codes, C=C, skip_diagonal=skip_diagonal, overlap=overlap)
+        finally:
+            if tmp:
+                eng.close()
+        return MixingStats(self.N, counts, codes=codes, labels=labels, expected=expected, skip_diagonal=skip_diagonal, seed=seed,
+                           n_trials=n_trials)
+
     def posterior_predictive_check(self, n_rep=100, seed=None, params="draw", n_trials=1, by_reporter=False, X=None, R=None):
         """Does data drawn from the fitted model look like the data it was fitted to?  n_rep replicated datasets are drawn on the
         GPU over the support of R and reduced there (vmr_ppc_replicates; no replicate is written) to the integers of
