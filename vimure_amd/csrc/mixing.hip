@@ -2,7 +2,7 @@
 // vmr_expected_mixing.
 //
 // The other read-outs treat the nodes as unlabelled and every layer on its own.  Given a group code per node (g_i in [0, C), -1:
-// the node is left out) vmr_sample_mixing draws S posterior samples of Y with ns_draw_chunk (sample s is what
+// the node is left out) vmr_sample_mixing draws S posterior samples of Y in chunks (sampled_side.h: sample s is what
 // vmr_sample(h, seed + s, n_trials) writes) and returns, per sample,
 //     mix[l][a][b]     #{(i,j) : g_i = a, g_j = b, Y_lij > 0}                    the mixing matrix of layer l
 //     mutual[l][a][b]  #{(i,j) : g_i = a, g_j = b, Y_lij > 0 and Y_lji > 0}      its reciprocated part (ordered pairs)
@@ -10,39 +10,28 @@
 // (include/vimure_hip.h has the contract).
 //
 // Layout.  A chunk's Y[c][L][N][N] bytes are reduced in natural order by k_mix_reduce, one workgroup (4 waves) per (strip of 64
-// rows, sample) -- k_ns_reduce's walk with the layer loop INSIDE the tile loop: wave w takes rows r = 4 it + w of tile (bi, bj)
-// with lane = column, so the L bytes of one tie meet in one thread, which keeps them as a bit mask per row (L <= 32) -- a ballot
-// per layer and a popcount per pair of layers give the overlap.  The transposed tile (bj, bi) of a layer goes through LDS as in
-// k_ns_reduce, for `mutual`.  The group codes (int8) of the strip's rows sit in LDS for the whole walk, the code of a lane's
-// column in a register for the tile.  The counters are 32-bit words of the workgroup's LDS -- mix and mutual of LB layers at a
+// rows, sample) -- the strip walk of sampled_side.h with the layer loop INSIDE the tile loop, so the L bytes of one tie meet in one
+// thread, which keeps them as a bit mask per row (L <= 32) -- a ballot per layer and a popcount per pair of layers give the
+// overlap.  The transposed tile of a layer is loaded for `mutual` only.  The group codes (int8) of the strip's rows sit in LDS for
+// the whole walk, the code of a lane's column in a register for the tile.  The counters are 32-bit words of the workgroup's LDS -- mix and mutual of LB layers at a
 // time ([LB][C][C] each, MIX_LDS_BINS bytes at most: the walk is repeated per round of LB layers, only the first round reads every
 // layer and forms the overlap), then [L][L].  A row's edges reach them by one LDS atomic instruction per (row, layer): per tile
 // lane b < C keeps the ballot of the columns of group b, the row's ballot of edges ANDed with it and popcounted is what lane b adds
 // to bin (g_row, b) -- a bin per lane, so no two lanes of the instruction meet, and never more adds than the row has edges
 // (samples are sparse: a few edges per row of 64 ties; rows without an edge add nothing).  The non-zero counters are flushed with
 // 64-bit global atomics: sums of integers, the same from run to run in any order.
-// Bytes per chunk of c samples: rho once (8 L N^2 K), Y written once (c L N^2) and read once or, with `mutual`, twice per round.
+// A chunk's Y is read once or, with `mutual`, twice per round.
 //
 // vmr_expected_mixing: the same tables in expectation under q(Y) = prod rho.  P comes from ns_exp_p; the host sorts the labelled
 // nodes by group (order, goff: group b is order[goff[b] .. goff[b + 1]), ascending node), so that one wave per (row, layer) sums
 // the row's columns group by group -- a fixed lane stride and a fixed shuffle tree per group -- into Rw[l][i][b], and one thread
 // per (l, a, b) adds the rows of group a in ascending i.  The overlap: one wave per row and a pair of layers at a time, then one
 // thread per pair over the rows in ascending i.  No atomics, grids of N, L and C only: bit-identical from run to run.
-#include "read_side.h"   // Tmp, grid_for
+#include "sampled_side.h"
 
 namespace {
 
-#define MIX_TILE 64
-#define MIX_BSTRIDE 68          // bytes per row of the transposed tile in LDS (k_ns_reduce's: 17 words, odd)
 #define MIX_LDS_BINS (40 << 10)   // bytes of mix / mutual counters a workgroup keeps in LDS at most: the layers of one round
-
-// the workgroup's n 32-bit LDS counters -> 64-bit global ones, the non-zero ones (flush_bins of read_side.h for 32-bit words)
-__device__ __forceinline__ void flush_bins32(const unsigned* lds, u64* __restrict__ bins, int n) {
-  for (int q = threadIdx.x; q < n; q += 256) {
-    const unsigned u = lds[q];
-    if (u) atomicAdd(bins + q, (u64)u);
-  }
-}
 
 // One workgroup per (strip bi of 64 rows, sample s).  group: int8 [N] or null (no mix, no mutual); mixg / mutg: [c][L][C][C],
 // ovg: [c][L][L], any of them null.  LB: layers per round (L when there are no group tables).  MUT: mutg is asked for.
@@ -50,19 +39,19 @@ template <bool MUT>
 __global__ __launch_bounds__(256) void k_mix_reduce(const uint8_t* __restrict__ Y, const int8_t* __restrict__ group, int N, int L, int C, int LB, int skip,
                                                     u64* __restrict__ mixg, u64* __restrict__ mutg, u64* __restrict__ ovg) {
   extern __shared__ unsigned bins_s[];   // [LB][C][C] mix, [LB][C][C] mutual (each when asked for), [L][L] overlap (when asked for)
-  __shared__ uint8_t Bs[MUT ? MIX_TILE * MIX_BSTRIDE : 4];
-  __shared__ int gi_s[MIX_TILE];
+  __shared__ uint8_t Bs[MUT ? SS_TILE * SS_BSTRIDE : 4];
+  __shared__ int gi_s[SS_TILE];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int bi = blockIdx.x, s = blockIdx.y;
   const size_t T = (size_t)N * N;
   const uint8_t* Ys = Y + (size_t)s * L * T;
-  const int i0 = bi * MIX_TILE, nb = (N + MIX_TILE - 1) / MIX_TILE, C2 = C * C;
+  const int i0 = bi * SS_TILE, nb = (N + SS_TILE - 1) / SS_TILE, C2 = C * C;
   const bool grp_any = mixg != nullptr || (MUT && mutg != nullptr);
   unsigned* mixb = mixg ? bins_s : nullptr;
   unsigned* mutb = bins_s + (mixg ? LB * C2 : 0);
   const int ngrp = grp_any ? ((mixg ? 1 : 0) + (MUT ? 1 : 0)) * LB * C2 : 0;
   unsigned* ovb = bins_s + ngrp;
-  if (threadIdx.x < MIX_TILE) gi_s[threadIdx.x] = (grp_any && i0 + (int)threadIdx.x < N) ? (int)group[i0 + threadIdx.x] : -1;
+  if (threadIdx.x < SS_TILE) gi_s[threadIdx.x] = (grp_any && i0 + (int)threadIdx.x < N) ? (int)group[i0 + threadIdx.x] : -1;
   if (ovg)
     for (int q = threadIdx.x; q < L * L; q += 256) ovb[q] = 0u;
   for (int l0 = 0; l0 < L; l0 += LB) {
@@ -71,29 +60,26 @@ __global__ __launch_bounds__(256) void k_mix_reduce(const uint8_t* __restrict__ 
     for (int q = threadIdx.x; q < ngrp; q += 256) bins_s[q] = 0u;
     __syncthreads();
     for (int bj = 0; bj < nb; ++bj) {
-      const int j0 = bj * MIX_TILE, j = j0 + lane;
+      const int j0 = bj * SS_TILE, j = j0 + lane;
       const int gc = (grp_any && j < N) ? (int)group[j] : -1;
       u64 cmv = 0ull;   // lane b < C: the tile's columns of group b (a column out of range or left out is in no group)
       for (int b = 0; b < C; ++b) {
         const u64 mb = __ballot(gc == b);
         if (lane == b) cmv = mb;
       }
-      unsigned m[MIX_TILE / 4];   // bit l of m[it]: tie (row 4 it + w, column lane) is an edge of layer l
+      unsigned m[SS_TILE / 4];   // bit l of m[it]: tie (row 4 it + w, column lane) is an edge of layer l
 #pragma unroll
-      for (int it = 0; it < MIX_TILE / 4; ++it) m[it] = 0u;
+      for (int it = 0; it < SS_TILE / 4; ++it) m[it] = 0u;
       for (int l = ov ? 0 : l0; l < (ov ? L : l1); ++l) {
         const uint8_t* Yl = Ys + (size_t)l * T;
         const bool grp = grp_any && l >= l0 && l < l1;   // (uniform over the workgroup)
         if (MUT && grp) {
           __syncthreads();   // (the last tile's reads of Bs are done)
-          for (int it = 0; it < MIX_TILE / 4; ++it) {
-            const int c = it * 4 + w, jj = j0 + c, ii = i0 + lane;
-            Bs[c * MIX_BSTRIDE + lane] = (jj < N && ii < N) ? Yl[(size_t)jj * N + ii] : (uint8_t)0;
-          }
+          tile_transposed(Bs, Yl, i0, j0, N);
           __syncthreads();
         }
 #pragma unroll
-        for (int it = 0; it < MIX_TILE / 4; ++it) {
+        for (int it = 0; it < SS_TILE / 4; ++it) {
           const int r = it * 4 + w, i = i0 + r;
           const bool in = i < N && j < N && !(skip && i == j);
           const bool a = in && Yl[(size_t)i * N + j] > 0;
@@ -105,7 +91,7 @@ __global__ __launch_bounds__(256) void k_mix_reduce(const uint8_t* __restrict__ 
             const unsigned n = (unsigned)__popcll(ba & cmv);
             if (mixb && n) atomicAdd(&mixb[q], n);
             if (MUT) {
-              const u64 bm = __ballot(a && Bs[lane * MIX_BSTRIDE + r] > 0);   // Y[j][i] > 0: in range, and off the skipped diagonal, as a is
+              const u64 bm = __ballot(a && Bs[lane * SS_BSTRIDE + r] > 0);   // Y[j][i] > 0: in range, and off the skipped diagonal, as a is
               const unsigned nm = (unsigned)__popcll(bm & cmv);
               if (nm) atomicAdd(&mutb[q], nm);
             }
@@ -114,7 +100,7 @@ __global__ __launch_bounds__(256) void k_mix_reduce(const uint8_t* __restrict__ 
       }
       if (ov) {
 #pragma unroll
-        for (int it = 0; it < MIX_TILE / 4; ++it) {
+        for (int it = 0; it < SS_TILE / 4; ++it) {
           if (!__ballot(m[it] != 0u)) continue;   // (uniform over the wave) no edge in this row of the tile, in any layer
           for (int l = 0; l < L; ++l) {
             const u64 bl = __ballot((m[it] >> l) & 1u);
@@ -132,11 +118,11 @@ __global__ __launch_bounds__(256) void k_mix_reduce(const uint8_t* __restrict__ 
     }
     __syncthreads();
     const size_t o = ((size_t)s * L + l0) * C2;
-    if (mixg) flush_bins32(mixb, mixg + o, (l1 - l0) * C2);
-    if (MUT && mutg) flush_bins32(mutb, mutg + o, (l1 - l0) * C2);
+    if (mixg) flush_bins(mixb, mixg + o, (l1 - l0) * C2, 256);
+    if (MUT && mutg) flush_bins(mutb, mutg + o, (l1 - l0) * C2, 256);
     __syncthreads();   // (the next round zeroes the counters)
   }
-  if (ovg) flush_bins32(ovb, ovg + (size_t)s * L * L, L * L);
+  if (ovg) flush_bins(ovb, ovg + (size_t)s * L * L, L * L, 256);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -253,40 +239,25 @@ int mix_check_args(vmr_ctx* h, const char* fn, const int32_t* group, int C, bool
 
 extern "C" int vmr_sample_mixing(vmr_handle h, uint64_t seed, int n_samples, int n_trials, const int32_t* group, int C, int skip_diagonal,
                                  uint64_t* mix, uint64_t* mutual, uint64_t* overlap) {
-  if (!h) return VMR_EINVAL;
-  if (n_samples < 1) return fail(h, VMR_EINVAL, "vmr_sample_mixing: n_samples must be positive");
-  if (n_trials < 1) return fail(h, VMR_EINVAL, "vmr_sample_mixing: n_trials must be positive");
   const bool want_grp = mix || mutual;
   int rc;
-  if ((rc = mix_check_args(h, "vmr_sample_mixing", group, C, want_grp, overlap != nullptr))) return rc;
-  if (!h->have_state) return fail(h, VMR_ESTATE, "vmr_set_state must be called before vmr_sample_mixing");
-  HIPCHK(h, hipSetDevice(h->device));
-  { const int rce = ensure_rho_ext(h); if (rce) return rce; }
+  if ((rc = sampled_counts(h, "vmr_sample_mixing", n_samples, n_trials)) ||
+      (rc = mix_check_args(h, "vmr_sample_mixing", group, C, want_grp, overlap != nullptr)) || (rc = expected_begin(h, "vmr_sample_mixing")))
+    return rc;
   const Geo& g = h->g;
   if (!want_grp) C = 0;
-  const size_t T = (size_t)g.N * g.N, ties = (size_t)g.L * T;
-  const size_t C2 = (size_t)C * C, grp_b = (size_t)g.L * C2 * 8, ov_b = (size_t)g.L * g.L * 8;
+  const size_t ties = (size_t)g.L * g.N * g.N, C2 = (size_t)C * C, grp_b = (size_t)g.L * C2 * 8, ov_b = (size_t)g.L * g.L * 8;
+  SampledOut out[3] = {{mix, grp_b, true, "vmr_sample_mixing: the mixing counts"},
+                       {mutual, grp_b, true, "vmr_sample_mixing: the mutual counts"},
+                       {overlap, ov_b, true, "vmr_sample_mixing: the overlap counts"}};
   const size_t per = ties + (mix ? grp_b : 0) + (mutual ? grp_b : 0) + (overlap ? ov_b : 0);   // device bytes per sample of a chunk
-  size_t fr = 0, tot = 0;
-  HIPCHK(h, hipMemGetInfo(&fr, &tot));
-  // half of the free memory at most, 64 MB left alone in any case
-  const size_t budget = fr / 2 > (64u << 20) ? fr / 2 - (64u << 20) : 0;
-  size_t S = std::min<size_t>(std::min<size_t>((size_t)n_samples, NS_CHUNK_MAX), budget / per);
-  if (h->opt.netstats_chunk > 0) S = std::min<size_t>(S, (size_t)h->opt.netstats_chunk);
-  if (S < 1) {
-    char msg[256];
-    snprintf(msg, sizeof msg, "vmr_sample_mixing: one sample's temporaries need %.3f GB of device memory, %.3f GB are free", per / 1e9, fr / 1e9);
-    return fail(h, VMR_EINVAL, msg);
-  }
+  size_t S;
+  if ((rc = chunk_samples(h, "vmr_sample_mixing", (size_t)n_samples, per, 0, &S))) return rc;
   std::vector<int8_t> codes;   // (outlives the temporaries: their release waits for the copy)
   Tmp tm(h);
   uint8_t* Y = nullptr;
   int8_t* gd = nullptr;
-  u64 *md = nullptr, *ud = nullptr, *od = nullptr;
   if ((rc = tm.get(&Y, S * ties, "vmr_sample_mixing: the samples"))) return rc;
-  if (mix && (rc = tm.get(&md, S * grp_b, "vmr_sample_mixing: the mixing counts"))) return rc;
-  if (mutual && (rc = tm.get(&ud, S * grp_b, "vmr_sample_mixing: the mutual counts"))) return rc;
-  if (overlap && (rc = tm.get(&od, S * ov_b, "vmr_sample_mixing: the overlap counts"))) return rc;
   if (want_grp) {
     codes.assign(group, group + g.N);
     if ((rc = tm.get(&gd, (size_t)g.N, "vmr_sample_mixing: the group codes"))) return rc;
@@ -296,38 +267,25 @@ extern "C" int vmr_sample_mixing(vmr_handle h, uint64_t seed, int n_samples, int
   const size_t grp_w = ((mix ? 1 : 0) + (mutual ? 1 : 0)) * C2;
   const int LB = want_grp ? (int)std::max<size_t>(1, std::min<size_t>((size_t)g.L, MIX_LDS_BINS / (grp_w * 4))) : g.L;
   const size_t smem = ((want_grp ? (size_t)LB * grp_w : 0) + (overlap ? (size_t)g.L * g.L : 0)) * 4;
-  const unsigned nstrip = (unsigned)((g.N + MIX_TILE - 1) / MIX_TILE);
-  for (size_t s0 = 0; s0 < (size_t)n_samples; s0 += S) {
-    const int c = (int)std::min<size_t>(S, (size_t)n_samples - s0);
-    if (md) HIPCHK(h, hipMemsetAsync(md, 0, (size_t)c * grp_b, h->stream));
-    if (ud) HIPCHK(h, hipMemsetAsync(ud, 0, (size_t)c * grp_b, h->stream));
-    if (od) HIPCHK(h, hipMemsetAsync(od, 0, (size_t)c * ov_b, h->stream));
-    if ((rc = ns_draw_chunk(h, Y, (unsigned long long)seed + (unsigned long long)s0, c, n_trials))) return rc;   // (mod 2^64)
-    if (mutual)
-      hipLaunchKernelGGL(k_mix_reduce<true>, dim3(nstrip, (unsigned)c), dim3(256), smem, h->stream, Y, gd, g.N, g.L, C, LB, skip_diagonal != 0, md, ud, od);
-    else
-      hipLaunchKernelGGL(k_mix_reduce<false>, dim3(nstrip, (unsigned)c), dim3(256), smem, h->stream, Y, gd, g.N, g.L, C, LB, skip_diagonal != 0, md, ud, od);
+  const unsigned nstrip = (unsigned)((g.N + SS_TILE - 1) / SS_TILE);
+  const auto kern = mutual ? k_mix_reduce<true> : k_mix_reduce<false>;
+  return sampled_chunks(h, tm, (size_t)n_samples, S, seed, n_trials, Y, out, [&](size_t, int c) -> int {
+    hipLaunchKernelGGL(kern, dim3(nstrip, (unsigned)c), dim3(256), smem, h->stream, Y, gd, g.N, g.L, C, LB,
+                       skip_diagonal != 0, out[0].as<u64>(), out[1].as<u64>(), out[2].as<u64>());
     HIPCHK(h, hipGetLastError());
-    if (mix) HIPCHK(h, hipMemcpyAsync(mix + s0 * g.L * C2, md, (size_t)c * grp_b, hipMemcpyDeviceToHost, h->stream));
-    if (mutual) HIPCHK(h, hipMemcpyAsync(mutual + s0 * g.L * C2, ud, (size_t)c * grp_b, hipMemcpyDeviceToHost, h->stream));
-    if (overlap) HIPCHK(h, hipMemcpyAsync(overlap + s0 * g.L * g.L, od, (size_t)c * ov_b, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-  }
-  return VMR_OK;
+    return VMR_OK;
+  });
 }
 
 extern "C" int vmr_expected_mixing(vmr_handle h, const int32_t* group, int C, int skip_diagonal, double* mix, double* mutual, double* overlap) {
   if (!h) return VMR_EINVAL;
   const bool want_grp = mix || mutual;
   int rc;
-  if ((rc = mix_check_args(h, "vmr_expected_mixing", group, C, want_grp, overlap != nullptr))) return rc;
-  if (!h->have_state) return fail(h, VMR_ESTATE, "vmr_set_state must be called before vmr_expected_mixing");
-  HIPCHK(h, hipSetDevice(h->device));
-  { const int rce = ensure_rho_ext(h); if (rce) return rce; }
+  if ((rc = mix_check_args(h, "vmr_expected_mixing", group, C, want_grp, overlap != nullptr)) || (rc = expected_begin(h, "vmr_expected_mixing"))) return rc;
   const Geo& g = h->g;
   if (!want_grp) C = 0;
   const size_t T = (size_t)g.N * g.N, ties = (size_t)g.L * T, C2 = (size_t)C * C;
-  const int nbp = (int)std::max<size_t>(1, std::min<size_t>(1024, (T + 255) / 256));   // k_ns_exp_p's grid, as in vmr_expected_stats
+  const int nbp = exp_p_blocks(T);
   const int skip = skip_diagonal != 0;
   const unsigned nquad = (unsigned)((g.N + 3) / 4);
   std::vector<int8_t> codes;   // (these outlive the temporaries: their release waits for the copies)

@@ -6,13 +6,12 @@
 // layer, over ALL (i, j), the diagonal included:
 //     edges #{Y > 0}, weight sum Y, mutual #{(i,j) : Y_ij > 0 and Y_ji > 0}, tp #{Y > 0 and y_ref > 0}, out- and in-degrees.
 //
-// Layout.  rho is stored by tie (dense tiles) or by sorted position (report lists: only perm, position -> tie, exists), and
-// `mutual` needs tie (j,i) next to tie (i,j).  So the samples are DRAWN by position -- k_ns_draw: one thread per position reads
-// its rho row once and draws a whole chunk of C samples from it, writing Y[s][l][i][j] as uint8 in natural order through perm --
-// and REDUCED in natural order: k_ns_reduce, one workgroup per (strip of 64 rows, layer, sample), walks the strip's 64 x 64
-// tiles, the transposed tile (bj, bi) going through LDS.  The workgroup of strip bi thereby sees all of rows i and all of columns
-// i of its 64 nodes: both degree arrays are plain stores, no atomics.  rho (8 L N^2 K bytes) is read once per chunk; the chunk
-// buffer costs L N^2 bytes per sample, written once and read twice.  No inverse permutation is built.
+// Layout (sampled_side.h has the chunking and the transposed tile).  rho is stored by tie (dense tiles) or by sorted position
+// (report lists: only perm, position -> tie, exists), and `mutual` needs tie (j,i) next to tie (i,j).  So the samples are DRAWN by
+// position -- k_ns_draw: one thread per position reads its rho row once and draws a whole chunk of C samples from it, writing
+// Y[s][l][i][j] through perm -- and REDUCED in natural order: k_ns_reduce, one workgroup per (strip of 64 rows, layer, sample),
+// walks the strip's tiles.  The workgroup of strip bi thereby sees all of rows i and all of columns i of its 64 nodes: both degree
+// arrays are plain stores, no atomics.  The chunk's Y is read twice.  No inverse permutation is built.
 //
 // Every count is an integer: ballots and popcounts inside the wave, a wave sum for the weight, LDS atomics, then one 64-bit
 // global atomic per workgroup, sample and column -- sums of integers, the same from run to run in any order.
@@ -21,13 +20,10 @@
 //     (sum p, sum_ij sum_k k rho_ijk, sum_ij p_ij p_ji, sum p (1 - p)) per layer,
 // p written in natural order by position (k_ns_exp_p), then read with its transpose (k_ns_exp_pairs); sums of doubles by a fixed
 // two-stage tree -- per-workgroup partials on a grid that depends on N only, one workgroup per layer to finish -- no atomics.
-#include "vmr_internal.h"
+#include "sampled_side.h"
 #include "sample_draw.h"
 
 namespace {
-
-#define NS_TILE 64
-#define NS_BSTRIDE 68   // bytes per row of the transposed tile in LDS: 17 words, odd, so a wave's column reads spread over the banks
 
 // A chunk of C samples drawn from one read of rho: Y[s][q's tie] = the draw of (seed0 + s, tie), s in [0, C).
 // LDS_CNT: K > KMAX, the trial counts in LDS (64 threads, [K][64] words); KC > 0: K = KC, the row is held in registers.
@@ -59,31 +55,28 @@ __global__ __launch_bounds__(LDS_CNT ? 64 : 256) void k_ns_draw(const double* __
 // Lane `it` of wave w keeps the degrees of row 4 it + w.
 __global__ __launch_bounds__(256) void k_ns_reduce(const uint8_t* __restrict__ Y, const uint8_t* __restrict__ yref, int N, int L,
                                                    unsigned long long* __restrict__ counts, int32_t* __restrict__ deg_out, int32_t* __restrict__ deg_in) {
-  __shared__ uint8_t Bs[NS_TILE * NS_BSTRIDE];
+  __shared__ uint8_t Bs[SS_TILE * SS_BSTRIDE];
   __shared__ unsigned long long tot[4];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int bi = blockIdx.x, l = blockIdx.y, s = blockIdx.z;
   const size_t T = (size_t)N * N;
   const uint8_t* Ys = Y + ((size_t)s * L + l) * T;
   const uint8_t* Yr = yref ? yref + (size_t)l * T : nullptr;
-  const int i0 = bi * NS_TILE, nb = (N + NS_TILE - 1) / NS_TILE;
+  const int i0 = bi * SS_TILE, nb = (N + SS_TILE - 1) / SS_TILE;
   if (threadIdx.x < 4) tot[threadIdx.x] = 0ull;
   unsigned long long edges = 0, mutual = 0, tp = 0, wsum = 0;   // edges, mutual, tp: uniform over the wave; wsum: per lane
   unsigned dout = 0, din = 0;
   for (int bj = 0; bj < nb; ++bj) {
-    const int j0 = bj * NS_TILE;
+    const int j0 = bj * SS_TILE;
     __syncthreads();   // (the last tile's reads of Bs are done)
-    for (int it = 0; it < NS_TILE / 4; ++it) {
-      const int c = it * 4 + w, jj = j0 + c, ii = i0 + lane;
-      Bs[c * NS_BSTRIDE + lane] = (jj < N && ii < N) ? Ys[(size_t)jj * N + ii] : (uint8_t)0;
-    }
+    tile_transposed(Bs, Ys, i0, j0, N);
     __syncthreads();
     const int j = j0 + lane;
-    for (int it = 0; it < NS_TILE / 4; ++it) {
+    for (int it = 0; it < SS_TILE / 4; ++it) {
       const int r = it * 4 + w, i = i0 + r;
       const bool in = i < N && j < N;
       const unsigned a = in ? Ys[(size_t)i * N + j] : 0u;
-      const unsigned b = Bs[lane * NS_BSTRIDE + r];
+      const unsigned b = Bs[lane * SS_BSTRIDE + r];
       const unsigned long long ba = __ballot(a > 0u), bb = __ballot(b > 0u);
       const unsigned ne = (unsigned)__popcll(ba);
       edges += ne;
@@ -96,15 +89,14 @@ __global__ __launch_bounds__(256) void k_ns_reduce(const uint8_t* __restrict__ Y
       if (lane == it) { dout += ne; din += (unsigned)__popcll(bb); }
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) wsum += (unsigned long long)__shfl_xor((long long)wsum, o, 64);
+  wsum = wave_sum_ull(wsum);
   if (lane == 0) {
     if (edges) atomicAdd(&tot[0], edges);
     if (wsum) atomicAdd(&tot[1], wsum);
     if (mutual) atomicAdd(&tot[2], mutual);
     if (tp) atomicAdd(&tot[3], tp);
   }
-  if (lane < NS_TILE / 4) {
+  if (lane < SS_TILE / 4) {
     const int i = i0 + lane * 4 + w;
     if (i < N) {
       const size_t o = ((size_t)s * L + l) * N + i;
@@ -159,29 +151,10 @@ __global__ __launch_bounds__(256) void k_ns_exp_finish(const double* __restrict_
   __shared__ double red[16];
   const int l = blockIdx.x;
   for (int c = 0; c < 4; ++c) {
-    double a = 0.0;
-    for (int b = threadIdx.x; b < nb; b += 256) a += part[((size_t)l * nb + b) * 4 + c];
-    const double sum = block_sum_n(a, red);
+    const double sum = partials_col_sum(part + (size_t)l * nb * 4, nb, 4, c, red);
     if (threadIdx.x == 0) out[l * 4 + c] = sum;
   }
 }
-
-// temporaries of one call, freed on every exit path
-struct Tmp {
-  std::vector<void*> ptrs;
-  ~Tmp() { for (void* q : ptrs) (void)hipFree(q); }
-  Tmp() = default;
-  Tmp(const Tmp&) = delete;
-  Tmp& operator=(const Tmp&) = delete;
-  template <class T_>
-  int get(vmr_ctx* h, T_** out, size_t bytes) {
-    void* q = nullptr;
-    HIPCHK(h, hipMalloc(&q, bytes ? bytes : 8));
-    ptrs.push_back(q);
-    *out = reinterpret_cast<T_*>(q);
-    return VMR_OK;
-  }
-};
 
 }  // namespace
 
@@ -216,65 +189,43 @@ extern "C" int vmr_sample_stats(vmr_handle h, uint64_t seed, int n_samples, int 
                                 uint64_t* counts, int32_t* deg_out, int32_t* deg_in) {
   if (!h) return VMR_EINVAL;
   if (!counts) return fail(h, VMR_EINVAL, "vmr_sample_stats: counts is NULL");
-  if (n_samples < 1) return fail(h, VMR_EINVAL, "vmr_sample_stats: n_samples must be positive");
-  if (n_trials < 1) return fail(h, VMR_EINVAL, "vmr_sample_stats: n_trials must be positive");
-  if (!h->have_state) return fail(h, VMR_ESTATE, "vmr_set_state must be called before vmr_sample_stats");
-  HIPCHK(h, hipSetDevice(h->device));
-  { const int rce = ensure_rho_ext(h); if (rce) return rce; }
-  const Geo& g = h->g;
-  const size_t T = (size_t)g.N * g.N, ties = (size_t)g.L * T;
-  const size_t cnt_b = (size_t)g.L * 4 * 8, deg_b = (size_t)g.L * g.N * 4;
-  const size_t per = ties + cnt_b + (deg_out ? deg_b : 0) + (deg_in ? deg_b : 0);   // device bytes per sample of a chunk
-  const size_t fixed = (y_ref && !y_ref_on_device) ? ties : 0;
-  size_t fr = 0, tot = 0;
-  HIPCHK(h, hipMemGetInfo(&fr, &tot));
-  // half of the free memory at most, 64 MB left alone in any case
-  const size_t budget = fr / 2 > fixed + (64u << 20) ? fr / 2 - fixed - (64u << 20) : 0;
-  size_t C = std::min<size_t>(std::min<size_t>((size_t)n_samples, NS_CHUNK_MAX), budget / per);
-  if (h->opt.netstats_chunk > 0) C = std::min<size_t>(C, (size_t)h->opt.netstats_chunk);
-  if (C < 1) {
-    char msg[256];
-    snprintf(msg, sizeof msg, "vmr_sample_stats: one sample's temporaries need %.3f GB of device memory, %.3f GB are free", (per + fixed) / 1e9, fr / 1e9);
-    return fail(h, VMR_EINVAL, msg);
-  }
-  Tmp tm;
   int rc;
+  if ((rc = sampled_begin(h, "vmr_sample_stats", n_samples, n_trials))) return rc;
+  const Geo& g = h->g;
+  const size_t ties = (size_t)g.L * g.N * g.N, deg_b = (size_t)g.L * g.N * 4;
+  SampledOut out[3] = {{counts, (size_t)g.L * 4 * 8, true, "vmr_sample_stats: the counts"},
+                       {deg_out, deg_b, false, "vmr_sample_stats: the out-degrees"},
+                       {deg_in, deg_b, false, "vmr_sample_stats: the in-degrees"}};
+  const size_t per = ties + out[0].bytes + (deg_out ? deg_b : 0) + (deg_in ? deg_b : 0);   // device bytes per sample of a chunk
+  const bool upload = y_ref && !y_ref_on_device;
+  size_t C;
+  if ((rc = chunk_samples(h, "vmr_sample_stats", (size_t)n_samples, per, upload ? ties : 0, &C))) return rc;
+  Tmp tm(h);
   uint8_t *Y = nullptr, *yr = nullptr;
-  unsigned long long* cd = nullptr;
-  int32_t *dout = nullptr, *din = nullptr;
-  if ((rc = tm.get(h, &Y, C * ties)) || (rc = tm.get(h, &cd, C * cnt_b))) return rc;
-  if (deg_out && (rc = tm.get(h, &dout, C * deg_b))) return rc;
-  if (deg_in && (rc = tm.get(h, &din, C * deg_b))) return rc;
+  if ((rc = tm.get(&Y, C * ties, "vmr_sample_stats: the samples"))) return rc;
   const uint8_t* yref_dev = y_ref;
-  if (y_ref && !y_ref_on_device) {
-    if ((rc = tm.get(h, &yr, ties))) return rc;
+  if (upload) {
+    if ((rc = tm.get(&yr, ties, "vmr_sample_stats: the reference network"))) return rc;
     HIPCHK(h, hipMemcpyAsync(yr, y_ref, ties, hipMemcpyHostToDevice, h->stream));
     yref_dev = yr;
   }
-  const unsigned nstrip = (unsigned)((g.N + NS_TILE - 1) / NS_TILE);
-  for (size_t s0 = 0; s0 < (size_t)n_samples; s0 += C) {
-    const int c = (int)std::min<size_t>(C, (size_t)n_samples - s0);
-    HIPCHK(h, hipMemsetAsync(cd, 0, (size_t)c * cnt_b, h->stream));
-    if ((rc = ns_draw_chunk(h, Y, (unsigned long long)seed + (unsigned long long)s0, c, n_trials))) return rc;   // (mod 2^64)
-    hipLaunchKernelGGL(k_ns_reduce, dim3(nstrip, (unsigned)g.L, (unsigned)c), dim3(256), 0, h->stream, Y, yref_dev, g.N, g.L, cd, dout, din);
+  const unsigned nstrip = (unsigned)((g.N + SS_TILE - 1) / SS_TILE);
+  return sampled_chunks(h, tm, (size_t)n_samples, C, seed, n_trials, Y, out, [&](size_t, int c) -> int {
+    hipLaunchKernelGGL(k_ns_reduce, dim3(nstrip, (unsigned)g.L, (unsigned)c), dim3(256), 0, h->stream, Y, yref_dev, g.N, g.L,
+                       out[0].as<unsigned long long>(), out[1].as<int32_t>(), out[2].as<int32_t>());
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(counts + s0 * g.L * 4, cd, (size_t)c * cnt_b, hipMemcpyDeviceToHost, h->stream));
-    if (deg_out) HIPCHK(h, hipMemcpyAsync(deg_out + s0 * g.L * g.N, dout, (size_t)c * deg_b, hipMemcpyDeviceToHost, h->stream));
-    if (deg_in) HIPCHK(h, hipMemcpyAsync(deg_in + s0 * g.L * g.N, din, (size_t)c * deg_b, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-  }
-  return VMR_OK;
+    return VMR_OK;
+  });
 }
 
 extern "C" int vmr_expected_stats(vmr_handle h, double* out) {
   if (!h) return VMR_EINVAL;
   if (!out) return fail(h, VMR_EINVAL, "vmr_expected_stats: out is NULL");
-  if (!h->have_state) return fail(h, VMR_ESTATE, "vmr_set_state must be called before vmr_expected_stats");
-  HIPCHK(h, hipSetDevice(h->device));
-  { const int rce = ensure_rho_ext(h); if (rce) return rce; }
+  int rc;
+  if ((rc = expected_begin(h, "vmr_expected_stats"))) return rc;
   const Geo& g = h->g;
   const size_t T = (size_t)g.N * g.N, ties = (size_t)g.L * T;
-  const int nb = (int)std::max<size_t>(1, std::min<size_t>(1024, (T + 255) / 256));   // (of N only: the tree is the same on every device)
+  const int nb = exp_p_blocks(T);
   const size_t need = ties * 8 + (size_t)g.L * nb * 32 + (size_t)g.L * 32;
   size_t fr = 0, tot = 0;
   HIPCHK(h, hipMemGetInfo(&fr, &tot));
@@ -283,10 +234,12 @@ extern "C" int vmr_expected_stats(vmr_handle h, double* out) {
     snprintf(msg, sizeof msg, "vmr_expected_stats: the edge probabilities need %.3f GB of device memory, %.3f GB are free", need / 1e9, fr / 1e9);
     return fail(h, VMR_EINVAL, msg);
   }
-  Tmp tm;
-  int rc;
+  Tmp tm(h);
   double *P = nullptr, *part = nullptr, *od = nullptr;
-  if ((rc = tm.get(h, &P, ties * 8)) || (rc = tm.get(h, &part, (size_t)g.L * nb * 32)) || (rc = tm.get(h, &od, (size_t)g.L * 32))) return rc;
+  if ((rc = tm.get(&P, ties * 8, "vmr_expected_stats: the edge probabilities")) ||
+      (rc = tm.get(&part, (size_t)g.L * nb * 32, "vmr_expected_stats: partial sums")) ||
+      (rc = tm.get(&od, (size_t)g.L * 32, "vmr_expected_stats: the result")))
+    return rc;
   if ((rc = ns_exp_p(h, P, part, nb))) return rc;
   hipLaunchKernelGGL(k_ns_exp_pairs, dim3((unsigned)nb, (unsigned)g.L), dim3(256), 0, h->stream, P, part, g.N);
   HIPCHK(h, hipGetLastError());

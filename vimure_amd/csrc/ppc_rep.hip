@@ -1,7 +1,7 @@
 // ppc_rep.hip -- posterior predictive checks on the device: vmr_ppc_replicates, vmr_ppc_observed.
 //
 // A replicate is data drawn from the fitted model over the support of the handle's own mask: Y_r from rho (the draw of
-// vmr_sample: ns_draw_chunk, netstats.hip), lambda of a tie from the replicate's table at Y_r, and for every unordered pair
+// vmr_sample, in chunks: sampled_side.h), lambda of a tie from the replicate's table at Y_r, and for every unordered pair
 // i < j and every reporter m that R keeps in either direction the pair draw of the generator (report_draw.h: what
 // vmr_generate_x would write at (l,i,j,m) and (l,j,i,m), unclamped).  The reports are never written: they are reduced where
 // they are drawn to VMR_PPC_NSTAT integers per replicate and layer (include/vimure_hip.h has the table), and the observed data is
@@ -18,7 +18,7 @@
 // k_obs: a group per ORDERED tie over the tie's own reports -- the dense row, or the tie's entries of the tie-major index of
 // ppc.hip (value x << 1 | R) -- `mutual` looks the mirror report up (dense: the mirror row; lists: binary search in the mirror
 // tie's entries).  A support element without a report adds nothing to any statistic, so the report lists are walked, not S.
-#include "read_side.h"
+#include "sampled_side.h"
 #include "report_draw.h"
 
 namespace {
@@ -178,9 +178,8 @@ __global__ __launch_bounds__(256) void k_obs(PpcLayer p, int G, unsigned long lo
 
 extern "C" int vmr_ppc_replicates(vmr_handle h, int n_rep, uint64_t seed_y, uint64_t seed_x, int n_trials, const double* theta,
                                   const double* lambda, const double* eta, uint64_t* counts, uint64_t* by_reporter) {
-  if (!h) return VMR_EINVAL;
-  if (n_rep < 1) return fail(h, VMR_EINVAL, "vmr_ppc_replicates: n_rep must be positive");
-  if (n_trials < 1) return fail(h, VMR_EINVAL, "vmr_ppc_replicates: n_trials must be positive");
+  int rc;
+  if ((rc = sampled_counts(h, "vmr_ppc_replicates", n_rep, n_trials, "n_rep"))) return rc;
   if (!theta || !lambda || !eta || !counts) return fail(h, VMR_EINVAL, "vmr_ppc_replicates: theta, lambda, eta or counts is NULL");
   const Geo& g = h->g;
   const size_t T = (size_t)g.N * g.N, ties = (size_t)g.L * T, LM = (size_t)g.L * g.M, LK = (size_t)g.L * g.K;
@@ -188,59 +187,44 @@ extern "C" int vmr_ppc_replicates(vmr_handle h, int n_rep, uint64_t seed_y, uint
     if (!(eta[r] >= 0.0 && eta[r] < 1.0)) return fail(h, VMR_EINVAL, "The mutuality parameter has to be in [0, 1)!");
   if (!table_nonneg(theta, (size_t)n_rep * LM)) return fail(h, VMR_EINVAL, "vmr_ppc_replicates: theta must be finite and non-negative");
   if (!table_nonneg(lambda, (size_t)n_rep * LK)) return fail(h, VMR_EINVAL, "vmr_ppc_replicates: lambda must be finite and non-negative");
-  if (!h->have_state) return fail(h, VMR_ESTATE, "vmr_set_state must be called before vmr_ppc_replicates");
-  HIPCHK(h, hipSetDevice(h->device));
-  { const int rce = ensure_rho_ext(h); if (rce) return rce; }
-  // a chunk of replicates: Y (L N^2 bytes each), the parameters, the outputs -- the chunking rule of vmr_sample_stats
-  const size_t cnt_b = (size_t)g.L * VMR_PPC_NSTAT * 8, rep_b = by_reporter ? LM * 16 : 0, par_b = (LM + LK + 1) * 8;
-  const size_t per = ties + cnt_b + rep_b + par_b;
-  size_t fr = 0, tot = 0;
-  HIPCHK(h, hipMemGetInfo(&fr, &tot));
-  const size_t budget = fr / 2 > (64u << 20) ? fr / 2 - (64u << 20) : 0;
-  size_t C = std::min<size_t>(std::min<size_t>((size_t)n_rep, NS_CHUNK_MAX), budget / per);
-  if (h->opt.netstats_chunk > 0) C = std::min<size_t>(C, (size_t)h->opt.netstats_chunk);
-  if (C < 1) {
-    char msg[256];
-    snprintf(msg, sizeof msg, "vmr_ppc_replicates: one replicate's temporaries need %.3f GB of device memory, %.3f GB are free", per / 1e9, fr / 1e9);
-    return fail(h, VMR_EINVAL, msg);
-  }
+  if ((rc = expected_begin(h, "vmr_ppc_replicates"))) return rc;
+  // a chunk of replicates: Y (L N^2 bytes each), the parameters, the outputs
+  SampledOut out[2] = {{counts, (size_t)g.L * VMR_PPC_NSTAT * 8, true, "the replicates' statistics"},
+                       {by_reporter, LM * 16, true, "the replicates' statistics by reporter"}};
+  const size_t per = ties + out[0].bytes + (by_reporter ? out[1].bytes : 0) + (LM + LK + 1) * 8;
+  size_t C;
+  if ((rc = chunk_samples(h, "vmr_ppc_replicates", (size_t)n_rep, per, 0, &C, "replicate"))) return rc;
   Tmp tm(h);
-  int rc;
   uint8_t* Y = nullptr;
   double *thd = nullptr, *lad = nullptr, *etd = nullptr;
-  unsigned long long *cd = nullptr, *bd = nullptr;
   if ((rc = tm.get(&Y, C * ties, "the replicates' Y")) || (rc = tm.get(&thd, C * LM * 8, "the replicates' theta")) ||
-      (rc = tm.get(&lad, C * LK * 8, "the replicates' lambda")) || (rc = tm.get(&etd, C * 8, "the replicates' eta")) ||
-      (rc = tm.get(&cd, C * cnt_b, "the replicates' statistics")))
+      (rc = tm.get(&lad, C * LK * 8, "the replicates' lambda")) || (rc = tm.get(&etd, C * 8, "the replicates' eta")))
     return rc;
-  if (by_reporter && (rc = tm.get(&bd, C * rep_b, "the replicates' statistics by reporter"))) return rc;
   RepArgs a;
   a.L = g.L; a.N = g.N; a.M = g.M; a.K = g.K; a.W = g.W;
   a.cls = h->rcls; a.Rb = h->Rb; a.rq = h->rq; a.Rm = h->Rm; a.rbase = h->rbase;
-  a.Y = Y; a.theta = thd; a.lambda = lad; a.eta = etd; a.counts = cd; a.byrep = bd;
+  a.Y = Y; a.theta = thd; a.lambda = lad; a.eta = etd;
   // rows of a handle with mask lists are all ones, empty or listed: a pair's support is two lists at most, unless a row is all ones
   a.G = pow2_lanes((h->rq && !h->all_full && 2u * h->rm_maxrow < (unsigned)g.M) ? 2u * h->rm_maxrow : (unsigned)g.M);
   const bool hist = by_reporter && g.M <= PR_HIST_M;
   const size_t smem = hist ? (size_t)g.M * 16 : 0;
   const dim3 grid(walk_blocks(T, 256, a.G, PR_SLOTS), (unsigned)g.L);
-  for (size_t s0 = 0; s0 < (size_t)n_rep; s0 += C) {
-    const size_t c = std::min<size_t>(C, (size_t)n_rep - s0);
-    HIPCHK(h, hipMemcpyAsync(thd, theta + s0 * LM, c * LM * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(lad, lambda + s0 * LK, c * LK * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(etd, eta + s0, c * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemsetAsync(cd, 0, c * cnt_b, h->stream));
-    if (bd) HIPCHK(h, hipMemsetAsync(bd, 0, c * rep_b, h->stream));
-    if ((rc = ns_draw_chunk(h, Y, (unsigned long long)seed_y + (unsigned long long)s0, (int)c, n_trials))) return rc;   // (mod 2^64)
-    a.seed_x = (unsigned long long)seed_x + (unsigned long long)s0;
+  // per chunk: its replicates' parameters go up before the draw, and the reports' seed moves with the first replicate
+  const auto upload = [&](size_t s0, int c) -> int {
+    HIPCHK(h, hipMemcpyAsync(thd, theta + s0 * LM, (size_t)c * LM * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(lad, lambda + s0 * LK, (size_t)c * LK * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(etd, eta + s0, (size_t)c * 8, hipMemcpyHostToDevice, h->stream));
+    return VMR_OK;
+  };
+  return sampled_chunks(h, tm, (size_t)n_rep, C, seed_y, n_trials, Y, out, upload, [&](size_t s0, int c) -> int {
+    a.counts = out[0].as<unsigned long long>(); a.byrep = out[1].as<unsigned long long>();
+    a.seed_x = (unsigned long long)seed_x + (unsigned long long)s0;   // (mod 2^64)
     const dim3 gr(grid.x, grid.y, (unsigned)c);
     if (hist) hipLaunchKernelGGL(k_rep<true>, gr, dim3(256), smem, h->stream, a);
     else hipLaunchKernelGGL(k_rep<false>, gr, dim3(256), 0, h->stream, a);
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(counts + s0 * g.L * VMR_PPC_NSTAT, cd, c * cnt_b, hipMemcpyDeviceToHost, h->stream));
-    if (bd) HIPCHK(h, hipMemcpyAsync(by_reporter + s0 * LM * 2, bd, c * rep_b, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-  }
-  return VMR_OK;
+    return VMR_OK;
+  });
 }
 
 extern "C" int vmr_ppc_observed(vmr_handle h, uint64_t* counts, uint64_t* by_reporter) {

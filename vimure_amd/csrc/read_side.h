@@ -76,11 +76,12 @@ __device__ __forceinline__ u64 order_key(double v) {
   return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
 }
 
-// the workgroup's n LDS bins -> global, the non-zero ones, by integer atomics (tpb threads)
-__device__ __forceinline__ void flush_bins(const u64* lds, u64* __restrict__ bins, int n, int tpb) {
+// the workgroup's n LDS bins (32- or 64-bit words) -> 64-bit global ones, the non-zero ones, by integer atomics (tpb threads)
+template <class W>
+__device__ __forceinline__ void flush_bins(const W* lds, u64* __restrict__ bins, int n, int tpb) {
   for (int q = threadIdx.x; q < n; q += tpb) {
-    const u64 u = lds[q];
-    if (u) atomicAdd(bins + q, u);
+    const W u = lds[q];
+    if (u) atomicAdd(bins + q, (u64)u);
   }
 }
 

@@ -1,15 +1,15 @@
 // triads.hip -- triad statistics of the posterior on the device: vmr_sample_triads, vmr_expected_triads.
 //
 // vmr_sample_stats (netstats.hip) stops at dyads; what measurement error distorts most is the triadic structure -- a missed or
-// invented tie opens or closes up to N - 2 triads.  vmr_sample_triads draws S posterior samples of Y with ns_draw_chunk (sample s
-// is what vmr_sample(h, seed + s, n_trials) writes) and returns per sample and layer, for A = (Y > 0) with the diagonal cleared
+// invented tie opens or closes up to N - 2 triads.  vmr_sample_triads draws S posterior samples of Y in chunks (sampled_side.h: sample
+// s is what vmr_sample(h, seed + s, n_trials) writes) and returns per sample and layer, for A = (Y > 0) with the diagonal cleared
 // and U = A | A^T:  transitive, cyclic, two_paths, triangles_u, wedges_u, edges_u (include/vimure_hip.h has the definitions) and,
 // per node, the triangles of U through it and its degree in U.
 //
 // Layout.  A chunk's Y[c][L][N][N] bytes are packed into two bitsets of 64-bit words, W = ceil(N / 64) per row:
 // Aout[c][L][N][W] (row i: the targets of i) and Ain[c][L][N][W] (row i: the sources of i, i.e. the rows of A^T) -- k_tri_pack,
-// the workgroup layout of k_ns_reduce: a wave's ballot over 64 consecutive bytes of a row is one word of Aout, the transposed
-// 64 x 64 tile through LDS gives the word of Ain.  The diagonal bit is cleared there, the bits at and above N are zero.
+// the strip walk of sampled_side.h: a wave's ballot over 64 consecutive bytes of a row is one word of Aout, the transposed tile
+// gives the word of Ain.  The diagonal bit is cleared there, the bits at and above N are zero.
 // k_tri_count: one wave per (node i, layer, sample).  It lists the neighbours of i in U (block of TRI_BLK words at a time: a
 // wave scan of the words' popcounts gives every lane its place in the wave's LDS list), then walks the list 64 / G neighbours per
 // step, G = the largest power of two <= min(W, 64) lanes striding over the W words of a neighbour's rows:
@@ -23,12 +23,10 @@
 // the workgroup of output tile (I, K) accumulates its 64 x 64 tiles of P P^T, P P and U U over j in registers (4 x 4 per thread,
 // operands in LDS), multiplies them into P_ik, P_ki and U_ik and reduces, together with the tile's elementwise sums.  Per-workgroup
 // partials on a grid that depends on N only, one workgroup per layer to finish in a fixed order -- no floating-point atomics.
-#include "read_side.h"   // Tmp, wave_sum_ull
+#include "sampled_side.h"
 
 namespace {
 
-#define TRI_TILE 64
-#define TRI_BSTRIDE 68   // bytes per row of the transposed tile in LDS (k_ns_reduce's: 17 words, odd)
 #define TRI_BLK 32       // words of row i whose neighbours are listed at a time
 #define TRI_LIST (TRI_BLK * 64)
 
@@ -38,31 +36,28 @@ namespace {
 // as 0, so do the diagonal elements: the pad bits and the diagonal bit are zero.
 __global__ __launch_bounds__(256) void k_tri_pack(const uint8_t* __restrict__ Y, int N, int L, int W, unsigned long long* __restrict__ Aout,
                                                   unsigned long long* __restrict__ Ain) {
-  __shared__ uint8_t Bs[TRI_TILE * TRI_BSTRIDE];
+  __shared__ uint8_t Bs[SS_TILE * SS_BSTRIDE];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int bi = blockIdx.x, l = blockIdx.y, s = blockIdx.z;
   const size_t T = (size_t)N * N, sl = (size_t)s * L + l;
   const uint8_t* Ys = Y + sl * T;
-  const int i0 = bi * TRI_TILE;
+  const int i0 = bi * SS_TILE;
   for (int bj = 0; bj < W; ++bj) {
-    const int j0 = bj * TRI_TILE;
+    const int j0 = bj * SS_TILE;
     __syncthreads();   // (the last tile's reads of Bs are done)
-    for (int it = 0; it < TRI_TILE / 4; ++it) {
-      const int c = it * 4 + w, jj = j0 + c, ii = i0 + lane;
-      Bs[c * TRI_BSTRIDE + lane] = (jj < N && ii < N) ? Ys[(size_t)jj * N + ii] : (uint8_t)0;
-    }
+    tile_transposed(Bs, Ys, i0, j0, N);
     __syncthreads();
     const int j = j0 + lane;
     unsigned long long wo = 0ull, wi = 0ull;
-    for (int it = 0; it < TRI_TILE / 4; ++it) {
+    for (int it = 0; it < SS_TILE / 4; ++it) {
       const int r = it * 4 + w, i = i0 + r;
       const bool in = i < N && j < N && i != j;
       const unsigned a = in ? Ys[(size_t)i * N + j] : 0u;
-      const unsigned b = in ? Bs[lane * TRI_BSTRIDE + r] : 0u;
+      const unsigned b = in ? Bs[lane * SS_BSTRIDE + r] : 0u;
       const unsigned long long ba = __ballot(a > 0u), bb = __ballot(b > 0u);
       if (lane == it) { wo = ba; wi = bb; }
     }
-    if (lane < TRI_TILE / 4) {
+    if (lane < SS_TILE / 4) {
       const int i = i0 + lane * 4 + w;
       if (i < N) {
         const size_t o = (sl * N + i) * W + bj;
@@ -280,9 +275,7 @@ __global__ __launch_bounds__(256) void k_tri_exp_finish(const double* __restrict
   __shared__ double tot[TE_NPART];
   const int l = blockIdx.x;
   for (int c = 0; c < TE_NPART; ++c) {
-    double a = 0.0;
-    for (int b = threadIdx.x; b < nb; b += 256) a += part[((size_t)l * nb + b) * TE_NPART + c];
-    const double sum = block_sum_n(a, red);
+    const double sum = partials_col_sum(part + (size_t)l * nb * TE_NPART, nb, TE_NPART, c, red);
     if (threadIdx.x == 0) tot[c] = sum;
   }
   if (threadIdx.x == 0) {
@@ -302,54 +295,36 @@ extern "C" int vmr_sample_triads(vmr_handle h, uint64_t seed, int n_samples, int
                                  int32_t* node_deg) {
   if (!h) return VMR_EINVAL;
   if (!counts) return fail(h, VMR_EINVAL, "vmr_sample_triads: counts is NULL");
-  if (n_samples < 1) return fail(h, VMR_EINVAL, "vmr_sample_triads: n_samples must be positive");
-  if (n_trials < 1) return fail(h, VMR_EINVAL, "vmr_sample_triads: n_trials must be positive");
-  if (!h->have_state) return fail(h, VMR_ESTATE, "vmr_set_state must be called before vmr_sample_triads");
+  int rc;
+  if ((rc = sampled_begin(h, "vmr_sample_triads", n_samples, n_trials))) return rc;
   const Geo& g = h->g;
   if (g.N > 65536) return fail(h, VMR_EINVAL, "vmr_sample_triads: the triangles through a node are 32-bit counts: N <= 65536");
-  HIPCHK(h, hipSetDevice(h->device));
-  { const int rce = ensure_rho_ext(h); if (rce) return rce; }
   const int W = (g.N + 63) / 64;
-  const size_t T = (size_t)g.N * g.N, ties = (size_t)g.L * T;
-  const size_t bits_b = (size_t)g.L * g.N * W * 8, cnt_b = (size_t)g.L * VMR_TRIAD_NSTAT * 8, node_b = (size_t)g.L * g.N * 4;
-  const size_t per = ties + 2 * bits_b + cnt_b + (node_tri ? node_b : 0) + (node_deg ? node_b : 0);   // device bytes per sample of a chunk
-  size_t fr = 0, tot = 0;
-  HIPCHK(h, hipMemGetInfo(&fr, &tot));
-  // half of the free memory at most, 64 MB left alone in any case
-  const size_t budget = fr / 2 > (64u << 20) ? fr / 2 - (64u << 20) : 0;
-  size_t C = std::min<size_t>(std::min<size_t>((size_t)n_samples, NS_CHUNK_MAX), budget / per);
-  if (h->opt.netstats_chunk > 0) C = std::min<size_t>(C, (size_t)h->opt.netstats_chunk);
-  if (C < 1) {
-    char msg[256];
-    snprintf(msg, sizeof msg, "vmr_sample_triads: one sample's temporaries need %.3f GB of device memory, %.3f GB are free", per / 1e9, fr / 1e9);
-    return fail(h, VMR_EINVAL, msg);
-  }
+  const size_t ties = (size_t)g.L * g.N * g.N, bits_b = (size_t)g.L * g.N * W * 8, node_b = (size_t)g.L * g.N * 4;
+  SampledOut out[3] = {{counts, (size_t)g.L * VMR_TRIAD_NSTAT * 8, true, "vmr_sample_triads: the counts"},
+                       {node_tri, node_b, false, "vmr_sample_triads: the node triangles"},
+                       {node_deg, node_b, false, "vmr_sample_triads: the node degrees"}};
+  const size_t per = ties + 2 * bits_b + out[0].bytes + (node_tri ? node_b : 0) + (node_deg ? node_b : 0);   // device bytes per sample of a chunk
+  size_t C;
+  if ((rc = chunk_samples(h, "vmr_sample_triads", (size_t)n_samples, per, 0, &C))) return rc;
   Tmp tm(h);
-  int rc;
   uint8_t* Y = nullptr;
-  unsigned long long *Ao = nullptr, *Ai = nullptr, *cd = nullptr;
-  int32_t *nt = nullptr, *nd = nullptr;
+  unsigned long long *Ao = nullptr, *Ai = nullptr;
   if ((rc = tm.get(&Y, C * ties, "vmr_sample_triads: the samples")) || (rc = tm.get(&Ao, C * bits_b, "vmr_sample_triads: the out-neighbour bits")) ||
-      (rc = tm.get(&Ai, C * bits_b, "vmr_sample_triads: the in-neighbour bits")) || (rc = tm.get(&cd, C * cnt_b, "vmr_sample_triads: the counts")))
+      (rc = tm.get(&Ai, C * bits_b, "vmr_sample_triads: the in-neighbour bits")))
     return rc;
-  if (node_tri && (rc = tm.get(&nt, C * node_b, "vmr_sample_triads: the node triangles"))) return rc;
-  if (node_deg && (rc = tm.get(&nd, C * node_b, "vmr_sample_triads: the node degrees"))) return rc;
   int lG = 0;   // lanes per neighbour: the largest power of two <= min(W, 64)
   while ((2 << lG) <= W && lG < 6) ++lG;
-  const unsigned nstrip = (unsigned)((g.N + TRI_TILE - 1) / TRI_TILE), nquad = (unsigned)((g.N + 3) / 4);
-  for (size_t s0 = 0; s0 < (size_t)n_samples; s0 += C) {
-    const int c = (int)std::min<size_t>(C, (size_t)n_samples - s0);
-    HIPCHK(h, hipMemsetAsync(cd, 0, (size_t)c * cnt_b, h->stream));
-    if ((rc = ns_draw_chunk(h, Y, (unsigned long long)seed + (unsigned long long)s0, c, n_trials))) return rc;   // (mod 2^64)
+  const unsigned nstrip = (unsigned)((g.N + SS_TILE - 1) / SS_TILE), nquad = (unsigned)((g.N + 3) / 4);
+  rc = sampled_chunks(h, tm, (size_t)n_samples, C, seed, n_trials, Y, out, [&](size_t, int c) -> int {
     hipLaunchKernelGGL(k_tri_pack, dim3(nstrip, (unsigned)g.L, (unsigned)c), dim3(256), 0, h->stream, Y, g.N, g.L, W, Ao, Ai);
     HIPCHK(h, hipGetLastError());
-    hipLaunchKernelGGL(k_tri_count, dim3(nquad, (unsigned)g.L, (unsigned)c), dim3(256), 0, h->stream, Ao, Ai, g.N, g.L, W, lG, cd, nt, nd);
+    hipLaunchKernelGGL(k_tri_count, dim3(nquad, (unsigned)g.L, (unsigned)c), dim3(256), 0, h->stream, Ao, Ai, g.N, g.L, W, lG,
+                       out[0].as<unsigned long long>(), out[1].as<int32_t>(), out[2].as<int32_t>());
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(counts + s0 * g.L * VMR_TRIAD_NSTAT, cd, (size_t)c * cnt_b, hipMemcpyDeviceToHost, h->stream));
-    if (node_tri) HIPCHK(h, hipMemcpyAsync(node_tri + s0 * g.L * g.N, nt, (size_t)c * node_b, hipMemcpyDeviceToHost, h->stream));
-    if (node_deg) HIPCHK(h, hipMemcpyAsync(node_deg + s0 * g.L * g.N, nd, (size_t)c * node_b, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-  }
+    return VMR_OK;
+  });
+  if (rc) return rc;
   // every node counted its triangles twice and every triangle has three nodes; every edge of U has two ends
   for (size_t q = 0; q < (size_t)n_samples * g.L; ++q) {
     counts[q * VMR_TRIAD_NSTAT + 3] /= 6;
@@ -361,17 +336,15 @@ extern "C" int vmr_sample_triads(vmr_handle h, uint64_t seed, int n_samples, int
 extern "C" int vmr_expected_triads(vmr_handle h, double* out) {
   if (!h) return VMR_EINVAL;
   if (!out) return fail(h, VMR_EINVAL, "vmr_expected_triads: out is NULL");
-  if (!h->have_state) return fail(h, VMR_ESTATE, "vmr_set_state must be called before vmr_expected_triads");
-  HIPCHK(h, hipSetDevice(h->device));
-  { const int rce = ensure_rho_ext(h); if (rce) return rce; }
+  int rc;
+  if ((rc = expected_begin(h, "vmr_expected_triads"))) return rc;
   const Geo& g = h->g;
   const size_t T = (size_t)g.N * g.N, ties = (size_t)g.L * T;
-  const int nbp = (int)std::max<size_t>(1, std::min<size_t>(1024, (T + 255) / 256));   // k_ns_exp_p's grid, as in vmr_expected_stats
+  const int nbp = exp_p_blocks(T);
   const int nt = (g.N + TE_T - 1) / TE_T;
   if ((size_t)nt * nt > 0x7fffffffu) return fail(h, VMR_EINVAL, "vmr_expected_triads: N is too large");
   const int nb = nt * nt;   // (of N only: the tree is the same on every device)
   Tmp tm(h);
-  int rc;
   double *P = nullptr, *U = nullptr, *wpart = nullptr, *part = nullptr, *od = nullptr;
   if ((rc = tm.get(&P, ties * 8, "vmr_expected_triads: the edge probabilities")) || (rc = tm.get(&U, ties * 8, "vmr_expected_triads: the pair probabilities")) ||
       (rc = tm.get(&wpart, (size_t)g.L * nbp * 32, "vmr_expected_triads: partial sums")) ||

@@ -94,7 +94,7 @@ struct VmrOpts {
   bool gen_no_lds_h;           // VMR_GEN_NO_LDS_H
   int gen_dbg;                 // VMR_GEN_DBG (-DGEN_DEBUG builds)
   int batch_fg;                // VMR_BATCH_FG: clamped to [1, FG_G], 0 when unset
-  int netstats_chunk;          // VMR_NETSTATS_CHUNK: samples per chunk of vmr_sample_stats / vmr_sample_triads at most (tests: several chunks); 0: sized from free memory
+  int netstats_chunk;          // VMR_NETSTATS_CHUNK: samples per chunk at most in chunk_samples (sampled_side.h: every chunked sampled call; tests: several chunks); 0: sized from free memory
   char debug_times[256];       // VMR_DEBUG_TIMES (-DSL_DEBUG builds): "" when unset
 };
 
@@ -499,12 +499,15 @@ int ensure_rho_ext(vmr_ctx* h);
 // C posterior samples of Y queued on the handle's stream: Y[s] (uint8 [L][N][N], natural order) is what vmr_sample(h, seed0 + s,
 // n_trials) writes, s in [0, C); rho is read once.  The caller has run ensure_rho_ext.  netstats.hip
 int ns_draw_chunk(vmr_ctx* h, uint8_t* Y, unsigned long long seed0, int C, int n_trials);
-#define NS_CHUNK_MAX 256   // samples per chunk at most (vmr_sample_stats, vmr_ppc_replicates, vmr_sample_triads)
+#define NS_CHUNK_MAX 256   // samples per chunk at most: chunk_samples (sampled_side.h), the rule of every chunked sampled call
 
 // The edge probabilities queued on the handle's stream: P[l][i][j] = sum_{k>=1} rho_ijk (k ascending), natural order, from rho
 // by tie or by sorted position (k_ns_exp_p).  part: [L][nb][4] doubles, of which column 1 receives the workgroups' sums of
 // sum_k k rho_k; nb workgroups per layer.  The caller has run ensure_rho_ext.  netstats.hip
 int ns_exp_p(vmr_ctx* h, double* P, double* part, int nb);
+// its nb for T = N^2 ties per layer, the one every caller passes: nb decides the summation tree of column 1, and being a function
+// of N only, the tree is the same on every device
+static inline int exp_p_blocks(size_t T) { return (int)std::max<size_t>(1, std::min<size_t>(1024, (T + 255) / 256)); }
 
 #define CK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { g_create_err = std::string(#call) + ": " + hipGetErrorString(e_); (void)hipGetLastError(); return VMR_EHIP; } } while (0)
 

@@ -194,10 +194,13 @@ class CaviEngine:
         return self
 
     # -- helpers
-    def _check(self, rc):
+    def _check(self, rc, einval=None):
+        """einval: the exception a refused argument (VMR_EINVAL) raises in place of ValueError."""
         if rc == 0:
             return
         msg = self.lib.vmr_last_error(self._h).decode()
+        if rc == _lib.VMR_EINVAL and einval is not None:
+            raise einval(msg)
         if rc in (_lib.VMR_EINVAL, _lib.VMR_ENAN):
             raise ValueError(msg)
         raise EngineError(msg)
@@ -446,11 +449,6 @@ class CaviEngine:
         self._check(self.lib.vmr_expected_stats(self._h, out.ctypes.data))
         return {"edges": out[:, 0].copy(), "weight": out[:, 1].copy(), "mutual": out[:, 2].copy(), "edges_var": out[:, 3].copy()}
 
-    def _check_triads(self, rc):
-        if rc == _lib.VMR_EINVAL:
-            raise TriadArgumentError(self.lib.vmr_last_error(self._h).decode())
-        self._check(rc)
-
     def sample_triads(self, seed, n_samples, n_trials=1, nodes=False):
         """Triad statistics of n_samples posterior samples, computed on the device (vmr_sample_triads): sample s is
         `self.sample(seed + s, n_trials)`, A = (Y > 0) with the diagonal cleared, U = A | A.T.  Returns a dict of int64 [S, L]
@@ -462,8 +460,9 @@ class CaviEngine:
         counts = np.zeros((max(S, 0), self.L, _lib.TRIAD_NSTAT), np.uint64)
         ntri = np.zeros((max(S, 0), self.L, self.N), np.int32) if nodes else None
         ndeg = np.zeros((max(S, 0), self.L, self.N), np.int32) if nodes else None
-        self._check_triads(self.lib.vmr_sample_triads(self._h, int(seed) & (2 ** 64 - 1), S, int(n_trials), counts.ctypes.data,
-                                                      ntri.ctypes.data if nodes else None, ndeg.ctypes.data if nodes else None))
+        self._check(self.lib.vmr_sample_triads(self._h, int(seed) & (2 ** 64 - 1), S, int(n_trials), counts.ctypes.data,
+                                               ntri.ctypes.data if nodes else None, ndeg.ctypes.data if nodes else None),
+                    TriadArgumentError)
         c = counts.astype(np.int64)
         out = {k: np.ascontiguousarray(c[..., q]) for q, k in enumerate(_lib.TRIAD_NAMES)}
         if nodes:
@@ -475,7 +474,7 @@ class CaviEngine:
         float64 [L] arrays under the same names.  Expectations of counts: a ratio of two of them is not the expectation of the
         ratio."""
         out = np.zeros((self.L, _lib.TRIAD_NSTAT), np.float64)
-        self._check_triads(self.lib.vmr_expected_triads(self._h, out.ctypes.data))
+        self._check(self.lib.vmr_expected_triads(self._h, out.ctypes.data), TriadArgumentError)
         return {k: out[:, q].copy() for q, k in enumerate(_lib.TRIAD_NAMES)}
 
     def _mixing_args(self, groups, C):
@@ -487,11 +486,6 @@ class CaviEngine:
             raise ValueError(f"groups must be {self.N} integer codes (-1: the node is left out), got {g.dtype} {g.shape}")
         g = np.ascontiguousarray(np.clip(g.astype(np.int64), -2, 2 ** 31 - 1), dtype=np.int32)   # (out of range stays out of range)
         return g, int(g.max(initial=-1)) + 1 if C is None else int(C)
-
-    def _check_mixing(self, rc):
-        if rc == _lib.VMR_EINVAL:
-            raise MixingArgumentError(self.lib.vmr_last_error(self._h).decode())
-        self._check(rc)
 
     def sample_mixing(self, seed, n_samples, groups=None, C=None, n_trials=1, skip_diagonal=True, overlap=True):
         """Mixing by node attribute and overlap between layers of n_samples posterior samples, computed on the device
@@ -508,9 +502,9 @@ class CaviEngine:
         mix = np.zeros(shape, np.uint64) if grp else None
         mut = np.zeros(shape, np.uint64) if grp else None
         ov = np.zeros((max(S, 0), self.L, self.L), np.uint64) if overlap else None
-        self._check_mixing(self.lib.vmr_sample_mixing(self._h, int(seed) & (2 ** 64 - 1), S, int(n_trials), g.ctypes.data if grp else None, C,
-                                                      int(bool(skip_diagonal)), mix.ctypes.data if grp else None,
-                                                      mut.ctypes.data if grp else None, ov.ctypes.data if overlap else None))
+        self._check(self.lib.vmr_sample_mixing(self._h, int(seed) & (2 ** 64 - 1), S, int(n_trials), g.ctypes.data if grp else None, C,
+                                               int(bool(skip_diagonal)), mix.ctypes.data if grp else None,
+                                               mut.ctypes.data if grp else None, ov.ctypes.data if overlap else None), MixingArgumentError)
         out = {}
         if grp:
             out["mix"], out["mutual"] = mix.astype(np.int64), mut.astype(np.int64)
@@ -528,9 +522,9 @@ class CaviEngine:
         mix = np.zeros((self.L, max(C, 0), max(C, 0)), np.float64) if grp else None
         mut = np.zeros((self.L, max(C, 0), max(C, 0)), np.float64) if grp else None
         ov = np.zeros((self.L, self.L), np.float64) if overlap else None
-        self._check_mixing(self.lib.vmr_expected_mixing(self._h, g.ctypes.data if grp else None, C, int(bool(skip_diagonal)),
-                                                        mix.ctypes.data if grp else None, mut.ctypes.data if grp else None,
-                                                        ov.ctypes.data if overlap else None))
+        self._check(self.lib.vmr_expected_mixing(self._h, g.ctypes.data if grp else None, C, int(bool(skip_diagonal)),
+                                                 mix.ctypes.data if grp else None, mut.ctypes.data if grp else None,
+                                                 ov.ctypes.data if overlap else None), MixingArgumentError)
         out = {}
         if grp:
             out["mix"], out["mutual"] = mix, mut
@@ -640,17 +634,11 @@ class CaviEngine:
                 sel |= bits[s]
         return codes[method], float(threshold), sel, self._layer_arg(layer)
 
-    def _check_edge(self, rc):
-        """A refused argument of the edge table is an EngineError AND a ValueError (EdgeTableArgumentError)."""
-        if rc == _lib.VMR_EINVAL:
-            raise EdgeTableArgumentError(self.lib.vmr_last_error(self._h).decode())
-        self._check(rc)
-
     def edge_table_size(self, method="rho_max", threshold=0.0, select=("reported", "inferred"), layer=None):
         """Rows of `edge_table` for the same arguments (vmr_edge_table_size)."""
         code, thr, sel, la = self._edge_args(method, threshold, select, layer)
         n = C.c_uint64()
-        self._check_edge(self.lib.vmr_edge_table_size(self._h, code, thr, sel, la, C.byref(n)))
+        self._check(self.lib.vmr_edge_table_size(self._h, code, thr, sel, la, C.byref(n)), EdgeTableArgumentError)
         return int(n.value)
 
     def edge_table(self, method="rho_max", threshold=0.0, select=("reported", "inferred"), layer=None, device=False, out=None):
@@ -694,7 +682,7 @@ class CaviEngine:
             import torch
             torch.cuda.synchronize(torch.device("cuda", self.device))
         if n or out is not None:
-            self._check_edge(self.lib.vmr_edge_table(self._h, code, thr, sel, la, n, *ptrs, int(on_dev)))
+            self._check(self.lib.vmr_edge_table(self._h, code, thr, sel, la, n, *ptrs, int(on_dev)), EdgeTableArgumentError)
         return cols
 
     def score_truth(self, Y_true, thresholds=None, score="rho1", skip_diagonal=False, auc=True, outputs=None):
@@ -745,9 +733,7 @@ class CaviEngine:
         rc = self.lib.vmr_score_truth(self._h, yp, ydev, SCORES.index(score), int(bool(skip_diagonal)), n_thr,
                                       thr.ctypes.data if n_thr else None, *ptrs)
         del keep
-        if rc == _lib.VMR_EINVAL:
-            raise ScoreArgumentError(self.lib.vmr_last_error(self._h).decode())
-        self._check(rc)
+        self._check(rc, ScoreArgumentError)
         out = {o: (bufs[o].astype(np.int64) if bufs[o].dtype == np.uint64 else bufs[o]) if o in outputs else None for o in SCORE_OUTPUTS}
         out["n_ties"] = np.full(self.L, self.N * self.N - (self.N if skip_diagonal else 0), np.int64)
         out["thresholds"] = thr
@@ -773,9 +759,7 @@ class CaviEngine:
         sums = np.zeros((Lq, self.M, _lib.RT_NSUM), np.float64) if "sums" in outputs else None
         rc = self.lib.vmr_reporter_table(self._h, codes[method], float(threshold), self._layer_arg(layer),
                                          None if counts is None else counts.ctypes.data, None if sums is None else sums.ctypes.data)
-        if rc == _lib.VMR_EINVAL:
-            raise ReporterTableArgumentError(self.lib.vmr_last_error(self._h).decode())
-        self._check(rc)
+        self._check(rc, ReporterTableArgumentError)
         return {"counts": None if counts is None else counts.astype(np.int64), "sums": sums}
 
     def heldout_loglik(self, subs, x, xt=None, theta=None, lam=None, eta=0.0, per_entry=True, device=False):
@@ -833,9 +817,7 @@ class CaviEngine:
         rc = self.lib.vmr_heldout_loglik(self._h, n, *ptrs, int(on_dev), theta.ctypes.data, lam.ctypes.data, float(eta), lp_ptr, mn_ptr,
                                          int(bool(device and per_entry)), sums.ctypes.data, counts.ctypes.data)
         del cols
-        if rc == _lib.VMR_EINVAL:
-            raise HeldoutArgumentError(self.lib.vmr_last_error(self._h).decode())
-        self._check(rc)
+        self._check(rc, HeldoutArgumentError)
         return {"logp": logp, "mean": mean, "sums": sums, "counts": counts.astype(np.int64)}
 
     def _rs_args(self, theta, lam, eta, threshold, select, layer):
@@ -852,16 +834,12 @@ class CaviEngine:
             raise ReportScoresArgumentError(f"layer {layer} out of range [0, {self.L})")
         return theta, lam, float(eta), float(threshold), int(select), self._layer_arg(layer)
 
-    def _check_rs(self, rc):
-        if rc == _lib.VMR_EINVAL:
-            raise ReportScoresArgumentError(self.lib.vmr_last_error(self._h).decode())
-        self._check(rc)
-
     def report_scores_size(self, theta, lam, eta, threshold, select="both", layer=None):
         """Rows of `report_scores` for the same arguments (vmr_report_scores_size): the flagged elements."""
         theta, lam, eta, thr, sel, la = self._rs_args(theta, lam, eta, threshold, select, layer)
         n = C.c_uint64()
-        self._check_rs(self.lib.vmr_report_scores_size(self._h, la, theta.ctypes.data, lam.ctypes.data, eta, sel, thr, C.byref(n)))
+        self._check(self.lib.vmr_report_scores_size(self._h, la, theta.ctypes.data, lam.ctypes.data, eta, sel, thr, C.byref(n)),
+                    ReportScoresArgumentError)
         return int(n.value)
 
     def report_scores(self, theta, lam, eta, threshold, select="both", layer=None, edges=None, rows=True, by_reporter=True, device=False,
@@ -927,7 +905,7 @@ class CaviEngine:
                                         ed.ctypes.data if n_edges else None, None if hist is None else hist.ctypes.data,
                                         sums.ctypes.data, counts.ctypes.data, None if rep is None else rep.ctypes.data,
                                         n if (rows or out is not None) else 0, *ptrs, int(on_dev))
-        self._check_rs(rc)
+        self._check(rc, ReportScoresArgumentError)
         res = {"counts": counts.astype(np.int64), "sums": sums, "hist": None if hist is None else hist.astype(np.int64), "edges": ed,
                "by_reporter": None if rep is None else rep.astype(np.int64),
                "layers": np.arange(self.L) if layer is None else np.array([int(layer)]), "threshold": thr, "select": sel}
@@ -957,19 +935,14 @@ class CaviEngine:
             raise ReporterInfluenceArgumentError(f"layer {layer} out of range [0, {self.L})")
         return tabs, float(g_nu), int(method), float(threshold), int(select), float(min_tv), self._layer_arg(layer)
 
-    def _check_inf(self, rc):
-        if rc == _lib.VMR_EINVAL:
-            raise ReporterInfluenceArgumentError(self.lib.vmr_last_error(self._h).decode())
-        self._check(rc)
-
     def reporter_influence_size(self, e_theta, elog_theta, e_lambda, elog_lambda, g_nu, method="rho_max", threshold=0.0, select="both",
                                 min_tv=np.inf, layer=None):
         """Rows of `reporter_influence` for the same arguments (vmr_reporter_influence_size): the flagged elements."""
         tabs, g_nu, code, thr, sel, mtv, la = self._inf_args(e_theta, elog_theta, e_lambda, elog_lambda, g_nu, method, threshold, select,
                                                             min_tv, layer)
         n = C.c_uint64()
-        self._check_inf(self.lib.vmr_reporter_influence_size(self._h, la, *[a.ctypes.data for a in tabs], g_nu, code, thr, sel, mtv,
-                                                             C.byref(n)))
+        self._check(self.lib.vmr_reporter_influence_size(self._h, la, *[a.ctypes.data for a in tabs], g_nu, code, thr, sel, mtv,
+                                                         C.byref(n)), ReporterInfluenceArgumentError)
         return int(n.value)
 
     def reporter_influence(self, e_theta, elog_theta, e_lambda, elog_lambda, g_nu, method="rho_max", threshold=0.0, select="both",
@@ -1038,7 +1011,7 @@ class CaviEngine:
         rc = self.lib.vmr_reporter_influence(self._h, la, *tp, g_nu, code, thr, sel, mtv, n_edges, ed.ctypes.data if n_edges else None,
                                              None if hist is None else hist.ctypes.data, counts.ctypes.data, sums.ctypes.data,
                                              n if (rows or out is not None) else 0, *ptrs, int(on_dev))
-        self._check_inf(rc)
+        self._check(rc, ReporterInfluenceArgumentError)
         res = {"counts": counts.astype(np.int64), "sums": sums, "hist": None if hist is None else hist.astype(np.int64), "edges": ed,
                "layers": np.arange(self.L) if layer is None else np.array([int(layer)]), "method": code, "threshold": thr,
                "select": sel, "min_tv": mtv}
@@ -1056,8 +1029,8 @@ class CaviEngine:
                 if nf and n_rows:
                     sub = {c: np.empty(nf, np.int32) for c in "lijm"}
                     p4 = [sub[c].ctypes.data for c in "lijm"] + [None] * 5
-                    self._check_inf(self.lib.vmr_reporter_influence(self._h, la, *tp, g_nu, code, thr, bit, np.inf, 0, None, None, None,
-                                                                    None, nf, *p4, 0))
+                    self._check(self.lib.vmr_reporter_influence(self._h, la, *tp, g_nu, code, thr, bit, np.inf, 0, None, None, None,
+                                                                None, nf, *p4, 0), ReporterInfluenceArgumentError)
                     mark = np.isin(key, np.ravel_multi_index(tuple(sub[c].astype(np.int64) for c in "lijm"), shape))
                 res[name] = mark
         return res
