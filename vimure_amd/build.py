@@ -17,7 +17,7 @@ HOST_SRC = os.path.join(CSRC, "host_init.c")
 HOST_LIB = os.path.join(HERE, "libvimure_host.so")
 HEADERS = [os.path.join(CSRC, "vmr_internal.h"), os.path.join(CSRC, "sweep_sl.h"), os.path.join(CSRC, "sweep_gen.h"),
            os.path.join(CSRC, "sample_draw.h"), os.path.join(CSRC, "report_draw.h"), os.path.join(CSRC, "ppc_layer.h"), os.path.join(CSRC, "rho_row.h"),
-           os.path.join(CSRC, "report_lik.h"), os.path.join(CSRC, "read_side.h"), os.path.join(CSRC, "sampled_side.h"),
+           os.path.join(CSRC, "report_lik.h"), os.path.join(CSRC, "read_side.h"), os.path.join(CSRC, "sampled_side.h"), os.path.join(CSRC, "sl_balance.h"),
            os.path.join(ROOT, "include", "vimure_hip.h")]
 KS = (2, 3, 4, 5, 6, 7, 8)
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]

@@ -2,6 +2,7 @@
 // the permutation kernels of the boundary functions.  Replaces the data set-up of `__check_fit_params` (model.py:136-171)
 // together with vmr_create / vmr_create_coo in vimure_hip.hip.
 #include "sweep_sl.h"
+#include "sl_balance.h"
 
 // keys = per-tie report counts, values = tie index (one layer)
 __global__ __launch_bounds__(256) void k_sl_keys(const unsigned* __restrict__ cnt, unsigned* __restrict__ keys, unsigned* __restrict__ vals, size_t T) {
@@ -46,7 +47,8 @@ __global__ __launch_bounds__(256) void k_sl_place(const unsigned* __restrict__ p
     // A tie's reports arrive in reporter order.  Left like that, round r would hold the r-th smallest reporter of all 64
     // ties -- a narrow band of table rows, several lanes on the SAME row: the LDS float atomics of walk 2 then serialise
     // (config-5 layer: 77 cycles per wave-instruction against ~25).  Every tie's list is therefore rotated by a per-tie
-    // pseudo-random offset, which spreads a round over the whole reporter range.
+    // pseudo-random offset, which spreads a round over the whole reporter range.  (The starting point only: k_sl_balance then
+    // permutes every column so that a round's rows also spread over the LDS bank slots.)
     unsigned rot = 0;
     if (n > 1) { unsigned hsh = t * 0x9E3779B1u; hsh ^= hsh >> 15; hsh *= 0x85EBCA77u; hsh ^= hsh >> 13; rot = hsh % n; }
     unsigned ymx = 0;
@@ -61,6 +63,75 @@ __global__ __launch_bounds__(256) void k_sl_place(const unsigned* __restrict__ p
 #pragma unroll
     for (int o2 = 32; o2 > 0; o2 >>= 1) ymx = max(ymx, (unsigned)__shfl_xor((int)ymx, o2, 64));
     if (lane == 0) syl[s] = ymx;
+  }
+}
+// One wave (= one workgroup) per step: the placement of sl_balance.h on the step's columns, in place, windows of SLB_WIN rounds
+// staged in LDS.  Loads, stores and the model's cycle counts are the wave's, one thread per lane; the placement itself takes the
+// lanes in a fixed order (so that it is a pure function of the lists) on SLB_CHAINS threads, one per chain -- once per dataset.
+// The only atomics are integer counts, which no order of arrival changes.  rows_near: entries of rows from there on are the ones
+// k_far_first moved to the front of their columns and stay there (0xffffffff: none).
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(7))) void k_sl_balance(unsigned* __restrict__ E, const unsigned* __restrict__ rsl, size_t NS, unsigned rows_near) {
+  __shared__ unsigned win[SLB_WIN * 64];
+  __shared__ unsigned lead[64], cnt[64];
+  __shared__ SlbScratch sc;
+  __shared__ unsigned tot[16];
+  // [as it came | placed][the read's groups, the contiguous groups][slot]: rows / lanes of one round -- in the memory of the placement's
+  // counts, which are done with by then (LDS bounds how many steps a CU has in flight, and the placement is all latency)
+  static_assert(sizeof sc.cr + sizeof sc.ca == 2 * 8 * 16 * sizeof(unsigned) && offsetof(SlbScratch, ca) == sizeof sc.cr, "hist aliases cr | ca");
+  unsigned (*hist)[8][16] = reinterpret_cast<unsigned (*)[8][16]>(&sc.cr[0][0][0]);
+  const int lane = threadIdx.x;
+  for (size_t s = blockIdx.x; s < NS; s += gridDim.x) {
+    const unsigned ea = rsl[s], R = (rsl[s + 1] - ea) >> 6;
+    if (R < 2) break;   // (R does not increase with s)
+    unsigned* col = E + (size_t)ea + lane;
+    unsigned n = 0, ld = 0;
+    for (unsigned r = 0; r < R; ++r) {
+      const unsigned e = col[(size_t)r * 64];
+      if (e != 0u) n = r + 1;
+      if (r == ld && e != 0u && SL_YM(e) >= rows_near) ++ld;
+    }
+    for (unsigned r0 = 0; r0 < R; r0 += SLB_WIN) {
+      const unsigned nr = min((unsigned)SLB_WIN, R - r0);
+      if (nr < 2) break;
+      for (unsigned r = 0; r < nr; ++r) { const unsigned e = col[(size_t)(r0 + r) * 64]; win[r * 64 + lane] = e; sc.in[r * 64 + lane] = e; }
+      lead[lane] = slb_clip(min(ld, n), r0);
+      cnt[lane] = slb_clip(n, r0);
+      for (int i = lane; i < SLB_WIN * 4 * 16; i += 64) { (&sc.cr[0][0][0])[i] = 0; (&sc.ca[0][0][0])[i] = 0; }
+      __syncthreads();
+      for (int pass = 0; pass < 2; ++pass)
+        for (int p = 0; p < 2; ++p) {
+          if (lane < SLB_CHAINS) slb_chain_phase(win, (int)nr, lead, cnt, &sc, lane, p, pass == 1);
+          __syncthreads();
+        }
+      // the model's cycles before and after (slb_round_cost, one thread per lane): threads 0..15 sum the fullest slots of their group
+      unsigned acc = 0;
+      for (unsigned r = 0; r < nr; ++r) {
+        for (int i = lane; i < 2 * 8 * 16; i += 64) (&hist[0][0][0])[i] = 0u;   // (after the barrier that ends the placement)
+        __syncthreads();
+        for (int a = 0; a < 2; ++a) {
+          const unsigned* w = (a ? win : sc.in) + r * 64;
+          const unsigned e = w[lane];
+          if (e != 0u) {
+            atomicAdd(&hist[a][4 + (lane >> 4)][SLB_ROW(e) & 15u], 1u);
+            if (slb_opens_row(w, lane)) atomicAdd(&hist[a][slb_read_group(lane)][SLB_ROW(e) & 15u], 1u);
+          }
+        }
+        __syncthreads();
+        if (lane < 16) {
+          unsigned m = 0;
+          for (int s = 0; s < 16; ++s) m = max(m, hist[lane >> 3][lane & 7][s]);
+          acc += m;
+        }
+        __syncthreads();
+      }
+      if (lane < 16) tot[lane] = acc;
+      __syncthreads();
+      const unsigned rd0 = tot[0] + tot[1] + tot[2] + tot[3], ad0 = tot[4] + tot[5] + tot[6] + tot[7];
+      const unsigned rd1 = tot[8] + tot[9] + tot[10] + tot[11], ad1 = tot[12] + tot[13] + tot[14] + tot[15];
+      if (rd1 <= rd0 && ad1 <= ad0)   // (never worse than it came, for the read and for the add: else the window stays)
+        for (unsigned r = 0; r < nr; ++r) col[(size_t)(r0 + r) * 64] = win[r * 64 + lane];
+      __syncthreads();
+    }
   }
 }
 
@@ -102,6 +173,15 @@ int sl_permute_rows(vmr_ctx* h, const double* in, double* out, bool to_pos) {
   const size_t T = (size_t)g.N * g.N, NS = (T + 63) / 64, n = (size_t)g.L * T * g.K;
   hipLaunchKernelGGL(k_sl_rows, dim3((unsigned)std::min<size_t>(16384, (n + 255) / 256)), dim3(256), 0, h->stream, h->perm, in, out, T, NS, g.L, g.K, to_pos ? 1 : 0);
   HIPCHK(h, hipGetLastError());
+  return VMR_OK;
+}
+
+int sl_balance_layer(vmr_ctx* h, int l, unsigned long long eb, unsigned rows_near) {
+  const Geo& g = h->g;
+  if (g.wide || h->opt.no_balance) return VMR_OK;
+  const size_t T = (size_t)g.N * g.N, NS = (T + 63) / 64;
+  hipLaunchKernelGGL(k_sl_balance, dim3((unsigned)std::min<size_t>(1u << 20, NS)), dim3(64), 0, h->stream, h->E + eb, h->rs + (size_t)l * (NS + 1), NS, rows_near);
+  CK(hipGetLastError());
   return VMR_OK;
 }
 
@@ -181,6 +261,7 @@ int sl_place_entries(vmr_ctx* h, unsigned* rp, const std::vector<unsigned long l
     off += nl[l];
   }
   CKS(hipGetLastError());
+  for (int l = 0; l < L; ++l) { const int rc = sl_balance_layer(h, l, eb[l], 0xffffffffu); if (rc) { cleanup(); return rc; } }
   CKS(hipStreamSynchronize(h->stream));
 #undef CKS
   cleanup();

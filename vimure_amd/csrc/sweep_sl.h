@@ -154,6 +154,10 @@ sl_launch_batch_fn vmr_sl_batch_launcher(int K);
 // Wide entries (Geo::wide): every entry is two words -- etmp2 / etmp2_all hold the second ones -- and h->EX receives them.
 typedef std::function<void(int l, const unsigned* rpl, unsigned* etmp, unsigned* etmp2)> SlFill;
 int sl_place_entries(vmr_ctx* h, unsigned* rp, const std::vector<unsigned long long>& nl, unsigned* etmp_all, unsigned* etmp2_all, const SlFill* fill);
+// Permutes the columns of layer l's steps in place so that a round's table rows spread over the LDS bank slots (k_sl_balance,
+// sl_balance.h); eb: the layer's first slot.  Entries of rows >= rows_near stay in front of their columns (after k_far_first;
+// 0xffffffff: none).  Nothing for wide entries and under VMR_NO_BALANCE.
+int sl_balance_layer(vmr_ctx* h, int l, unsigned long long eb, unsigned rows_near);
 // out[l][pos] = in[l][perm[l][pos]] for the per-tie arrays the sweeps read by position
 int sl_permute_u8(vmr_ctx* h, const uint8_t* in, uint8_t* out);
 int sl_permute_u32(vmr_ctx* h, const unsigned* in, unsigned* out);

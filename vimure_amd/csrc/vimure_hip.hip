@@ -2420,6 +2420,7 @@ static void read_opts(VmrOpts& o) {
   o.no_rm2 = set("VMR_NO_RM2");
   o.no_lp0 = set("VMR_NO_LP0");
   o.no_lpd = set("VMR_NO_LPD");
+  o.no_balance = set("VMR_NO_BALANCE");
   o.always_store_rho = set("VMR_ALWAYS_STORE_RHO");
   o.debug_lazy_rho = set("VMR_DEBUG_LAZY_RHO");
   o.gen_hsum = num("VMR_GEN_HSUM", 0);
@@ -2606,6 +2607,7 @@ static int build_far_lists(vmr_ctx* h) {
     hipLaunchKernelGGL(k_far_first, dim3((unsigned)std::min<size_t>(8192, (NS + 3) / 4)), dim3(256), 0, h->stream, h->E + eb[l], h->rs + (size_t)l * (NS + 1),
                        h->sy + (size_t)l * NS, NS, (unsigned)g.hc * (unsigned)g.Mp, (unsigned*)nullptr);
     CK(hipGetLastError());
+    { const int rcb = sl_balance_layer(h, l, eb[l], (unsigned)g.hc * (unsigned)g.Mp); if (rcb) return rcb; }   // (before the positions are recorded)
     CK(hipMemsetAsync(cnt, 0, 8, h->stream));
     hipLaunchKernelGGL(k_far_collect, dim3((unsigned)std::min<size_t>(8192, (NS + 3) / 4)), dim3(256), 0, h->stream, h->E + eb[l], h->rs + (size_t)l * (NS + 1), NS,
                        (unsigned)g.hc * (unsigned)g.Mp, h->far_pos + h->far_off[l], h->far_ent + h->far_off[l], cnt);
@@ -2823,6 +2825,7 @@ static int create_tail(vmr_ctx* h, const hipDeviceProp_t& prop) {
         hipLaunchKernelGGL(k_far_first, dim3((unsigned)std::min<size_t>(8192, (NS_ + 3) / 4)), dim3(256), 0, h->stream, h->E + eb[l], h->rs + (size_t)l * (NS_ + 1),
                            h->sy + (size_t)l * NS_, NS_, (unsigned)g.Mp, h->x0p ? h->x0p + (size_t)l * NS_ * 64 : nullptr);
       CK(hipGetLastError());
+      for (int l = 0; l < L; ++l) { const int rcb = sl_balance_layer(h, l, eb[l], (unsigned)g.Mp); if (rcb) return rcb; }
       if (h->x0p) {
         unsigned long long* ss = nullptr;
         CK(hipMalloc(&ss, 8));

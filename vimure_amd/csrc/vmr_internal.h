@@ -88,7 +88,7 @@ struct VmrOpts {
   int two_pass, farl;          // VMR_TWO_PASS, VMR_FARL
   int yt, hc;                  // VMR_YT, VMR_HC: max(0, atoi), -1 when unset
   int tpb, st_tpb;             // VMR_TPB, VMR_ST_TPB: taken when a multiple of 64 in [64, 1024]
-  bool no_level0, no_x0, no_lv0r, no_level_sort, no_rlists, no_rm2, no_lp0, no_lpd;   // VMR_NO_*
+  bool no_level0, no_x0, no_lv0r, no_level_sort, no_rlists, no_rm2, no_lp0, no_lpd, no_balance;   // VMR_NO_*
   bool always_store_rho, debug_lazy_rho;   // VMR_ALWAYS_STORE_RHO, VMR_DEBUG_LAZY_RHO
   int gen_hsum;                // VMR_GEN_HSUM: taken when > 0
   bool gen_no_lds_h;           // VMR_GEN_NO_LDS_H
