@@ -346,6 +346,48 @@ int vmr_sample_mixing(vmr_handle h, uint64_t seed, int n_samples, int n_trials, 
  * 8 L N^2 bytes, and the rows' sums, 16 L N C + 8 N L^2 bytes; one that does not fit is refused with VMR_EINVAL.  Synchronises. */
 int vmr_expected_mixing(vmr_handle h, const int32_t* group, int C, int skip_diagonal, double* mix, double* mutual, double* overlap);
 
+/* Connectivity of n_samples posterior samples of Y, computed where rho lives -- what a user otherwise gets from
+ * `scipy.sparse.csgraph` (connected_components, shortest_path) on every `sample_inferred_model` draw.  Sample s is exactly what
+ * vmr_sample(h, seed + s, n_trials, ..) writes (seed + s mod 2^64).  Per sample and layer: A_ij = (Y_ij > 0) with the DIAGONAL
+ * CLEARED, U = A | A^T; d(i,j) is the length of a shortest directed path in A, infinite if there is none, d(i,i) = 0.  Weak
+ * components are the components of U, strong components the classes of mutual reachability in A.
+ * counts: host uint64 [n_samples][L][VMR_CONN_NSTAT]:
+ *   0 components_w  weak components, isolated nodes included
+ *   1 giant_w       size of the largest weak component
+ *   2 pairs_w       #{(i,j), i != j, same weak component} = sum_c n_c (n_c - 1)
+ *   3 isolates      nodes of degree 0 in U (a self-loop does not count)
+ *   4 components_s  strong components
+ *   5 giant_s       size of the largest strong component
+ *   6 pairs_s       #{(i,j), i != j, d(i,j) < inf and d(j,i) < inf}
+ *   7 reach_pairs   #{(i,j), i != j, d(i,j) < inf}
+ *   8 dist_sum      sum of d(i,j) over those pairs
+ *   9 diameter      the largest finite d(i,j); 0 when A is empty
+ * dist_hist: host uint64 [n_samples][L][VMR_CONN_NDIST]: bin b = d - 1 counts the ordered pairs at distance d, 1 <= d <
+ * VMR_CONN_NDIST; the last bin collects every pair at distance >= VMR_CONN_NDIST.  dist_sum and diameter are exact whatever the
+ * bins hold.  Node arrays, host int32 [n_samples][L][N]:
+ *   node_comp_w, node_comp_s      the smallest node index in the node's weak / strong component
+ *   node_reach_out[i] = #{j != i : d(i,j) < inf}      node_reach_in[j] = #{i != j : d(i,j) < inf}
+ *   node_dist_out[i] = sum_j d(i,j)                    node_dist_in[j] = sum_i d(i,j), over the reachable pairs only
+ *                                                      (at most N (N - 1) / 2 each)
+ * dist_hist and every node array may be NULL; counts may not.
+ * The samples are packed into the bit rows of vmr_sample_triads; one workgroup per (block of 64 sources, layer, sample) runs a
+ * breadth-first search from its 64 sources at once over 64-bit words in LDS (seen, frontier, next frontier: 24 N bytes), three
+ * times: over U, A and A^T.  That working set bounds N: N <= VMR_CONN_NMAX = 2048 (48 KiB of LDS per workgroup, three workgroups
+ * to a compute unit); a larger N is refused with VMR_EINVAL and a message that names the bound, whatever the state of the
+ * handle.  All sums are integer sums, the diameter an integer maximum, the labels integer minima: bit-identical from run to run
+ * and for any chunking.  Reads the CURRENT rho (after vmr_restore: the snapshot's) once per chunk of samples; any K, any
+ * n_trials >= 1, both data formats.  A chunk (L N^2 + 16 L N ceil(N/64) + 24 L N bytes per sample -- the six node arrays stay on
+ * the device whether or not they are asked for -- plus the counts and the histogram when it is asked for; half of the free
+ * device memory at most, 256 samples at most, VMR_NETSTATS_CHUNK at most) is freed before return; a single
+ * sample that does not fit is refused with VMR_EINVAL.  n_samples < 1, n_trials < 1 or counts NULL: VMR_EINVAL, with a message
+ * that names the argument; before vmr_set_state: VMR_ESTATE.  Synchronises. */
+#define VMR_CONN_NSTAT 10
+#define VMR_CONN_NDIST 64
+#define VMR_CONN_NMAX 2048   /* nodes at most */
+int vmr_sample_connectivity(vmr_handle h, uint64_t seed, int n_samples, int n_trials, uint64_t* counts, uint64_t* dist_hist,
+                            int32_t* node_comp_w, int32_t* node_comp_s, int32_t* node_reach_out, int32_t* node_reach_in,
+                            int32_t* node_dist_out, int32_t* node_dist_in);
+
 /* Posterior predictive checks: n_rep replicated datasets drawn from the fitted model over the support of the handle's own R and
  * reduced where they are drawn -- no replicate is ever written -- and the same reduction of the observed data.
  * Replicate r: Y_r is exactly what vmr_sample(h, seed_y + r, n_trials, ..) writes (mod 2^64; the CURRENT rho, after vmr_restore

@@ -16,6 +16,10 @@ PPC_NSTAT = 6
 TRIAD_NSTAT = 6
 TRIAD_NAMES = ["transitive", "cyclic", "two_paths", "triangles_u", "wedges_u", "edges_u"]
 MIX_CMAX, MIX_LMAX = 64, 32
+CONN_NSTAT, CONN_NDIST, CONN_NMAX = 10, 64, 2048
+CONN_NAMES = ["components_w", "giant_w", "pairs_w", "isolates", "components_s", "giant_s", "pairs_s", "reach_pairs", "dist_sum",
+              "diameter"]
+CONN_NODE_NAMES = ["node_comp_w", "node_comp_s", "node_reach_out", "node_reach_in", "node_dist_out", "node_dist_in"]
 EDGE_REPORTED, EDGE_INFERRED = 1, 2
 SCORE_RHO1, SCORE_PROB = 0, 1
 SCORE_NCONF, SCORE_NSUM, SCORE_MAX_THR = 5, 4, 4096
@@ -72,6 +76,7 @@ SIGNATURES = {
     "vmr_expected_triads": (C.c_int, [C.c_void_p, C.c_void_p]),
     "vmr_sample_mixing": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vmr_expected_mixing": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vmr_sample_connectivity": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int] + [C.c_void_p] * 8),
     "vmr_ppc_replicates": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
     "vmr_ppc_observed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

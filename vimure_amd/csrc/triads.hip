@@ -291,6 +291,14 @@ __global__ __launch_bounds__(256) void k_tri_exp_finish(const double* __restrict
 
 }  // namespace
 
+int tri_pack_chunk(vmr_ctx* h, const uint8_t* Y, int c, unsigned long long* Aout, unsigned long long* Ain) {
+  const Geo& g = h->g;
+  const unsigned nstrip = (unsigned)((g.N + SS_TILE - 1) / SS_TILE);
+  hipLaunchKernelGGL(k_tri_pack, dim3(nstrip, (unsigned)g.L, (unsigned)c), dim3(256), 0, h->stream, Y, g.N, g.L, (g.N + 63) / 64, Aout, Ain);
+  HIPCHK(h, hipGetLastError());
+  return VMR_OK;
+}
+
 extern "C" int vmr_sample_triads(vmr_handle h, uint64_t seed, int n_samples, int n_trials, uint64_t* counts, int32_t* node_tri,
                                  int32_t* node_deg) {
   if (!h) return VMR_EINVAL;
@@ -315,10 +323,10 @@ extern "C" int vmr_sample_triads(vmr_handle h, uint64_t seed, int n_samples, int
     return rc;
   int lG = 0;   // lanes per neighbour: the largest power of two <= min(W, 64)
   while ((2 << lG) <= W && lG < 6) ++lG;
-  const unsigned nstrip = (unsigned)((g.N + SS_TILE - 1) / SS_TILE), nquad = (unsigned)((g.N + 3) / 4);
+  const unsigned nquad = (unsigned)((g.N + 3) / 4);
   rc = sampled_chunks(h, tm, (size_t)n_samples, C, seed, n_trials, Y, out, [&](size_t, int c) -> int {
-    hipLaunchKernelGGL(k_tri_pack, dim3(nstrip, (unsigned)g.L, (unsigned)c), dim3(256), 0, h->stream, Y, g.N, g.L, W, Ao, Ai);
-    HIPCHK(h, hipGetLastError());
+    int rc2;
+    if ((rc2 = tri_pack_chunk(h, Y, c, Ao, Ai))) return rc2;
     hipLaunchKernelGGL(k_tri_count, dim3(nquad, (unsigned)g.L, (unsigned)c), dim3(256), 0, h->stream, Ao, Ai, g.N, g.L, W, lG,
                        out[0].as<unsigned long long>(), out[1].as<int32_t>(), out[2].as<int32_t>());
     HIPCHK(h, hipGetLastError());

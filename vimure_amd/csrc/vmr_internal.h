@@ -501,6 +501,11 @@ int ensure_rho_ext(vmr_ctx* h);
 int ns_draw_chunk(vmr_ctx* h, uint8_t* Y, unsigned long long seed0, int C, int n_trials);
 #define NS_CHUNK_MAX 256   // samples per chunk at most: chunk_samples (sampled_side.h), the rule of every chunked sampled call
 
+// The bit rows of a chunk of c samples Y[c][L][N][N] queued on the handle's stream (k_tri_pack), W = ceil(N / 64) 64-bit words
+// per row: Aout[c][L][N][W], row i the targets of i, and Ain[c][L][N][W], row i the sources of i, for A = (Y > 0) with the
+// diagonal cleared; the bits at and above N are zero.  triads.hip
+int tri_pack_chunk(vmr_ctx* h, const uint8_t* Y, int c, unsigned long long* Aout, unsigned long long* Ain);
+
 // The edge probabilities queued on the handle's stream: P[l][i][j] = sum_{k>=1} rho_ijk (k ascending), natural order, from rho
 // by tie or by sorted position (k_ns_exp_p).  part: [L][nb][4] doubles, of which column 1 receives the workgroups' sums of
 // sum_k k rho_k; nb workgroups per layer.  The caller has run ensure_rho_ext.  netstats.hip

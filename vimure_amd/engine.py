@@ -58,6 +58,11 @@ class MixingArgumentError(EngineError, ValueError):
     not fit in the free device memory."""
 
 
+class ConnectivityArgumentError(EngineError, ValueError):
+    """An argument `sample_connectivity` refuses (VMR_EINVAL): n_samples or n_trials below 1, more nodes than the closure's
+    working set holds (`_lib.CONN_NMAX`), temporaries that do not fit in the free device memory."""
+
+
 SCORE_OUTPUTS = ("hist", "conf", "sums", "auc", "auc_pairs")
 INF_SELECT = {"none": 0, "lost": _lib.INF_LOST, "gained": _lib.INF_GAINED, "both": _lib.INF_LOST | _lib.INF_GAINED}
 # columns of the table of `CaviEngine.reporter_influence`, in the order of vmr_reporter_influence's row pointers
@@ -476,6 +481,32 @@ class CaviEngine:
         out = np.zeros((self.L, _lib.TRIAD_NSTAT), np.float64)
         self._check(self.lib.vmr_expected_triads(self._h, out.ctypes.data), TriadArgumentError)
         return {k: out[:, q].copy() for q, k in enumerate(_lib.TRIAD_NAMES)}
+
+    def sample_connectivity(self, seed, n_samples, n_trials=1, hist=True, nodes=False):
+        """Connectivity of n_samples posterior samples, computed on the device (vmr_sample_connectivity): sample s is
+        `self.sample(seed + s, n_trials)`, A = (Y > 0) with the diagonal cleared, U = A | A.T, d(i, j) the length of a shortest
+        directed path in A.  Returns a dict of int64 [S, L] arrays keyed by `_lib.CONN_NAMES`: `components_w`, `giant_w`, `pairs_w`
+        (ordered pairs in one weak component), `isolates`, `components_s`, `giant_s`, `pairs_s` (ordered pairs that reach each
+        other), `reach_pairs` #{i != j : d(i, j) finite}, `dist_sum` (the sum of those distances) and `diameter` (their maximum);
+        with hist=True also `dist_hist` int64 [S, L, 64], bin d - 1 the ordered pairs at distance d, the last bin every distance
+        >= 64; with nodes=True also `node_comp_w`, `node_comp_s` (the smallest node index of the node's weak / strong component),
+        `node_reach_out`, `node_reach_in` (nodes it reaches / is reached by) and `node_dist_out`, `node_dist_in` (the sums of
+        those distances), int32 [S, L, N].  N is at most `_lib.CONN_NMAX`.  A refused argument raises
+        `ConnectivityArgumentError`."""
+        S = int(n_samples)
+        counts = np.zeros((max(S, 0), self.L, _lib.CONN_NSTAT), np.uint64)
+        dh = np.zeros((max(S, 0), self.L, _lib.CONN_NDIST), np.uint64) if hist else None
+        na = [np.zeros((max(S, 0), self.L, self.N), np.int32) if nodes else None for _ in _lib.CONN_NODE_NAMES]
+        self._check(self.lib.vmr_sample_connectivity(self._h, int(seed) & (2 ** 64 - 1), S, int(n_trials), counts.ctypes.data,
+                                                     dh.ctypes.data if hist else None, *[a.ctypes.data if nodes else None for a in na]),
+                    ConnectivityArgumentError)
+        c = counts.astype(np.int64)
+        out = {k: np.ascontiguousarray(c[..., q]) for q, k in enumerate(_lib.CONN_NAMES)}
+        if hist:
+            out["dist_hist"] = dh.astype(np.int64)
+        if nodes:
+            out.update(zip(_lib.CONN_NODE_NAMES, na))
+        return out
 
     def _mixing_args(self, groups, C):
         """(codes int32 [N] or None, C) for the mixing calls: C None is the largest code + 1."""

@@ -793,6 +793,27 @@ class VimureModel(TransformerMixin, BaseEstimator):
         return MixingStats(self.N, counts, codes=codes, labels=labels, expected=expected, skip_diagonal=skip_diagonal, seed=seed,
                            n_trials=n_trials)
 
+    def posterior_connectivity(self, n_samples=100, seed=None, n_trials=1, nodes=False, X=None, R=None):
+        """Does the inferred network hang together, how large is its giant component, who reaches whom and in how many steps --
+        over the posterior of the network, computed on the GPU (vmr_sample_connectivity): n_samples draws of Y from q(Y) -- sample
+        s is `sample_inferred_model(N=n_trials, seed=seed + s, device=True)[0]` -- reduced where rho lives to the weak and strong
+        components, the reachable ordered pairs, the sum, the histogram and the maximum of their shortest-path lengths (self-loops
+        left out); only those integers cross PCIe.  nodes=True: also every node's component labels, how many nodes it reaches
+        and is reached by and the sums of those distances.  Returns a `connectivity.ConnectivityStats`: the integers, the giant
+        components' fractions, connectedness, average path length, global efficiency, with nodes the closeness centralities and
+        `same_component(i, j)`, `summary()` and `frame()`.  There is no closed form under the mean field, hence no expectations.
+        At most 2048 nodes.  seed None: the fit's.  Engine as in `calculate_mean_poisson`."""
+        from .connectivity import ConnectivityStats
+        if seed is None:
+            seed = self.seed
+        eng, tmp = self._ppc_engine(X, R)
+        try:
+            counts = eng.sample_connectivity(seed, n_samples, n_trials=n_trials, hist=True, nodes=bool(nodes))
+        finally:
+            if tmp:
+                eng.close()
+        return ConnectivityStats(self.N, counts, seed=seed, n_trials=n_trials)
+
     def posterior_predictive_check(self, n_rep=100, seed=None, params="draw", n_trials=1, by_reporter=False, X=None, R=None):
         """Does data drawn from the fitted model look like the data it was fitted to?  n_rep replicated datasets are drawn on the
         GPU over the support of R and reduced there (vmr_ppc_replicates; no replicate is written) to the integers of
