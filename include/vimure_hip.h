@@ -388,6 +388,58 @@ int vmr_sample_connectivity(vmr_handle h, uint64_t seed, int n_samples, int n_tr
                             int32_t* node_comp_w, int32_t* node_comp_s, int32_t* node_reach_out, int32_t* node_reach_in,
                             int32_t* node_dist_out, int32_t* node_dist_in);
 
+/* Diffusion centrality of n_samples posterior samples of Y, computed where rho lives -- what a user otherwise gets from
+ * `scipy.sparse` matrix-vector products on every `sample_inferred_model` draw.  Sample s is exactly what vmr_sample(h, seed + s,
+ * n_trials, ..) writes (seed + s mod 2^64).  Per sample and layer l: A_ij = (Y_ij > 0) with the DIAGONAL CLEARED, and M chosen by
+ * direction: VMR_CENT_OUT M = A (walks leave the node: how far its word travels), VMR_CENT_IN M = A^T, VMR_CENT_UNION
+ * M = A | A^T.  x_0 = 1, x_t = q_l (M x_{t-1}), c = x_1 + x_2 + .. + x_T added in ascending t: c = sum_{t=1..T} (q_l M)^t 1, the
+ * expected number of times a message from the node is heard within T rounds when each tie passes it with probability q_l
+ * (Banerjee et al. 2013).  T = 1 is q times the degree; large T with q < 1 / lambda_1 is Katz centrality.
+ * rank[v] = #{u : c[u] > c[v]}, strict comparisons of the device's own c: 0 is the most central node, tied nodes share the
+ * smaller rank.
+ * q: host double [L], each finite and in [0, 1]; T in [1, VMR_CENT_TMAX]; top_k in [1, N].  Host outputs:
+ *   node_sum, node_sumsq   sum_s c and sum_s c^2 (the square rounded, then added), in ascending s     double [L][N]
+ *   node_rank_sum          sum_s rank                                                                uint64 [L][N]
+ *   node_top               #{s : rank < top_k}                                                       uint32 [L][N]
+ *   summary                (sum_v c[v] by a fixed tree, max_v c[v])                                  double [n_samples][L][2]
+ *   values                 the c of every sample                                                     double [n_samples][L][N]
+ * node_sum may not be NULL, every other output may be.
+ * The samples are packed into the bit rows of vmr_sample_triads; one workgroup per (layer, sample) keeps x_{t-1} and x_t in LDS
+ * (16 N bytes) and re-reads the rows from L2 on each step.  That working set bounds N: N <= VMR_CENT_NMAX = 2048 (32 KiB of LDS
+ * per workgroup); a larger N is refused with VMR_EINVAL and a message that names the bound.  A row's sum, the sum over t, the
+ * per-node sums over s and the summary's tree have a fixed order and nothing is added with floating-point atomics: every output is
+ * bit-identical from run to run and for any chunking.  When q_l = 2^-k and the walk counts are small enough every number is
+ * exact.  Reads the CURRENT rho (after vmr_restore: the snapshot's) once per chunk of samples; any K, any n_trials >= 1, both
+ * data formats.  A chunk (L N^2 + 16 L N ceil(N/64) + 12 L N bytes per sample plus the summary when asked for, beside 28 L N
+ * bytes of per-node accumulators per call; half of the free device memory at most, 256 samples at most, VMR_NETSTATS_CHUNK at
+ * most) is freed before return; a single sample that does not fit is refused with VMR_EINVAL.
+ * VMR_EINVAL, with a message that names the argument and whatever the state of the handle: N above the bound, direction outside
+ * 0..2, T or top_k out of range, q NULL or an entry non-finite or outside [0, 1], node_sum NULL, n_samples < 1, n_trials < 1.
+ * Before vmr_set_state: VMR_ESTATE.  Synchronises. */
+#define VMR_CENT_OUT 0
+#define VMR_CENT_IN 1
+#define VMR_CENT_UNION 2
+#define VMR_CENT_TMAX 64     /* steps at most */
+#define VMR_CENT_NMAX 2048   /* nodes at most (vmr_sample_centrality) */
+int vmr_sample_centrality(vmr_handle h, uint64_t seed, int n_samples, int n_trials, const double* q, int T, int direction, int top_k,
+                          double* node_sum, double* node_sumsq, uint64_t* node_rank_sum, uint32_t* node_top, double* summary,
+                          double* values);
+
+/* The same recursion on the posterior mean network, no sampling: p_ij = sum_{k>=1} rho_ijk (k ascending, the number of
+ * vmr_expected_stats), p_ii := 0, and M = P (VMR_CENT_OUT), P^T (VMR_CENT_IN) or U with u_ij = 1 - (1 - p_ij)(1 - p_ji)
+ * (VMR_CENT_UNION); out[l] = sum_{t=1..T} (q_l M)^t 1, host double [L][N].
+ * What this number is: a PLUG-IN, the centrality of the mean network.  For OUT and IN with T <= 2 it is also the exact
+ * expectation of the sampled c: a walk of length <= 2 without self-loops uses distinct ties, and distinct ties are independent
+ * under the mean field.  What it is not: for T >= 3 it is not that expectation (a walk i -> j -> i -> j uses a tie twice, and
+ * E[a^2] = p, not p^2), and for UNION it is not at any T >= 2 (u_ij and u_ji are one variable).  Take the expectation from
+ * vmr_sample_centrality then.
+ * Any N: x lives in global memory.  P (or P^T, or U) is formed once -- IN and UNION keep it beside P, written through a transposed
+ * tile so that every step reads along rows -- then T batched FP64 matrix-vector steps, a wave per row with a fixed shuffle tree,
+ * no atomics, on a grid that depends on N and L only: bit-identical from run to run.  Temporaries: 8 L N^2 bytes, 16 L N^2 for IN
+ * and UNION; refused with VMR_EINVAL when they do not fit.  q, T and direction as for vmr_sample_centrality; out NULL:
+ * VMR_EINVAL.  Before vmr_set_state: VMR_ESTATE.  Synchronises. */
+int vmr_mean_centrality(vmr_handle h, const double* q, int T, int direction, double* out);
+
 /* Posterior predictive checks: n_rep replicated datasets drawn from the fitted model over the support of the handle's own R and
  * reduced where they are drawn -- no replicate is ever written -- and the same reduction of the observed data.
  * Replicate r: Y_r is exactly what vmr_sample(h, seed_y + r, n_trials, ..) writes (mod 2^64; the CURRENT rho, after vmr_restore

@@ -20,6 +20,8 @@ CONN_NSTAT, CONN_NDIST, CONN_NMAX = 10, 64, 2048
 CONN_NAMES = ["components_w", "giant_w", "pairs_w", "isolates", "components_s", "giant_s", "pairs_s", "reach_pairs", "dist_sum",
               "diameter"]
 CONN_NODE_NAMES = ["node_comp_w", "node_comp_s", "node_reach_out", "node_reach_in", "node_dist_out", "node_dist_in"]
+CENT_NMAX, CENT_TMAX = 2048, 64
+CENT_DIRECTIONS = ("out", "in", "union")   # VMR_CENT_OUT, VMR_CENT_IN, VMR_CENT_UNION
 EDGE_REPORTED, EDGE_INFERRED = 1, 2
 SCORE_RHO1, SCORE_PROB = 0, 1
 SCORE_NCONF, SCORE_NSUM, SCORE_MAX_THR = 5, 4, 4096
@@ -77,6 +79,8 @@ SIGNATURES = {
     "vmr_sample_mixing": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vmr_expected_mixing": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vmr_sample_connectivity": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int] + [C.c_void_p] * 8),
+    "vmr_sample_centrality": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6),
+    "vmr_mean_centrality": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "vmr_ppc_replicates": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
     "vmr_ppc_observed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -36,6 +36,7 @@ def units(dev=False):
          ("triads", os.path.join(CSRC, "triads.hip"), extra),          # triad statistics of posterior samples and their expectations
          ("mixing", os.path.join(CSRC, "mixing.hip"), extra),          # mixing by node attribute and overlap between layers
          ("connectivity", os.path.join(CSRC, "connectivity.hip"), extra),  # components, reach and path lengths of posterior samples
+         ("centrality", os.path.join(CSRC, "centrality.hip"), extra),  # diffusion centrality of posterior samples and of the mean network
          ("ppc_rep", os.path.join(CSRC, "ppc_rep.hip"), extra),        # posterior predictive replicates, reduced
          ("edge_table", os.path.join(CSRC, "edge_table.hip"), extra),  # the inferred network as an edge table
          ("score_truth", os.path.join(CSRC, "score_truth.hip"), extra),  # the posterior scored against a ground truth

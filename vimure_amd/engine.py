@@ -63,6 +63,13 @@ class ConnectivityArgumentError(EngineError, ValueError):
     working set holds (`_lib.CONN_NMAX`), temporaries that do not fit in the free device memory."""
 
 
+class CentralityArgumentError(EngineError, ValueError):
+    """An argument `sample_centrality` / `mean_centrality` refuse (VMR_EINVAL): a direction other than out, in or union, T outside
+    [1, `_lib.CENT_TMAX`], top_k outside [1, N], a q that is not finite or outside [0, 1], n_samples or n_trials below 1, more
+    nodes than the walk's working set holds (`_lib.CENT_NMAX`, sampled call only), temporaries that do not fit in the free device
+    memory."""
+
+
 SCORE_OUTPUTS = ("hist", "conf", "sums", "auc", "auc_pairs")
 INF_SELECT = {"none": 0, "lost": _lib.INF_LOST, "gained": _lib.INF_GAINED, "both": _lib.INF_LOST | _lib.INF_GAINED}
 # columns of the table of `CaviEngine.reporter_influence`, in the order of vmr_reporter_influence's row pointers
@@ -506,6 +513,54 @@ class CaviEngine:
             out["dist_hist"] = dh.astype(np.int64)
         if nodes:
             out.update(zip(_lib.CONN_NODE_NAMES, na))
+        return out
+
+    def _centrality_args(self, q, direction):
+        """(q float64 [L], the direction's code) for the centrality calls; what is not a number or a name is refused here."""
+        try:
+            qa = np.ascontiguousarray(np.broadcast_to(np.asarray(q, dtype=np.float64), (self.L,)))
+        except (TypeError, ValueError):
+            raise CentralityArgumentError(f"q must be a scalar or {self.L} numbers, one per layer") from None
+        if isinstance(direction, str):
+            if direction not in _lib.CENT_DIRECTIONS:
+                raise CentralityArgumentError(f"direction must be one of {_lib.CENT_DIRECTIONS}, got {direction!r}")
+            direction = _lib.CENT_DIRECTIONS.index(direction)
+        return qa, int(direction)
+
+    def sample_centrality(self, seed, n_samples, q, T, direction="out", top_k=10, n_trials=1, values=False):
+        """Diffusion centrality of n_samples posterior samples, computed on the device (vmr_sample_centrality): sample s is
+        `self.sample(seed + s, n_trials)`, A = (Y > 0) with the diagonal cleared, M = A ("out": walks leave the node), A.T ("in")
+        or A | A.T ("union"), and c = sum_{t=1..T} (q_l M)^t 1 per layer l; q: a scalar or [L], each in [0, 1]; T in [1,
+        `_lib.CENT_TMAX`].  rank[v] = #{u : c[u] > c[v]} (0: the most central node; ties share the smaller rank).  Returns a dict:
+        `node_sum`, `node_sumsq` float64 [L, N] (sum_s c, sum_s c^2), `node_rank_sum` int64 [L, N], `node_top` int64 [L, N]
+        (#{s : rank < top_k}), `total`, `max` float64 [S, L] (sum_v c[v], max_v c[v]); with values=True also `values` float64
+        [S, L, N].  Every number is the same from run to run and for any chunking.  N is at most `_lib.CENT_NMAX`.  A refused
+        argument raises `CentralityArgumentError`."""
+        S = int(n_samples)
+        qa, d = self._centrality_args(q, direction)
+        LN = (self.L, self.N)
+        ns, nq = np.zeros(LN, np.float64), np.zeros(LN, np.float64)
+        nr, ntop = np.zeros(LN, np.uint64), np.zeros(LN, np.uint32)
+        sm = np.zeros((max(S, 0), self.L, 2), np.float64)
+        vals = np.zeros((max(S, 0),) + LN, np.float64) if values else None
+        self._check(self.lib.vmr_sample_centrality(self._h, int(seed) & (2 ** 64 - 1), S, int(n_trials), qa.ctypes.data, int(T), d, int(top_k),
+                                                   ns.ctypes.data, nq.ctypes.data, nr.ctypes.data, ntop.ctypes.data, sm.ctypes.data,
+                                                   vals.ctypes.data if values else None),
+                    CentralityArgumentError)
+        out = {"node_sum": ns, "node_sumsq": nq, "node_rank_sum": nr.astype(np.int64), "node_top": ntop.astype(np.int64),
+               "total": np.ascontiguousarray(sm[..., 0]), "max": np.ascontiguousarray(sm[..., 1])}
+        if values:
+            out["values"] = vals
+        return out
+
+    def mean_centrality(self, q, T, direction="out"):
+        """The diffusion centrality of the posterior MEAN network (vmr_mean_centrality), no sampling: float64 [L, N],
+        sum_{t=1..T} (q_l M)^t 1 with M = P ("out"; p_ij = sum_{k>=1} rho_ijk, p_ii := 0), P.T ("in") or U ("union"; u_ij = 1 -
+        (1 - p_ij)(1 - p_ji)).  A plug-in: for "out" and "in" with T <= 2 it is also the expectation of the sampled centrality,
+        for T >= 3 or "union" it is not.  Any N.  A refused argument raises `CentralityArgumentError`."""
+        qa, d = self._centrality_args(q, direction)
+        out = np.zeros((self.L, self.N), np.float64)
+        self._check(self.lib.vmr_mean_centrality(self._h, qa.ctypes.data, int(T), d, out.ctypes.data), CentralityArgumentError)
         return out
 
     def _mixing_args(self, groups, C):

@@ -814,6 +814,35 @@ class VimureModel(TransformerMixin, BaseEstimator):
                 eng.close()
         return ConnectivityStats(self.N, counts, seed=seed, n_trials=n_trials)
 
+    def posterior_centrality(self, q=None, T=3, direction="out", n_samples=100, seed=None, n_trials=1, top_k=10, values=False,
+                             X=None, R=None):
+        """Who is central, and how sure is the posterior of it?  Diffusion centrality (Banerjee et al. 2013) of every node over
+        the posterior of the network, computed on the GPU (vmr_sample_centrality, vmr_mean_centrality): n_samples draws of Y from
+        q(Y) -- sample s is `sample_inferred_model(N=n_trials, seed=seed + s, device=True)[0]` -- and per draw and layer
+        c = sum_{t=1..T} (q M)^t 1 with M = A = (Y > 0) without self-loops (direction "out": how far a node's word travels), A.T
+        ("in") or A | A.T ("union"); reduced where rho lives to every node's sum and sum of squares of c, the sum of its ranks and
+        how often it is among the top_k, and each draw's total and maximum; only those cross PCIe (values=True: also every
+        draw's c).  T = 1 is q times the degree; T large with q below 1 / lambda_1 is Katz centrality.
+        q: a scalar or one value per layer in [0, 1].  q None takes, per layer, min(1, N / expected edges) from `expected_stats()`:
+        the reciprocal of the expected mean degree, at which a walk's expected offspring is one -- a choice of scale, not the
+        literature's 1 / lambda_1.  Returns a `centrality.CentralityStats`: mean, sd, expected_rank, top_prob, the plug-in
+        centrality of the mean network (`plug_in`: the expectation of c only for "out" / "in" with T <= 2), `top()`, `frame()` and
+        `summary()`.  At most 2048 nodes.  seed None: the fit's.  Engine as in `calculate_mean_poisson`."""
+        from .centrality import CentralityStats, default_q
+        if seed is None:
+            seed = self.seed
+        eng, tmp = self._ppc_engine(X, R)
+        try:
+            if q is None:
+                q = default_q(self.N, eng.expected_stats()["edges"])
+            counts = eng.sample_centrality(seed, n_samples, q, T, direction=direction, top_k=top_k, n_trials=n_trials, values=bool(values))
+            plug_in = eng.mean_centrality(q, T, direction=direction)
+        finally:
+            if tmp:
+                eng.close()
+        return CentralityStats(self.N, counts, np.broadcast_to(np.asarray(q, dtype=np.float64), (self.L,)).copy(), T, direction=direction,
+                               top_k=top_k, plug_in=plug_in, seed=seed, n_trials=n_trials)
+
     def posterior_predictive_check(self, n_rep=100, seed=None, params="draw", n_trials=1, by_reporter=False, X=None, R=None):
         """Does data drawn from the fitted model look like the data it was fitted to?  n_rep replicated datasets are drawn on the
         GPU over the support of R and reduced there (vmr_ppc_replicates; no replicate is written) to the integers of
