@@ -440,6 +440,51 @@ int vmr_sample_centrality(vmr_handle h, uint64_t seed, int n_samples, int n_tria
  * VMR_EINVAL.  Before vmr_set_state: VMR_ESTATE.  Synchronises. */
 int vmr_mean_centrality(vmr_handle h, const double* q, int T, int direction, double* out);
 
+/* Betweenness centrality of n_samples posterior samples of Y, computed where rho lives -- what a user otherwise gets from
+ * `networkx.betweenness_centrality(normalized=False)` on every `sample_inferred_model` draw.  Sample s is exactly what
+ * vmr_sample(h, seed + s, n_trials, ..) writes (seed + s mod 2^64).  Per sample and layer: A_ij = (Y_ij > 0) with the DIAGONAL
+ * CLEARED and the search graph G = A (VMR_BTW_DIRECTED) or A | A^T (VMR_BTW_UNION).  With sigma_st the number of shortest s -> t
+ * paths in G and sigma_st(v) the number of those through v,
+ *   b(v) = sum over s != v != t, s != t, t reachable from s, of sigma_st(v) / sigma_st:
+ * unnormalised, endpoints excluded; for UNION the sum over the ordered pairs is halved, so that every unordered pair counts
+ * once.  There is no "in" direction: reversing the graph leaves b unchanged.  sigma is carried in FP64 -- exact while it is
+ * <= 2^53, and for every power of two beyond; it never wraps; past 1.8e308 it is infinite and b undefined.
+ * rank[v] = #{u : b[u] > b[v]}, strict comparisons of the device's own b: 0 is the first broker, tied nodes share the smaller
+ * rank.  top_k in [1, N].  Host outputs:
+ *   node_sum, node_sumsq   sum_s b and sum_s b^2 (the square rounded, then added), in ascending s     double [L][N]
+ *   node_rank_sum          sum_s rank                                                                uint64 [L][N]
+ *   node_top               #{s : rank < top_k}                                                       uint32 [L][N]
+ *   summary                (sum_v b[v] by a fixed tree, max_v b[v])                                  double [n_samples][L][2]
+ *   values                 the b of every sample                                                     double [n_samples][L][N]
+ * node_sum may not be NULL, every other output may be.
+ * The samples are packed into the bit rows of vmr_sample_triads; one workgroup per (block of 16 consecutive sources, layer,
+ * sample) runs Brandes' algorithm by levels with the levels, sigma and delta of one source in LDS (18 N bytes) and reads every
+ * bit row three times per source from L2.  That working set bounds N: N <= VMR_BTW_NMAX = 2048; a larger N is refused with
+ * VMR_EINVAL and a message that names the bound.  The block of sources depends on N only; a node's neighbours are added in a
+ * fixed order, the sources of a block in ascending order, the blocks in ascending order, the samples in ascending s, the total by
+ * a fixed tree, and nothing is added with floating-point atomics: every output is bit-identical from run to run and for any
+ * chunking.  Every level loop ends after N - 1 levels at the latest.  Reads the CURRENT rho (after vmr_restore: the snapshot's)
+ * once per chunk of samples; any K, any n_trials >= 1, both data formats.  A chunk (L N^2 + 16 L N ceil(N/64) +
+ * 8 L N ceil(N/16) + 12 L N bytes per sample plus the summary when asked for, beside 28 L N bytes of per-node accumulators per
+ * call; half of the free device memory at most, 256 samples at most, VMR_NETSTATS_CHUNK at most) is freed before return; a single
+ * sample that does not fit is refused with VMR_EINVAL.
+ * VMR_EINVAL, with a message that names the argument and whatever the state of the handle: n_samples < 1, n_trials < 1, N above
+ * the bound, direction outside 0..1, top_k out of range, node_sum NULL.  Before vmr_set_state: VMR_ESTATE.  Synchronises. */
+#define VMR_BTW_DIRECTED 0
+#define VMR_BTW_UNION 1
+#define VMR_BTW_NMAX 2048   /* nodes at most */
+int vmr_sample_betweenness(vmr_handle h, uint64_t seed, int n_samples, int n_trials, int direction, int top_k, double* node_sum,
+                           double* node_sumsq, uint64_t* node_rank_sum, uint32_t* node_top, double* summary, double* values);
+
+/* The same b, by the same packing and the same kernels, of n networks the caller supplies -- the inferred network, a ground
+ * truth, a designed graph.  Y: HOST uint8 [n][L][N][N]; an entry > 0 is a tie, the diagonal is ignored.  values: host double
+ * [n][L][N].  The handle gives N, L, the device and the stream and nothing else: the call works before vmr_set_state and does not
+ * touch rho.  Network q of a call equals what vmr_sample_betweenness returns in `values` for a sample with the same ties, bit
+ * for bit.  The networks are uploaded in chunks (the bytes of vmr_sample_betweenness per network, without the ranks).
+ * VMR_EINVAL, with a message that names the argument: n < 1, N above VMR_BTW_NMAX, direction outside 0..1, Y or values NULL,
+ * a single network whose temporaries do not fit.  Synchronises. */
+int vmr_network_betweenness(vmr_handle h, const uint8_t* Y, int n, int direction, double* values);
+
 /* Posterior predictive checks: n_rep replicated datasets drawn from the fitted model over the support of the handle's own R and
  * reduced where they are drawn -- no replicate is ever written -- and the same reduction of the observed data.
  * Replicate r: Y_r is exactly what vmr_sample(h, seed_y + r, n_trials, ..) writes (mod 2^64; the CURRENT rho, after vmr_restore

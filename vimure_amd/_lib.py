@@ -22,6 +22,8 @@ CONN_NAMES = ["components_w", "giant_w", "pairs_w", "isolates", "components_s", 
 CONN_NODE_NAMES = ["node_comp_w", "node_comp_s", "node_reach_out", "node_reach_in", "node_dist_out", "node_dist_in"]
 CENT_NMAX, CENT_TMAX = 2048, 64
 CENT_DIRECTIONS = ("out", "in", "union")   # VMR_CENT_OUT, VMR_CENT_IN, VMR_CENT_UNION
+BTW_NMAX = 2048
+BTW_DIRECTIONS = ("directed", "union")     # VMR_BTW_DIRECTED, VMR_BTW_UNION
 EDGE_REPORTED, EDGE_INFERRED = 1, 2
 SCORE_RHO1, SCORE_PROB = 0, 1
 SCORE_NCONF, SCORE_NSUM, SCORE_MAX_THR = 5, 4, 4096
@@ -81,6 +83,8 @@ SIGNATURES = {
     "vmr_sample_connectivity": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int] + [C.c_void_p] * 8),
     "vmr_sample_centrality": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6),
     "vmr_mean_centrality": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "vmr_sample_betweenness": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6),
+    "vmr_network_betweenness": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "vmr_ppc_replicates": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
     "vmr_ppc_observed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -17,7 +17,8 @@ HOST_SRC = os.path.join(CSRC, "host_init.c")
 HOST_LIB = os.path.join(HERE, "libvimure_host.so")
 HEADERS = [os.path.join(CSRC, "vmr_internal.h"), os.path.join(CSRC, "sweep_sl.h"), os.path.join(CSRC, "sweep_gen.h"),
            os.path.join(CSRC, "sample_draw.h"), os.path.join(CSRC, "report_draw.h"), os.path.join(CSRC, "ppc_layer.h"), os.path.join(CSRC, "rho_row.h"),
-           os.path.join(CSRC, "report_lik.h"), os.path.join(CSRC, "read_side.h"), os.path.join(CSRC, "sampled_side.h"), os.path.join(CSRC, "sl_balance.h"),
+           os.path.join(CSRC, "report_lik.h"), os.path.join(CSRC, "read_side.h"), os.path.join(CSRC, "sampled_side.h"), os.path.join(CSRC, "node_fold.h"),
+           os.path.join(CSRC, "sl_balance.h"),
            os.path.join(ROOT, "include", "vimure_hip.h")]
 KS = (2, 3, 4, 5, 6, 7, 8)
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
@@ -37,6 +38,7 @@ def units(dev=False):
          ("mixing", os.path.join(CSRC, "mixing.hip"), extra),          # mixing by node attribute and overlap between layers
          ("connectivity", os.path.join(CSRC, "connectivity.hip"), extra),  # components, reach and path lengths of posterior samples
          ("centrality", os.path.join(CSRC, "centrality.hip"), extra),  # diffusion centrality of posterior samples and of the mean network
+         ("betweenness", os.path.join(CSRC, "betweenness.hip"), extra),  # betweenness centrality of posterior samples and of given networks
          ("ppc_rep", os.path.join(CSRC, "ppc_rep.hip"), extra),        # posterior predictive replicates, reduced
          ("edge_table", os.path.join(CSRC, "edge_table.hip"), extra),  # the inferred network as an edge table
          ("score_truth", os.path.join(CSRC, "score_truth.hip"), extra),  # the posterior scored against a ground truth

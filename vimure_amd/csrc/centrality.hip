@@ -17,8 +17,8 @@
 // x[bit] from LDS, a fixed xor tree runs over the G lanes and the group's first lane stores q times the sum.  One barrier per
 // step.  After step T, c goes to LDS and every thread counts, for its nodes, the strictly larger entries (all lanes read the same
 // address: a broadcast); c, the rank and the sample's (sum by a fixed tree, maximum) go to the chunk's buffers.
-// k_cent_fold: one thread per (layer, node) adds the chunk's samples in ascending s into the per-node accumulators, which span
-// the chunks of a call.
+// k_node_fold (node_fold.h): one thread per (layer, node) adds the chunk's samples in ascending s into the per-node accumulators,
+// which span the chunks of a call.
 // Every sum has a fixed order and there is no floating-point atomic: every output is the same from run to run and for any
 // chunking.
 // Bytes of the walk per (sample, layer): the rows are read on each of the T steps, 8 N W T bytes from L2 (16 N W T with UNION)
@@ -28,18 +28,12 @@
 // zeroed; IN and UNION keep a second matrix (P^T, or U with u_ij = 1 - (1 - p_ij)(1 - p_ji)) written through a transposed tile in
 // LDS, so that every one of the T steps reads along rows: a wave per row, a fixed shuffle tree, no atomics, x in global memory.
 #include <cmath>
-#include "sampled_side.h"
+#include "node_fold.h"
 
 namespace {
 
 #define CENT_TPB 256
 #define CENT_FLY 4   // rows whose words a lane group has in flight
-
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
 
 // One step: xn[i] = q * sum over the set bits j of row i of A (| B with UNION) of x[j], i in [0, N).  Every lane of the
 // workgroup calls it; the lane's own words in ascending order, then the xor tree over the G = 1 << lG lanes of the row.
@@ -152,29 +146,6 @@ __global__ __launch_bounds__(CENT_TPB) void k_cent_walk(const u64* __restrict__ 
       summary[sl * 2 + 1] = m;
     }
   }
-}
-
-// One thread per (l, v): the chunk's c samples in ascending s into the call's accumulators.  The square is rounded before it is
-// added (no contraction), as a host restatement rounds it.
-__global__ __launch_bounds__(256) void k_cent_fold(const double* __restrict__ cval, const unsigned* __restrict__ crank, int c, size_t LN,
-                                                   unsigned top_k, double* __restrict__ sum, double* __restrict__ sumsq, u64* __restrict__ rank_sum,
-                                                   unsigned* __restrict__ top) {
-#pragma clang fp contract(off)
-  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= LN) return;
-  double a = sum[e], b = sumsq[e];
-  u64 r = rank_sum[e];
-  unsigned tp = top[e];
-  for (int s = 0; s < c; ++s) {
-    const double v = cval[(size_t)s * LN + e];
-    const unsigned k = crank[(size_t)s * LN + e];
-    const double v2 = v * v;
-    a += v;
-    b += v2;
-    r += k;
-    tp += k < top_k ? 1u : 0u;
-  }
-  sum[e] = a; sumsq[e] = b; rank_sum[e] = r; top[e] = tp;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -329,7 +300,7 @@ extern "C" int vmr_sample_centrality(vmr_handle h, uint64_t seed, int n_samples,
     else if (kpt <= 4) cent_launch_walk<4>(h, c, smem, Ao, Ai, W, lG, direction, T, qd, cval, crank, sm);
     else cent_launch_walk<8>(h, c, smem, Ao, Ai, W, lG, direction, T, qd, cval, crank, sm);
     HIPCHK(h, hipGetLastError());
-    hipLaunchKernelGGL(k_cent_fold, dim3(grid_for(LN, 256, 0xffffffffu)), dim3(256), 0, h->stream, cval, crank, c, LN, (unsigned)top_k, asum, asq,
+    hipLaunchKernelGGL(k_node_fold, dim3(grid_for(LN, 256, 0xffffffffu)), dim3(256), 0, h->stream, cval, crank, c, LN, (unsigned)top_k, asum, asq,
                        arank, atop);
     HIPCHK(h, hipGetLastError());
     if (values) HIPCHK(h, hipMemcpyAsync(values + s0 * LN, cval, (size_t)c * LN * 8, hipMemcpyDeviceToHost, h->stream));

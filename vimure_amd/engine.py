@@ -70,6 +70,12 @@ class CentralityArgumentError(EngineError, ValueError):
     memory."""
 
 
+class BetweennessArgumentError(EngineError, ValueError):
+    """An argument `sample_betweenness` / `network_betweenness` refuse (VMR_EINVAL): a direction other than directed or union,
+    top_k outside [1, N], n_samples or n_trials below 1, networks of another shape than the handle's, more nodes than a source's
+    working set holds (`_lib.BTW_NMAX`), temporaries that do not fit in the free device memory."""
+
+
 SCORE_OUTPUTS = ("hist", "conf", "sums", "auc", "auc_pairs")
 INF_SELECT = {"none": 0, "lost": _lib.INF_LOST, "gained": _lib.INF_GAINED, "both": _lib.INF_LOST | _lib.INF_GAINED}
 # columns of the table of `CaviEngine.reporter_influence`, in the order of vmr_reporter_influence's row pointers
@@ -562,6 +568,58 @@ class CaviEngine:
         out = np.zeros((self.L, self.N), np.float64)
         self._check(self.lib.vmr_mean_centrality(self._h, qa.ctypes.data, int(T), d, out.ctypes.data), CentralityArgumentError)
         return out
+
+    @staticmethod
+    def _betweenness_direction(direction):
+        """The direction's code for the betweenness calls; a name that is none is refused here."""
+        if isinstance(direction, str):
+            if direction not in _lib.BTW_DIRECTIONS:
+                raise BetweennessArgumentError(f"direction must be one of {_lib.BTW_DIRECTIONS}, got {direction!r}")
+            return _lib.BTW_DIRECTIONS.index(direction)
+        return int(direction)
+
+    def sample_betweenness(self, seed, n_samples, direction="directed", top_k=10, n_trials=1, values=False):
+        """Betweenness centrality of n_samples posterior samples, computed on the device (vmr_sample_betweenness): sample s is
+        `self.sample(seed + s, n_trials)`, A = (Y > 0) with the diagonal cleared, the search graph A ("directed") or A | A.T
+        ("union"), and b[v] = sum over s != v != t of the share of the shortest s -> t paths through v: unnormalised, endpoints
+        excluded, every unordered pair once for "union" -- `networkx.betweenness_centrality(normalized=False)`.  rank[v] =
+        #{u : b[u] > b[v]} (0: the first broker; ties share the smaller rank).  Returns a dict: `node_sum`, `node_sumsq` float64
+        [L, N] (sum_s b, sum_s b^2), `node_rank_sum` int64 [L, N], `node_top` int64 [L, N] (#{s : rank < top_k}), `total`, `max`
+        float64 [S, L] (sum_v b[v], max_v b[v]); with values=True also `values` float64 [S, L, N].  Every number is the same from
+        run to run and for any chunking.  N is at most `_lib.BTW_NMAX`.  A refused argument raises `BetweennessArgumentError`."""
+        S = int(n_samples)
+        d = self._betweenness_direction(direction)
+        LN = (self.L, self.N)
+        ns, nq = np.zeros(LN, np.float64), np.zeros(LN, np.float64)
+        nr, ntop = np.zeros(LN, np.uint64), np.zeros(LN, np.uint32)
+        sm = np.zeros((max(S, 0), self.L, 2), np.float64)
+        vals = np.zeros((max(S, 0),) + LN, np.float64) if values else None
+        self._check(self.lib.vmr_sample_betweenness(self._h, int(seed) & (2 ** 64 - 1), S, int(n_trials), d, int(top_k), ns.ctypes.data,
+                                                    nq.ctypes.data, nr.ctypes.data, ntop.ctypes.data, sm.ctypes.data,
+                                                    vals.ctypes.data if values else None),
+                    BetweennessArgumentError)
+        out = {"node_sum": ns, "node_sumsq": nq, "node_rank_sum": nr.astype(np.int64), "node_top": ntop.astype(np.int64),
+               "total": np.ascontiguousarray(sm[..., 0]), "max": np.ascontiguousarray(sm[..., 1])}
+        if values:
+            out["values"] = vals
+        return out
+
+    def network_betweenness(self, Y, direction="directed"):
+        """The betweenness of `sample_betweenness` of networks the caller supplies (vmr_network_betweenness), by the same kernels:
+        Y [L, N, N] -> float64 [L, N], or [n, L, N, N] -> [n, L, N]; an entry > 0 is a tie, the diagonal is ignored.  The engine
+        gives the shape and the device only: no state is needed and rho is not touched.  A refused argument raises
+        `BetweennessArgumentError`."""
+        d = self._betweenness_direction(direction)
+        Ya = np.asarray(Y)
+        one = Ya.ndim == 3
+        if one:
+            Ya = Ya[None]
+        if Ya.ndim != 4 or Ya.shape[1:] != (self.L, self.N, self.N):
+            raise BetweennessArgumentError(f"Y has shape {np.shape(Y)}, the engine's networks {(self.L, self.N, self.N)}")
+        ties = np.ascontiguousarray(Ya > 0, dtype=np.uint8)
+        out = np.zeros((ties.shape[0], self.L, self.N), np.float64)
+        self._check(self.lib.vmr_network_betweenness(self._h, ties.ctypes.data, ties.shape[0], d, out.ctypes.data), BetweennessArgumentError)
+        return out[0] if one else out
 
     def _mixing_args(self, groups, C):
         """(codes int32 [N] or None, C) for the mixing calls: C None is the largest code + 1."""

@@ -843,6 +843,28 @@ class VimureModel(TransformerMixin, BaseEstimator):
         return CentralityStats(self.N, counts, np.broadcast_to(np.asarray(q, dtype=np.float64), (self.L,)).copy(), T, direction=direction,
                                top_k=top_k, plug_in=plug_in, seed=seed, n_trials=n_trials)
 
+    def posterior_betweenness(self, direction="directed", n_samples=100, seed=None, n_trials=1, top_k=10, values=False, X=None, R=None):
+        """Who brokers, and how sure is the posterior of it?  Betweenness centrality of every node -- the share of the shortest
+        paths between the others that pass through it, unnormalised, `networkx.betweenness_centrality(normalized=False)` -- over
+        the posterior of the network, computed on the GPU (vmr_sample_betweenness): n_samples draws of Y from q(Y) -- sample s is
+        `sample_inferred_model(N=n_trials, seed=seed + s, device=True)[0]` -- and per draw and layer Brandes' algorithm on A =
+        (Y > 0) without self-loops (direction "directed") or on A | A.T ("union"); reduced where rho lives to every node's sum and
+        sum of squares of b, the sum of its ranks and how often it is among the top_k, and each draw's total and maximum; only
+        those cross PCIe (values=True: also every draw's b).  Returns a `betweenness.BetweennessStats`: mean, sd, expected_rank,
+        top_prob, the betweenness of the point estimate `get_inferred_model()` (`inferred`, by the same kernels), `normalized()`,
+        `top()`, `frame()` and `summary()`.  At most 2048 nodes.  seed None: the fit's.  Engine as in `calculate_mean_poisson`."""
+        from .betweenness import BetweennessStats
+        if seed is None:
+            seed = self.seed
+        eng, tmp = self._ppc_engine(X, R)
+        try:
+            counts = eng.sample_betweenness(seed, n_samples, direction=direction, top_k=top_k, n_trials=n_trials, values=bool(values))
+            inferred = eng.network_betweenness(self.get_inferred_model(), direction=direction)
+        finally:
+            if tmp:
+                eng.close()
+        return BetweennessStats(self.N, counts, direction=direction, top_k=top_k, inferred=inferred, seed=seed, n_trials=n_trials)
+
     def posterior_predictive_check(self, n_rep=100, seed=None, params="draw", n_trials=1, by_reporter=False, X=None, R=None):
         """Does data drawn from the fitted model look like the data it was fitted to?  n_rep replicated datasets are drawn on the
         GPU over the support of R and reduced there (vmr_ppc_replicates; no replicate is written) to the integers of
