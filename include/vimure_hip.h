@@ -485,6 +485,57 @@ int vmr_sample_betweenness(vmr_handle h, uint64_t seed, int n_samples, int n_tri
  * a single network whose temporaries do not fit.  Synchronises. */
 int vmr_network_betweenness(vmr_handle h, const uint8_t* Y, int n, int direction, double* values);
 
+/* The k-core decomposition of n_samples posterior samples of Y, computed where rho lives -- what a user otherwise gets from
+ * `networkx.core_number` on every `sample_inferred_model` draw.  Sample s is exactly what vmr_sample(h, seed + s, n_trials, ..)
+ * writes (seed + s mod 2^64).  Per sample and layer: A_ij = (Y_ij > 0) with the DIAGONAL CLEARED.  The k-core is the largest node
+ * set in which every node has degree >= k, counted inside the set; core(v) is the largest k whose core holds v, the degeneracy is
+ * max_v core(v) and the main core the nodes that attain it.  The degree is chosen by mode:
+ *   VMR_CORE_UNION   the distinct neighbours in A | A^T          (`networkx.core_number(G.to_undirected())`)
+ *   VMR_CORE_TOTAL   in-degree plus out-degree in A: a reciprocated pair counts 2   (`networkx.core_number` of a DiGraph)
+ *   VMR_CORE_IN      the in-degree, VMR_CORE_OUT the out-degree
+ * core(v) <= N - 1, and <= 2 (N - 1) for TOTAL: an exact integer, no floating point enters the search.
+ * rank[v] = #{u : core[u] > core[v]}: 0 is the innermost shell, and a WHOLE SHELL SHARES A RANK -- every node of the main core
+ * has rank 0, so node_top can count more than top_k nodes per sample (all N of them on a regular graph).
+ * k_min in [0, 2 (N - 1)]; top_k in [1, N].  Host outputs:
+ *   node_sum, node_sumsq   sum_s core and sum_s core^2, in ascending s (integers below 2^53: exact)   double [L][N]
+ *   node_rank_sum          sum_s rank                                                                uint64 [L][N]
+ *   node_top               #{s : rank < top_k}                                                       uint32 [L][N]
+ *   node_main              #{s : core = the sample's degeneracy in that layer}                       uint32 [L][N]
+ *   node_atleast           #{s : core >= k_min}                                                      uint32 [L][N]
+ *   summary                (degeneracy, main-core size, sum_v core(v), #{v : core(v) >= k_min})      uint32 [n_samples][L][4]
+ *   values                 the coreness of every sample                                              uint16 [n_samples][L][N]
+ * node_sum may not be NULL, every other output may be.
+ * The samples are packed into the bit rows of vmr_sample_triads; one workgroup per (layer, sample) keeps every node's remaining
+ * degree and the row of alive nodes in LDS (12.4 KiB whatever N) and peels in rounds: the alive nodes of degree <= k get core = k
+ * and leave together, their rows are read once and their alive neighbours lose a degree each (integer LDS atomics); when nobody
+ * can leave, k jumps to the smallest remaining degree.  At most 2 N rounds by construction.  That working set bounds N: N <=
+ * VMR_CORE_NMAX = 2048; a larger N is refused with VMR_EINVAL and a message that names the bound.  Integer adds commute and the
+ * samples are folded in ascending s: every output is bit-identical from run to run and for any chunking.  Reads the CURRENT rho
+ * (after vmr_restore: the snapshot's) once per chunk of samples; any K, any n_trials >= 1, both data formats.  A chunk (L N^2 +
+ * 16 L N ceil(N/64) + 14 L N + 16 L bytes per sample, whichever outputs are asked for, beside 36 L N bytes of per-node
+ * accumulators per call; half of the free device memory at most, 256 samples at most, VMR_NETSTATS_CHUNK at most) is freed before
+ * return; a single sample that does not fit is refused with VMR_EINVAL.
+ * VMR_EINVAL, with a message that names the call and the argument, whatever the state of the handle: n_samples < 1, n_trials < 1,
+ * N above the bound, mode outside 0..3, k_min or top_k out of range, node_sum NULL.  Before vmr_set_state: VMR_ESTATE.
+ * Synchronises. */
+#define VMR_CORE_UNION 0
+#define VMR_CORE_TOTAL 1
+#define VMR_CORE_IN 2
+#define VMR_CORE_OUT 3
+#define VMR_CORE_NMAX 2048   /* nodes at most */
+int vmr_sample_cores(vmr_handle h, uint64_t seed, int n_samples, int n_trials, int mode, int k_min, int top_k, double* node_sum,
+                     double* node_sumsq, uint64_t* node_rank_sum, uint32_t* node_top, uint32_t* node_main, uint32_t* node_atleast,
+                     uint32_t* summary, uint16_t* values);
+
+/* The same coreness, by the same packing and the same kernel, of n networks the caller supplies -- the inferred network, a ground
+ * truth, a designed graph.  Y: HOST uint8 [n][L][N][N]; an entry > 0 is a tie, the diagonal is ignored.  values: host uint16
+ * [n][L][N]; summary: host uint32 [n][L][4] as above, or NULL.  The handle gives N, L, the device and the stream and nothing
+ * else: the call works before vmr_set_state and does not touch rho.  Network q of a call equals what vmr_sample_cores returns in
+ * `values` for a sample with the same ties.  The networks are uploaded in chunks (L N^2 + 16 L N ceil(N/64) + 2 L N + 16 L bytes
+ * per network).  VMR_EINVAL, with a message that names the call and the argument: n < 1, N above VMR_CORE_NMAX, mode outside
+ * 0..3, k_min out of range, Y or values NULL, a single network whose temporaries do not fit.  Synchronises. */
+int vmr_network_cores(vmr_handle h, const uint8_t* Y, int n, int mode, int k_min, uint16_t* values, uint32_t* summary);
+
 /* Posterior predictive checks: n_rep replicated datasets drawn from the fitted model over the support of the handle's own R and
  * reduced where they are drawn -- no replicate is ever written -- and the same reduction of the observed data.
  * Replicate r: Y_r is exactly what vmr_sample(h, seed_y + r, n_trials, ..) writes (mod 2^64; the CURRENT rho, after vmr_restore

@@ -24,6 +24,8 @@ CENT_NMAX, CENT_TMAX = 2048, 64
 CENT_DIRECTIONS = ("out", "in", "union")   # VMR_CENT_OUT, VMR_CENT_IN, VMR_CENT_UNION
 BTW_NMAX = 2048
 BTW_DIRECTIONS = ("directed", "union")     # VMR_BTW_DIRECTED, VMR_BTW_UNION
+CORE_NMAX = 2048
+CORE_MODES = ("union", "total", "in", "out")   # VMR_CORE_UNION, VMR_CORE_TOTAL, VMR_CORE_IN, VMR_CORE_OUT
 EDGE_REPORTED, EDGE_INFERRED = 1, 2
 SCORE_RHO1, SCORE_PROB = 0, 1
 SCORE_NCONF, SCORE_NSUM, SCORE_MAX_THR = 5, 4, 4096
@@ -85,6 +87,8 @@ SIGNATURES = {
     "vmr_mean_centrality": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "vmr_sample_betweenness": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6),
     "vmr_network_betweenness": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "vmr_sample_cores": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 8),
+    "vmr_network_cores": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vmr_ppc_replicates": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
     "vmr_ppc_observed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

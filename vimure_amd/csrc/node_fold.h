@@ -1,4 +1,4 @@
-// node_fold.h -- what the units that return a per-node value of every posterior sample share (centrality.hip, betweenness.hip), on
+// node_fold.h -- what the units that return a per-node value of every posterior sample share (centrality.hip, betweenness.hip, cores.hip), on
 // top of sampled_side.h: the wave's maximum and the fold of a chunk's values and ranks into the call's per-node accumulators.
 // Everything here is static or inline.
 #ifndef VMR_NODE_FOLD_H

@@ -1,5 +1,5 @@
 // sampled_side.h -- what the units that reduce posterior samples of Y share (netstats.hip, triads.hip, mixing.hip, connectivity.hip,
-// centrality.hip, betweenness.hip and the replicates of ppc_rep.hip), on top of read_side.h: the entry checks, the chunk rule, the chunk loop, and on the device the transposed tile.
+// centrality.hip, betweenness.hip, cores.hip and the replicates of ppc_rep.hip), on top of read_side.h: the entry checks, the chunk rule, the chunk loop, and on the device the transposed tile.
 // Everything here is static or inline.
 //
 // Sampling in chunks.  Sample s of a call is what vmr_sample(h, seed + s, n_trials) writes (seed + s mod 2^64).  ns_draw_chunk

@@ -76,6 +76,12 @@ class BetweennessArgumentError(EngineError, ValueError):
     working set holds (`_lib.BTW_NMAX`), temporaries that do not fit in the free device memory."""
 
 
+class CoresArgumentError(EngineError, ValueError):
+    """An argument `sample_cores` / `network_cores` refuse (VMR_EINVAL): a mode other than union, total, in or out, k_min outside
+    [0, 2 (N - 1)], top_k outside [1, N], n_samples or n_trials below 1, networks of another shape than the handle's, more nodes
+    than the peel's working set holds (`_lib.CORE_NMAX`), temporaries that do not fit in the free device memory."""
+
+
 SCORE_OUTPUTS = ("hist", "conf", "sums", "auc", "auc_pairs")
 INF_SELECT = {"none": 0, "lost": _lib.INF_LOST, "gained": _lib.INF_GAINED, "both": _lib.INF_LOST | _lib.INF_GAINED}
 # columns of the table of `CaviEngine.reporter_influence`, in the order of vmr_reporter_influence's row pointers
@@ -620,6 +626,70 @@ class CaviEngine:
         out = np.zeros((ties.shape[0], self.L, self.N), np.float64)
         self._check(self.lib.vmr_network_betweenness(self._h, ties.ctypes.data, ties.shape[0], d, out.ctypes.data), BetweennessArgumentError)
         return out[0] if one else out
+
+    @staticmethod
+    def _cores_mode(mode):
+        """The mode's code for the k-core calls; a name that is none is refused here."""
+        if isinstance(mode, str):
+            if mode not in _lib.CORE_MODES:
+                raise CoresArgumentError(f"mode must be one of {_lib.CORE_MODES}, got {mode!r}")
+            return _lib.CORE_MODES.index(mode)
+        return int(mode)
+
+    def sample_cores(self, seed, n_samples, mode="union", k_min=0, top_k=10, n_trials=1, values=False):
+        """The k-core decomposition of n_samples posterior samples, computed on the device (vmr_sample_cores): sample s is
+        `self.sample(seed + s, n_trials)`, A = (Y > 0) with the diagonal cleared, core[v] the largest k such that v lies in a node
+        set whose every node has degree >= k inside the set; the degree is the distinct neighbours in A | A.T ("union":
+        `networkx.core_number` of the undirected graph), in-degree plus out-degree ("total": `networkx.core_number` of the
+        DiGraph), the in-degree ("in") or the out-degree ("out").  rank[v] = #{u : core[u] > core[v]}: a whole shell shares a
+        rank, the main core has rank 0.  Returns a dict: `node_sum`, `node_sumsq` float64 [L, N] (sum_s core, sum_s core^2, exact
+        integers), `node_rank_sum`, `node_top` (#{s : rank < top_k}), `node_main` (#{s : core = the sample's degeneracy}),
+        `node_atleast` (#{s : core >= k_min}) int64 [L, N], and `degeneracy`, `main_core_size`, `core_sum`, `kcore_size` int64
+        [S, L] (max_v core, the nodes that attain it, sum_v core, #{v : core >= k_min}); with values=True also `values` uint16
+        [S, L, N].  Every number is the same from run to run and for any chunking.  N is at most `_lib.CORE_NMAX`.  A refused
+        argument raises `CoresArgumentError`."""
+        S = int(n_samples)
+        md = self._cores_mode(mode)
+        LN = (self.L, self.N)
+        ns, nq = np.zeros(LN, np.float64), np.zeros(LN, np.float64)
+        nr = np.zeros(LN, np.uint64)
+        ntop, nmain, nat = np.zeros(LN, np.uint32), np.zeros(LN, np.uint32), np.zeros(LN, np.uint32)
+        sm = np.zeros((max(S, 0), self.L, 4), np.uint32)
+        vals = np.zeros((max(S, 0),) + LN, np.uint16) if values else None
+        self._check(self.lib.vmr_sample_cores(self._h, int(seed) & (2 ** 64 - 1), S, int(n_trials), md, int(k_min), int(top_k), ns.ctypes.data,
+                                              nq.ctypes.data, nr.ctypes.data, ntop.ctypes.data, nmain.ctypes.data, nat.ctypes.data,
+                                              sm.ctypes.data, vals.ctypes.data if values else None),
+                    CoresArgumentError)
+        out = {"node_sum": ns, "node_sumsq": nq, "node_rank_sum": nr.astype(np.int64), "node_top": ntop.astype(np.int64),
+               "node_main": nmain.astype(np.int64), "node_atleast": nat.astype(np.int64)}
+        for q, name in enumerate(("degeneracy", "main_core_size", "core_sum", "kcore_size")):
+            out[name] = sm[..., q].astype(np.int64)
+        if values:
+            out["values"] = vals
+        return out
+
+    def network_cores(self, Y, mode="union", k_min=0, summary=False):
+        """The coreness of `sample_cores` of networks the caller supplies (vmr_network_cores), by the same kernel: Y [L, N, N] ->
+        uint16 [L, N], or [n, L, N, N] -> [n, L, N]; an entry > 0 is a tie, the diagonal is ignored.  summary=True: returns
+        (values, dict of `degeneracy`, `main_core_size`, `core_sum`, `kcore_size`, int64 [L] or [n, L]).  The engine gives the
+        shape and the device only: no state is needed and rho is not touched.  A refused argument raises `CoresArgumentError`."""
+        md = self._cores_mode(mode)
+        Ya = np.asarray(Y)
+        one = Ya.ndim == 3
+        if one:
+            Ya = Ya[None]
+        if Ya.ndim != 4 or Ya.shape[1:] != (self.L, self.N, self.N):
+            raise CoresArgumentError(f"Y has shape {np.shape(Y)}, the engine's networks {(self.L, self.N, self.N)}")
+        ties = np.ascontiguousarray(Ya > 0, dtype=np.uint8)
+        out = np.zeros((ties.shape[0], self.L, self.N), np.uint16)
+        sm = np.zeros((ties.shape[0], self.L, 4), np.uint32) if summary else None
+        self._check(self.lib.vmr_network_cores(self._h, ties.ctypes.data, ties.shape[0], md, int(k_min), out.ctypes.data,
+                                               sm.ctypes.data if summary else None), CoresArgumentError)
+        if not summary:
+            return out[0] if one else out
+        smd = {name: (sm[0, :, q] if one else sm[..., q]).astype(np.int64)
+               for q, name in enumerate(("degeneracy", "main_core_size", "core_sum", "kcore_size"))}
+        return (out[0] if one else out), smd
 
     def _mixing_args(self, groups, C):
         """(codes int32 [N] or None, C) for the mixing calls: C None is the largest code + 1."""

@@ -865,6 +865,36 @@ class VimureModel(TransformerMixin, BaseEstimator):
                 eng.close()
         return BetweennessStats(self.N, counts, direction=direction, top_k=top_k, inferred=inferred, seed=seed, n_trials=n_trials)
 
+    def posterior_cores(self, mode="union", k=None, n_samples=100, seed=None, n_trials=1, top_k=10, values=False, X=None, R=None):
+        """Where is the dense core of the network, who sits in it and who is periphery -- and how sure is the posterior of it?
+        The k-core decomposition (`networkx.core_number`) over the posterior of the network, computed on the GPU
+        (vmr_sample_cores): n_samples draws of Y from q(Y) -- sample s is `sample_inferred_model(N=n_trials, seed=seed + s,
+        device=True)[0]` -- and per draw and layer the coreness of every node on A = (Y > 0) without self-loops: the largest k
+        such that the node lies in a set whose every node has degree >= k inside the set.  mode: "union" (distinct neighbours in
+        A | A.T: the undirected graph), "total" (in plus out: a reciprocated pair counts 2, networkx on the DiGraph), "in" or
+        "out".  Reduced where rho lives to every node's sum and sum of squares of the coreness, the sum of its ranks, how often it
+        is among the top_k, in the main core and in the k-core, and each draw's degeneracy, main-core size and k-core size; only
+        those cross PCIe (values=True: also every draw's coreness).
+        k: the core whose membership is counted (`kcore_prob`, `kcore_size`, `core_members()`).  k None takes the degeneracy of
+        the point estimate `get_inferred_model()` -- ONE number for all layers, the smallest over the layers, so that the k-core of
+        the point estimate is not empty in any layer; pass a k to choose another.
+        Returns a `cores.CoreStats`: mean, sd, expected_rank, top_prob, main_core_prob, kcore_prob, the coreness of the point
+        estimate (`inferred`, by the same kernel), `top()`, `core_members()`, `frame()` and `summary()`.  At most 2048 nodes.
+        seed None: the fit's.  Engine as in `calculate_mean_poisson`."""
+        from .cores import CoreStats
+        if seed is None:
+            seed = self.seed
+        eng, tmp = self._ppc_engine(X, R)
+        try:
+            inferred = eng.network_cores(self.get_inferred_model(), mode=mode)
+            if k is None:
+                k = int(inferred.max(axis=1).min())
+            counts = eng.sample_cores(seed, n_samples, mode=mode, k_min=k, top_k=top_k, n_trials=n_trials, values=bool(values))
+        finally:
+            if tmp:
+                eng.close()
+        return CoreStats(self.N, counts, mode=mode, k_min=k, top_k=top_k, inferred=inferred, seed=seed, n_trials=n_trials)
+
     def posterior_predictive_check(self, n_rep=100, seed=None, params="draw", n_trials=1, by_reporter=False, X=None, R=None):
         """Does data drawn from the fitted model look like the data it was fitted to?  n_rep replicated datasets are drawn on the
         GPU over the support of R and reduced there (vmr_ppc_replicates; no replicate is written) to the integers of
