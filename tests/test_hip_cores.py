@@ -179,6 +179,51 @@ def test_medium_case_chunks_and_reruns(monkeypatch):
         _assert_equal_cores(again[m], one[m])
 
 
+def test_networks_across_chunk_boundaries(monkeypatch):
+    """The upload loop `network_betweenness` and `network_cores` share, on a handle with no state: L = 2, N = 65 (two words per
+    bit row), seven random networks with diagonal entries, in one chunk and in chunks of 3 + 3 + 1 on a fresh handle (the switch is
+    read once per handle).  Every array is the same bytes in both runs; the coreness and its summary equal the restatement, the
+    betweenness is held to its restatement by the bound tests/test_hip_betweenness.py derives (the blocks' sums associate
+    differently from NumPy's)."""
+    from tests.betweenness_util import DIRECTIONS, betweenness_np
+    from tests.test_hip_betweenness import _assert_values
+    L, N, n = 2, 65, 7
+    rng = np.random.RandomState(65)
+    Y = (rng.random_sample((n, L, N, N)) < 3.0 / N).astype(np.uint8) * rng.randint(1, 4, (n, L, N, N)).astype(np.uint8)
+    Y[:, :, np.arange(0, N, 3), np.arange(0, N, 3)] = 1
+    Y[:, :, N - 1, 0], Y[:, :, 1, N - 1] = 1, 2
+    assert Y[..., N - 1].any(axis=-1).all() and Y[..., N - 1, :].any(axis=-1).all()      # the second word's node has ties both ways
+
+    def run():
+        eng = _stateless(L, N)
+        try:
+            out = {("btw", d): eng.network_betweenness(Y, direction=d) for d in DIRECTIONS}
+            for m in MODES:
+                vals, sm = eng.network_cores(Y, mode=m, k_min=2, summary=True)
+                out[("cores", m)] = vals
+                out.update({("cores", m, k): sm[k] for k in SUMMARY})
+            return out
+        finally:
+            eng.close()
+
+    monkeypatch.delenv("VMR_NETSTATS_CHUNK", raising=False)
+    one = run()
+    monkeypatch.setenv("VMR_NETSTATS_CHUNK", "3")
+    many = run()
+    assert len(one) == len(many) == 2 + 4 * 5
+    for k in one:
+        assert one[k].dtype == many[k].dtype and one[k].shape == many[k].shape and one[k].tobytes() == many[k].tobytes(), k
+    for d in DIRECTIONS:
+        assert one[("btw", d)].shape == (n, L, N) and one[("btw", d)].dtype == np.float64
+        assert (one[("btw", d)] > 0).any(axis=-1).all()
+        _assert_values(one[("btw", d)], betweenness_np(Y, d)["values"], N, "chunked networks " + d)
+    for m in MODES:
+        want = cores_np(Y, m, 2, 1)
+        assert one[("cores", m)].dtype == np.uint16 and np.array_equal(one[("cores", m)], want["values"]), m
+        for k in SUMMARY:
+            assert one[("cores", m, k)].dtype == np.int64 and np.array_equal(one[("cores", m, k)], want[k]), (m, k)
+
+
 def test_the_node_bound():
     """N = CORE_NMAX: one network, 3 ties per node and a planted 64-clique that holds node N - 1 -- 32 words per bit row, threads
     own eight nodes -- against the restatement, every mode."""

@@ -4,6 +4,7 @@
 import numpy as np
 
 from .netstats import _ratio
+from .node_scores import quantile_row
 
 CONN_KEYS = ("components_w", "giant_w", "pairs_w", "isolates", "components_s", "giant_s", "pairs_s", "reach_pairs", "dist_sum",
              "diameter")
@@ -82,15 +83,6 @@ class ConnectivityStats:
             del out["global_efficiency"]
         return out
 
-    @staticmethod
-    def _row(v, q):
-        v = np.asarray(v, dtype=np.float64)
-        v = v[~np.isnan(v)]
-        row = {"mean": v.mean() if v.size else np.nan, "std": v.std() if v.size else np.nan}
-        qs = np.quantile(v, q) if v.size else np.full(len(q), np.nan)
-        row.update({"q%g" % x: float(y) for x, y in zip(q, qs)})
-        return row
-
     def summary(self, q=(0.025, 0.5, 0.975)):
         """DataFrame with one row per (layer, statistic): mean, std (population) and the quantiles q over the samples (NaN
         samples left out)."""
@@ -100,7 +92,7 @@ class ConnectivityStats:
         for l in range(self.L):
             for name, arr in self.statistics().items():
                 row = {"layer": l, "statistic": name}
-                row.update(self._row(arr[:, l], q))
+                row.update(quantile_row(arr[:, l], q))
                 rows.append(row)
         return pd.DataFrame(rows, columns=["layer", "statistic", "mean", "std"] + ["q%g" % x for x in q])
 
@@ -117,6 +109,6 @@ class ConnectivityStats:
             used = np.nonzero(self.dist_hist[:, l].any(axis=0))[0]
             for b in range(int(used.max()) + 1 if used.size else 0):
                 row = {"layer": l, "distance": b + 1}
-                row.update(self._row(self.dist_hist[:, l, b], q))
+                row.update(quantile_row(self.dist_hist[:, l, b], q))
                 rows.append(row)
         return pd.DataFrame(rows, columns=["layer", "distance", "mean", "std"] + ["q%g" % x for x in q])

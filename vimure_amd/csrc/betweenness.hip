@@ -8,9 +8,8 @@
 // one level down of sigma[w] / sigma[v] (1 + delta[v]); b(v) = sum_s delta_s[v].
 //
 // vmr_sample_betweenness draws S posterior samples of Y in chunks (sampled_side.h: sample s is what vmr_sample(h, seed + s,
-// n_trials) writes) and packs them into the bit rows of triads.hip (tri_pack_chunk: Aout[c][L][N][W], Ain[c][L][N][W], W =
-// ceil(N / 64) words per row, diagonal cleared, pad bits zero); vmr_network_betweenness uploads the caller's networks in chunks
-// and packs them the same way.
+// n_trials) writes) and packs them into bit rows (sampled_side.h has the layout); vmr_network_betweenness uploads the caller's
+// networks in chunks and packs them the same way.
 // k_btw_brandes: one workgroup (4 waves) per (block of BTW_SB = 16 consecutive sources, layer, sample): the block depends on N
 // only, never on the device or the chunk.  Per source, in LDS: sigma and delta (FP64, N each), d (16-bit, over the 64 W padded
 // nodes) and one bit row `nx`, and 64 slots of 16 bits per node a thread owns for the waves' node lists: 16 N + 136 W + 512 KPT
@@ -279,47 +278,34 @@ int btw_args(vmr_ctx* h, const char* fn, int direction) {
   return VMR_OK;
 }
 
-// the shape of both calls' kernels on a handle
-struct BtwShape {
-  int W, lG, nblk, kpt;
-  size_t smem, LN, ties, bits_b, part_b;   // bytes per sample: Y, one set of bit rows, the blocks' shares
+// the shape of both calls' kernels on a handle: the bit rows' and what is this unit's
+struct BtwShape : BitRows {
+  int nblk, kpt;
+  size_t smem, part_b;   // part_b: bytes per sample of the blocks' shares
 };
 BtwShape btw_shape(const Geo& g) {
   BtwShape b;
-  b.W = (g.N + 63) / 64;
-  b.lG = 0;   // lanes per row: the largest power of two <= min(W, 64)
-  while ((2 << b.lG) <= b.W && b.lG < 6) ++b.lG;
+  static_cast<BitRows&>(b) = bit_rows(g);
   b.nblk = (g.N + BTW_SB - 1) / BTW_SB;
   b.kpt = (g.N + BTW_TPB - 1) / BTW_TPB;   // nodes a thread owns: 1 .. BTW_KPT
   b.smem = (size_t)g.N * 16 + (size_t)b.W * (8 + 64 * 2);
-  b.LN = (size_t)g.L * g.N;
-  b.ties = b.LN * g.N;
-  b.bits_b = b.LN * b.W * 8;
   b.part_b = b.LN * b.nblk * 8;
   return b;
-}
-
-template <bool UNION, int KPT>
-void btw_launch(vmr_ctx* h, const BtwShape& b, int nsl, const u64* Ao, const u64* Ai, double* part) {
-  const unsigned grid = 8u * (unsigned)b.nblk * (unsigned)((nsl + 7) / 8);
-  hipLaunchKernelGGL((k_btw_brandes<UNION, KPT>), dim3(grid), dim3(BTW_TPB), b.smem, h->stream, Ao, Ai, h->g.N, b.W, b.lG, b.nblk, nsl, part);
 }
 
 // the packed chunk of c samples (or networks) -> cval[c][L][N], and crank, summary unless null
 int btw_chunk(vmr_ctx* h, const BtwShape& b, int c, int direction, const u64* Ao, const u64* Ai, double* part, double* cval, unsigned* crank,
               double* summary) {
   const int nsl = c * h->g.L;
-  if (direction == VMR_BTW_UNION) {
-    if (b.kpt <= 1) btw_launch<true, 1>(h, b, nsl, Ao, Ai, part);
-    else if (b.kpt <= 2) btw_launch<true, 2>(h, b, nsl, Ao, Ai, part);
-    else if (b.kpt <= 4) btw_launch<true, 4>(h, b, nsl, Ao, Ai, part);
-    else btw_launch<true, 8>(h, b, nsl, Ao, Ai, part);
-  } else {
-    if (b.kpt <= 1) btw_launch<false, 1>(h, b, nsl, Ao, Ai, part);
-    else if (b.kpt <= 2) btw_launch<false, 2>(h, b, nsl, Ao, Ai, part);
-    else if (b.kpt <= 4) btw_launch<false, 4>(h, b, nsl, Ao, Ai, part);
-    else btw_launch<false, 8>(h, b, nsl, Ao, Ai, part);
-  }
+  const unsigned grid = 8u * (unsigned)b.nblk * (unsigned)((nsl + 7) / 8);
+  auto launch = [&](auto U, auto K) {
+    hipLaunchKernelGGL((k_btw_brandes<decltype(U)::value, decltype(K)::value>), dim3(grid), dim3(BTW_TPB), b.smem, h->stream, Ao, Ai, h->g.N, b.W, b.lG,
+                       b.nblk, nsl, part);
+  };
+  with_kpt(b.kpt, [&](auto K) {
+    if (direction == VMR_BTW_UNION) launch(std::true_type{}, K);
+    else launch(std::false_type{}, K);
+  });
   HIPCHK(h, hipGetLastError());
   hipLaunchKernelGGL(k_btw_fold_blocks, dim3((unsigned)nsl), dim3(BTW_TPB), 0, h->stream, part, h->g.N, b.nblk, direction == VMR_BTW_UNION, cval, crank,
                      summary);
@@ -336,58 +322,36 @@ extern "C" int vmr_sample_betweenness(vmr_handle h, uint64_t seed, int n_samples
   int rc;
   if ((rc = sampled_counts(h, fn, n_samples, n_trials))) return rc;
   if ((rc = btw_args(h, fn, direction))) return rc;
-  const Geo& g = h->g;
-  if (top_k < 1 || top_k > g.N) {
-    char msg[256];
-    snprintf(msg, sizeof msg, "%s: top_k must be in [1, N = %d], got %d", fn, g.N, top_k);
-    return fail(h, VMR_EINVAL, msg);
-  }
-  if (!node_sum) return fail(h, VMR_EINVAL, "vmr_sample_betweenness: node_sum is NULL");
+  if ((rc = node_fold_args(h, fn, top_k, node_sum))) return rc;
   if ((rc = expected_begin(h, fn))) return rc;
+  const Geo& g = h->g;
   const BtwShape b = btw_shape(g);
   const size_t LN = b.LN;
   SampledOut out[1] = {{summary, (size_t)g.L * 16, false, "vmr_sample_betweenness: the summary", nullptr}};
-  // device bytes per sample of a chunk: Y, the bit rows, the blocks' shares, b and the ranks, the summary; per call: the accumulators
-  const size_t per = b.ties + 2 * b.bits_b + b.part_b + LN * 12 + (summary ? out[0].bytes : 0);
+  // device bytes per sample of a chunk: the bit-row chunk, the blocks' shares, b and the ranks, the summary; per call: the accumulators
+  const size_t per = b.per() + b.part_b + LN * 12 + (summary ? out[0].bytes : 0);
   size_t C;
-  if ((rc = chunk_samples(h, fn, (size_t)n_samples, per, LN * 28, &C))) return rc;
+  if ((rc = chunk_samples(h, fn, (size_t)n_samples, per, NodeFold::bytes(LN), &C))) return rc;
   Tmp tm(h);
   uint8_t* Y = nullptr;
-  u64 *Ao = nullptr, *Ai = nullptr, *arank = nullptr;
-  double *part = nullptr, *cval = nullptr, *asum = nullptr, *asq = nullptr;
-  unsigned *crank = nullptr, *atop = nullptr;
-  if ((rc = tm.get(&Y, C * b.ties, "vmr_sample_betweenness: the samples")) ||
-      (rc = tm.get(&Ao, C * b.bits_b, "vmr_sample_betweenness: the out-neighbour bits")) ||
-      (rc = tm.get(&Ai, C * b.bits_b, "vmr_sample_betweenness: the in-neighbour bits")) ||
+  u64 *Ao = nullptr, *Ai = nullptr;
+  double *part = nullptr, *cval = nullptr;
+  unsigned* crank = nullptr;
+  NodeFold fold;
+  if ((rc = bit_rows_get(tm, b, C, fn, "samples", &Y, &Ao, &Ai)) ||
       (rc = tm.get(&part, C * b.part_b, "vmr_sample_betweenness: the source blocks' shares")) ||
       (rc = tm.get(&cval, C * LN * 8, "vmr_sample_betweenness: the values")) ||
-      (rc = tm.get(&crank, C * LN * 4, "vmr_sample_betweenness: the ranks")) ||
-      (rc = tm.get(&asum, LN * 8, "vmr_sample_betweenness: the node sums")) ||
-      (rc = tm.get(&asq, LN * 8, "vmr_sample_betweenness: the node sums of squares")) ||
-      (rc = tm.get(&arank, LN * 8, "vmr_sample_betweenness: the node rank sums")) ||
-      (rc = tm.get(&atop, LN * 4, "vmr_sample_betweenness: the node top counts")))
+      (rc = tm.get(&crank, C * LN * 4, "vmr_sample_betweenness: the ranks")) || (rc = fold.begin(h, tm, fn, LN, top_k)))
     return rc;
-  HIPCHK(h, hipMemsetAsync(asum, 0, LN * 8, h->stream));
-  HIPCHK(h, hipMemsetAsync(asq, 0, LN * 8, h->stream));
-  HIPCHK(h, hipMemsetAsync(arank, 0, LN * 8, h->stream));
-  HIPCHK(h, hipMemsetAsync(atop, 0, LN * 4, h->stream));
   rc = sampled_chunks(h, tm, (size_t)n_samples, C, seed, n_trials, Y, out, [&](size_t s0, int c) -> int {
     int rc2;
     if ((rc2 = tri_pack_chunk(h, Y, c, Ao, Ai))) return rc2;
     if ((rc2 = btw_chunk(h, b, c, direction, Ao, Ai, part, cval, crank, out[0].as<double>()))) return rc2;
-    hipLaunchKernelGGL(k_node_fold, dim3(grid_for(LN, 256, 0xffffffffu)), dim3(256), 0, h->stream, cval, crank, c, LN, (unsigned)top_k, asum, asq,
-                       arank, atop);
-    HIPCHK(h, hipGetLastError());
+    if ((rc2 = fold.add(h, cval, crank, c))) return rc2;
     if (values) HIPCHK(h, hipMemcpyAsync(values + s0 * LN, cval, (size_t)c * LN * 8, hipMemcpyDeviceToHost, h->stream));
     return VMR_OK;
   });
-  if (rc) return rc;
-  HIPCHK(h, hipMemcpyAsync(node_sum, asum, LN * 8, hipMemcpyDeviceToHost, h->stream));
-  if (node_sumsq) HIPCHK(h, hipMemcpyAsync(node_sumsq, asq, LN * 8, hipMemcpyDeviceToHost, h->stream));
-  if (node_rank_sum) HIPCHK(h, hipMemcpyAsync(node_rank_sum, arank, LN * 8, hipMemcpyDeviceToHost, h->stream));
-  if (node_top) HIPCHK(h, hipMemcpyAsync(node_top, atop, LN * 4, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return VMR_OK;
+  return rc ? rc : fold.finish(h, node_sum, node_sumsq, node_rank_sum, node_top);
 }
 
 extern "C" int vmr_network_betweenness(vmr_handle h, const uint8_t* Y, int n, int direction, double* values) {
@@ -400,26 +364,21 @@ extern "C" int vmr_network_betweenness(vmr_handle h, const uint8_t* Y, int n, in
   if (!values) return fail(h, VMR_EINVAL, "vmr_network_betweenness: values is NULL");
   HIPCHK(h, hipSetDevice(h->device));
   const BtwShape b = btw_shape(h->g);
-  const size_t per = b.ties + 2 * b.bits_b + b.part_b + b.LN * 8;
+  const size_t per = b.per() + b.part_b + b.LN * 8;
   size_t C;
   if ((rc = chunk_samples(h, fn, (size_t)n, per, 0, &C, "network"))) return rc;
   Tmp tm(h);
   uint8_t* Yd = nullptr;
   u64 *Ao = nullptr, *Ai = nullptr;
   double *part = nullptr, *cval = nullptr;
-  if ((rc = tm.get(&Yd, C * b.ties, "vmr_network_betweenness: the networks")) ||
-      (rc = tm.get(&Ao, C * b.bits_b, "vmr_network_betweenness: the out-neighbour bits")) ||
-      (rc = tm.get(&Ai, C * b.bits_b, "vmr_network_betweenness: the in-neighbour bits")) ||
+  if ((rc = bit_rows_get(tm, b, C, fn, "networks", &Yd, &Ao, &Ai)) ||
       (rc = tm.get(&part, C * b.part_b, "vmr_network_betweenness: the source blocks' shares")) ||
       (rc = tm.get(&cval, C * b.LN * 8, "vmr_network_betweenness: the values")))
     return rc;
-  for (size_t s0 = 0; s0 < (size_t)n; s0 += C) {
-    const size_t c = std::min<size_t>(C, (size_t)n - s0);
-    HIPCHK(h, hipMemcpyAsync(Yd, Y + s0 * b.ties, c * b.ties, hipMemcpyHostToDevice, h->stream));
-    if ((rc = tri_pack_chunk(h, Yd, (int)c, Ao, Ai))) return rc;
-    if ((rc = btw_chunk(h, b, (int)c, direction, Ao, Ai, part, cval, nullptr, nullptr))) return rc;
-    HIPCHK(h, hipMemcpyAsync(values + s0 * b.LN, cval, c * b.LN * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-  }
-  return VMR_OK;
+  return uploaded_chunks(h, b, (size_t)n, C, Y, Yd, Ao, Ai, [&](size_t s0, int c) -> int {
+    int rc2;
+    if ((rc2 = btw_chunk(h, b, c, direction, Ao, Ai, part, cval, nullptr, nullptr))) return rc2;
+    HIPCHK(h, hipMemcpyAsync(values + s0 * b.LN, cval, (size_t)c * b.LN * 8, hipMemcpyDeviceToHost, h->stream));
+    return VMR_OK;
+  });
 }

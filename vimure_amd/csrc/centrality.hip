@@ -7,9 +7,8 @@
 // any graph; T = 1 is the degree, large T with q below 1 / lambda_1 Katz centrality.
 //
 // vmr_sample_centrality draws S posterior samples of Y in chunks (sampled_side.h: sample s is what vmr_sample(h, seed + s,
-// n_trials) writes), packs them into the bit rows of triads.hip (tri_pack_chunk: Aout[c][L][N][W], Ain[c][L][N][W], W =
-// ceil(N / 64) words per row, diagonal cleared, pad bits zero) and runs, per sample and layer, x_0 = 1, x_t = q_l (M x_{t-1}),
-// c = x_1 + .. + x_T with M = A (the rows of Aout), A^T (the rows of Ain) or A | A^T (the OR of the two words).
+// n_trials) writes), packs them into bit rows (sampled_side.h has the layout) and runs, per sample and layer, x_0 = 1, x_t = q_l
+// (M x_{t-1}), c = x_1 + .. + x_T with M = A (the rows of Aout), A^T (the rows of Ain) or A | A^T (the OR of the two words).
 // k_cent_walk: one workgroup (4 waves) per (layer, sample).  x_{t-1} and x_t ping-pong in LDS (16 N bytes: N <= VMR_CENT_NMAX =
 // 2048 is 32 KiB); thread t keeps the c of nodes t, t + 256, .. in registers (KPT of them).  A step: a wave takes 64 consecutive
 // rows at a time; G lanes (the largest power of two <= min(W, 64)) stride the W words of a row, 64 / G rows side by side, the
@@ -228,13 +227,6 @@ int cent_args(vmr_ctx* h, const char* fn, const double* q, int T, int direction)
   return VMR_OK;
 }
 
-template <int KPT>
-void cent_launch_walk(vmr_ctx* h, int c, size_t smem, const u64* Ao, const u64* Ai, int W, int lG, int dir, int T, const double* qd, double* cval,
-                      unsigned* crank, double* summary) {
-  hipLaunchKernelGGL(k_cent_walk<KPT>, dim3((unsigned)h->g.L, (unsigned)c), dim3(CENT_TPB), smem, h->stream, Ao, Ai, h->g.N, h->g.L, W, lG, dir, T, qd,
-                     cval, crank, summary);
-}
-
 }  // namespace
 
 extern "C" int vmr_sample_centrality(vmr_handle h, uint64_t seed, int n_samples, int n_trials, const double* q, int T, int direction, int top_k,
@@ -251,68 +243,44 @@ extern "C" int vmr_sample_centrality(vmr_handle h, uint64_t seed, int n_samples,
     return fail(h, VMR_EINVAL, msg);
   }
   if ((rc = cent_args(h, fn, q, T, direction))) return rc;
-  if (top_k < 1 || top_k > g.N) {
-    snprintf(msg, sizeof msg, "%s: top_k must be in [1, N = %d], got %d", fn, g.N, top_k);
-    return fail(h, VMR_EINVAL, msg);
-  }
-  if (!node_sum) return fail(h, VMR_EINVAL, "vmr_sample_centrality: node_sum is NULL");
+  if ((rc = node_fold_args(h, fn, top_k, node_sum))) return rc;
   if ((rc = expected_begin(h, fn))) return rc;
-  const int W = (g.N + 63) / 64;
-  const size_t LN = (size_t)g.L * g.N;
-  const size_t ties = LN * g.N, bits_b = LN * W * 8;
+  const BitRows b = bit_rows(g);
+  const size_t LN = b.LN;
   SampledOut out[1] = {{summary, (size_t)g.L * 16, false, "vmr_sample_centrality: the summary", nullptr}};
-  // device bytes per sample of a chunk: Y, the bit rows, c and the ranks, the summary; per call: the accumulators and q
-  const size_t per = ties + 2 * bits_b + LN * 12 + (summary ? out[0].bytes : 0);
-  const size_t fixed = LN * 28 + (size_t)g.L * 8;
+  // device bytes per sample of a chunk: the bit-row chunk, c and the ranks, the summary; per call: the accumulators and q
+  const size_t per = b.per() + LN * 12 + (summary ? out[0].bytes : 0);
+  const size_t fixed = NodeFold::bytes(LN) + (size_t)g.L * 8;
   size_t C;
   if ((rc = chunk_samples(h, fn, (size_t)n_samples, per, fixed, &C))) return rc;
   Tmp tm(h);
   uint8_t* Y = nullptr;
-  u64 *Ao = nullptr, *Ai = nullptr, *arank = nullptr;
-  double *cval = nullptr, *qd = nullptr, *asum = nullptr, *asq = nullptr;
-  unsigned *crank = nullptr, *atop = nullptr;
-  if ((rc = tm.get(&Y, C * ties, "vmr_sample_centrality: the samples")) ||
-      (rc = tm.get(&Ao, C * bits_b, "vmr_sample_centrality: the out-neighbour bits")) ||
-      (rc = tm.get(&Ai, C * bits_b, "vmr_sample_centrality: the in-neighbour bits")) ||
+  u64 *Ao = nullptr, *Ai = nullptr;
+  double *cval = nullptr, *qd = nullptr;
+  unsigned* crank = nullptr;
+  NodeFold fold;
+  if ((rc = bit_rows_get(tm, b, C, fn, "samples", &Y, &Ao, &Ai)) ||
       (rc = tm.get(&cval, C * LN * 8, "vmr_sample_centrality: the values")) ||
       (rc = tm.get(&crank, C * LN * 4, "vmr_sample_centrality: the ranks")) ||
-      (rc = tm.get(&asum, LN * 8, "vmr_sample_centrality: the node sums")) ||
-      (rc = tm.get(&asq, LN * 8, "vmr_sample_centrality: the node sums of squares")) ||
-      (rc = tm.get(&arank, LN * 8, "vmr_sample_centrality: the node rank sums")) ||
-      (rc = tm.get(&atop, LN * 4, "vmr_sample_centrality: the node top counts")) ||
       (rc = tm.get(&qd, (size_t)g.L * 8, "vmr_sample_centrality: q")))
     return rc;
   HIPCHK(h, hipMemcpyAsync(qd, q, (size_t)g.L * 8, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemsetAsync(asum, 0, LN * 8, h->stream));
-  HIPCHK(h, hipMemsetAsync(asq, 0, LN * 8, h->stream));
-  HIPCHK(h, hipMemsetAsync(arank, 0, LN * 8, h->stream));
-  HIPCHK(h, hipMemsetAsync(atop, 0, LN * 4, h->stream));
-  int lG = 0;   // lanes per row: the largest power of two <= min(W, 64)
-  while ((2 << lG) <= W && lG < 6) ++lG;
-  const size_t smem = (size_t)W * 64 * 2 * 8;
+  if ((rc = fold.begin(h, tm, fn, LN, top_k))) return rc;
+  const size_t smem = (size_t)b.W * 64 * 2 * 8;
   const int kpt = (g.N + CENT_TPB - 1) / CENT_TPB;   // nodes a thread owns: 1 .. VMR_CENT_NMAX / 256 = 8
   rc = sampled_chunks(h, tm, (size_t)n_samples, C, seed, n_trials, Y, out, [&](size_t s0, int c) -> int {
     int rc2;
     if ((rc2 = tri_pack_chunk(h, Y, c, Ao, Ai))) return rc2;
-    double* sm = out[0].as<double>();
-    if (kpt <= 1) cent_launch_walk<1>(h, c, smem, Ao, Ai, W, lG, direction, T, qd, cval, crank, sm);
-    else if (kpt <= 2) cent_launch_walk<2>(h, c, smem, Ao, Ai, W, lG, direction, T, qd, cval, crank, sm);
-    else if (kpt <= 4) cent_launch_walk<4>(h, c, smem, Ao, Ai, W, lG, direction, T, qd, cval, crank, sm);
-    else cent_launch_walk<8>(h, c, smem, Ao, Ai, W, lG, direction, T, qd, cval, crank, sm);
+    with_kpt(kpt, [&](auto K) {
+      hipLaunchKernelGGL(k_cent_walk<decltype(K)::value>, dim3((unsigned)g.L, (unsigned)c), dim3(CENT_TPB), smem, h->stream, Ao, Ai, g.N, g.L, b.W,
+                         b.lG, direction, T, qd, cval, crank, out[0].as<double>());
+    });
     HIPCHK(h, hipGetLastError());
-    hipLaunchKernelGGL(k_node_fold, dim3(grid_for(LN, 256, 0xffffffffu)), dim3(256), 0, h->stream, cval, crank, c, LN, (unsigned)top_k, asum, asq,
-                       arank, atop);
-    HIPCHK(h, hipGetLastError());
+    if ((rc2 = fold.add(h, cval, crank, c))) return rc2;
     if (values) HIPCHK(h, hipMemcpyAsync(values + s0 * LN, cval, (size_t)c * LN * 8, hipMemcpyDeviceToHost, h->stream));
     return VMR_OK;
   });
-  if (rc) return rc;
-  HIPCHK(h, hipMemcpyAsync(node_sum, asum, LN * 8, hipMemcpyDeviceToHost, h->stream));
-  if (node_sumsq) HIPCHK(h, hipMemcpyAsync(node_sumsq, asq, LN * 8, hipMemcpyDeviceToHost, h->stream));
-  if (node_rank_sum) HIPCHK(h, hipMemcpyAsync(node_rank_sum, arank, LN * 8, hipMemcpyDeviceToHost, h->stream));
-  if (node_top) HIPCHK(h, hipMemcpyAsync(node_top, atop, LN * 4, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return VMR_OK;
+  return rc ? rc : fold.finish(h, node_sum, node_sumsq, node_rank_sum, node_top);
 }
 
 extern "C" int vmr_mean_centrality(vmr_handle h, const double* q, int T, int direction, double* out) {

@@ -8,8 +8,7 @@
 // and the maximum of their distances and, per node, its component labels, how many nodes it reaches and is reached by, and the
 // sums of those distances (include/vimure_hip.h has the definitions).  Everything is an integer.
 //
-// Layout.  The chunk's samples are packed into the bit rows of triads.hip (tri_pack_chunk: Aout[c][L][N][W], Ain[c][L][N][W],
-// W = ceil(N / 64) words per row, diagonal cleared, pad bits zero).
+// Layout.  The chunk's samples are packed into bit rows (sampled_side.h has the layout).
 // k_conn_closure: one workgroup (4 waves) per (source block b of 64 nodes, layer, sample).  A closure is a breadth-first search
 // from the block's 64 sources at once: node v carries a 64-bit word seen[v] whose bit q says that source 64 b + q has reached v.
 // Three arrays of 64 W words live in LDS: seen, the frontier and the next frontier (24 N bytes: N <= VMR_CONN_NMAX = 2048 is
@@ -236,27 +235,24 @@ extern "C" int vmr_sample_connectivity(vmr_handle h, uint64_t seed, int n_sample
     return fail(h, VMR_EINVAL, msg);
   }
   if ((rc = expected_begin(h, "vmr_sample_connectivity"))) return rc;
-  const int W = (g.N + 63) / 64;
-  const size_t ties = (size_t)g.L * g.N * g.N, bits_b = (size_t)g.L * g.N * W * 8, node_b = (size_t)g.L * g.N * 4;
+  const BitRows b = bit_rows(g);
+  const int W = b.W;
+  const size_t node_b = b.LN * 4;
   SampledOut out[2] = {{counts, (size_t)g.L * VMR_CONN_NSTAT * 8, true, "vmr_sample_connectivity: the counts"},
                        {dist_hist, (size_t)g.L * VMR_CONN_NDIST * 8, true, "vmr_sample_connectivity: the distance histogram"}};
   int32_t* const node_host[6] = {node_comp_w, node_comp_s, node_reach_out, node_reach_in, node_dist_out, node_dist_in};
   const bool want_nodes = node_reach_out || node_reach_in || node_dist_out || node_dist_in;
   // device bytes per sample of a chunk: Y, the bit rows, the six node arrays (the labels are needed in any case), the outputs
-  const size_t per = ties + 2 * bits_b + 6 * node_b + out[0].bytes + (dist_hist ? out[1].bytes : 0);
+  const size_t per = b.per() + 6 * node_b + out[0].bytes + (dist_hist ? out[1].bytes : 0);
   size_t C;
   if ((rc = chunk_samples(h, "vmr_sample_connectivity", (size_t)n_samples, per, 0, &C))) return rc;
   Tmp tm(h);
   uint8_t* Y = nullptr;
   u64 *Ao = nullptr, *Ai = nullptr;
   int32_t* nodes = nullptr;
-  if ((rc = tm.get(&Y, C * ties, "vmr_sample_connectivity: the samples")) ||
-      (rc = tm.get(&Ao, C * bits_b, "vmr_sample_connectivity: the out-neighbour bits")) ||
-      (rc = tm.get(&Ai, C * bits_b, "vmr_sample_connectivity: the in-neighbour bits")) ||
+  if ((rc = bit_rows_get(tm, b, C, "vmr_sample_connectivity", "samples", &Y, &Ao, &Ai)) ||
       (rc = tm.get(&nodes, 6 * C * node_b, "vmr_sample_connectivity: the node arrays")))
     return rc;
-  int lG = 0;   // lanes per frontier node: the largest power of two <= min(W, 64)
-  while ((2 << lG) <= W && lG < 6) ++lG;
   const size_t smem = (size_t)W * 64 * 3 * 8;
   const size_t plane = C * (size_t)g.L * g.N;   // elements of one node array of a chunk
   return sampled_chunks(h, tm, (size_t)n_samples, C, seed, n_trials, Y, out, [&](size_t s0, int c) -> int {
@@ -264,7 +260,7 @@ extern "C" int vmr_sample_connectivity(vmr_handle h, uint64_t seed, int n_sample
     if ((rc2 = tri_pack_chunk(h, Y, c, Ao, Ai))) return rc2;
     HIPCHK(h, hipMemsetAsync(nodes, 0x7f, 2 * plane * 4, h->stream));   // (0x7f7f7f7f: above every node index)
     if (want_nodes) HIPCHK(h, hipMemsetAsync(nodes + 2 * plane, 0, 4 * plane * 4, h->stream));
-    hipLaunchKernelGGL(k_conn_closure, dim3((unsigned)W, (unsigned)g.L, (unsigned)c), dim3(CONN_TPB), smem, h->stream, Ao, Ai, g.N, g.L, W, lG,
+    hipLaunchKernelGGL(k_conn_closure, dim3((unsigned)W, (unsigned)g.L, (unsigned)c), dim3(CONN_TPB), smem, h->stream, Ao, Ai, g.N, g.L, W, b.lG,
                        out[0].as<u64>(), out[1].as<u64>(), nodes, plane, want_nodes);
     HIPCHK(h, hipGetLastError());
     hipLaunchKernelGGL(k_conn_finish, dim3((unsigned)g.L, (unsigned)c), dim3(CONN_TPB), 0, h->stream, nodes, nodes + plane, g.N, g.L, out[0].as<u64>());

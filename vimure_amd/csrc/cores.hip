@@ -6,8 +6,8 @@
 // A | A^T, TOTAL in-degree plus out-degree, IN, OUT.
 //
 // vmr_sample_cores draws S posterior samples of Y in chunks (sampled_side.h: sample s is what vmr_sample(h, seed + s, n_trials)
-// writes) and packs them into the bit rows of triads.hip (tri_pack_chunk: Aout[c][L][N][W], Ain[c][L][N][W], W = ceil(N / 64) words
-// per row, diagonal cleared, pad bits zero); vmr_network_cores uploads the caller's networks in chunks and packs them the same way.
+// writes) and packs them into bit rows (sampled_side.h has the layout); vmr_network_cores uploads the caller's networks in chunks
+// and packs them the same way.
 // k_core_peel: one workgroup (4 waves) per (sample or network, layer).  In LDS: deg (32 bits for each of the 64 W padded nodes),
 // the bit row `alive` (W words), 64 slots of 16 bits per node a thread owns for the waves' node lists and 28 words of the rounds'
 // tallies and the summary's sums: 8192 + 256 + 4096 + 112 = 12,656 bytes whatever N, twelve workgroups' worth to a CU.  Thread t owns nodes t, t + 256,
@@ -43,22 +43,6 @@ namespace {
 #define CORE_FLY 4                             // rows whose words a lane group has in flight
 #define CORE_KPT (VMR_CORE_NMAX / CORE_TPB)    // nodes a thread owns at most
 #define CORE_NONE 0xffffffffu                  // the smallest deg of no node
-
-__device__ __forceinline__ unsigned wave_min_u(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, (unsigned)__shfl_xor((int)v, o, 64));
-  return v;
-}
-__device__ __forceinline__ unsigned wave_max_u(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, o, 64));
-  return v;
-}
-__device__ __forceinline__ unsigned wave_sum_u(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += (unsigned)__shfl_xor((int)v, o, 64);
-  return v;
-}
 
 // one LDS atomicSub per set bit of w, the bits of word ww (x < 64 W: inside deg whatever the pad bits hold)
 __device__ __forceinline__ void core_drop(u64 w, int ww, unsigned* deg) {
@@ -266,41 +250,18 @@ int core_args(vmr_ctx* h, const char* fn, int mode, int k_min) {
   return VMR_OK;
 }
 
-// the shape of both calls' kernels on a handle
-struct CoreShape {
-  int W, lG;
-  size_t LN, ties, bits_b;   // bytes per sample: Y, one set of bit rows
-};
-CoreShape core_shape(const Geo& g) {
-  CoreShape b;
-  b.W = (g.N + 63) / 64;
-  b.lG = 0;   // lanes per row: the largest power of two <= min(W, 64)
-  while ((2 << b.lG) <= b.W && b.lG < 6) ++b.lG;
-  b.LN = (size_t)g.L * g.N;
-  b.ties = b.LN * g.N;
-  b.bits_b = b.LN * b.W * 8;
-  return b;
-}
-
 // the packed chunk of c samples (or networks) -> values[c][L][N], summary[c][L][4], and cval, crank unless null
-int core_chunk(vmr_ctx* h, const CoreShape& b, int c, int mode, int k_min, const u64* Ao, const u64* Ai, unsigned short* values, double* cval,
+int core_chunk(vmr_ctx* h, const BitRows& b, int c, int mode, int k_min, const u64* Ao, const u64* Ai, unsigned short* values, double* cval,
                unsigned* crank, unsigned* summary) {
-  const dim3 grid((unsigned)(c * h->g.L)), block(CORE_TPB);
-  const int N = h->g.N;
-  const unsigned km = (unsigned)k_min;
+  auto launch = [&](auto M) {
+    hipLaunchKernelGGL(k_core_peel<decltype(M)::value>, dim3((unsigned)(c * h->g.L)), dim3(CORE_TPB), 0, h->stream, Ao, Ai, h->g.N, b.W, b.lG,
+                       (unsigned)k_min, values, cval, crank, summary);
+  };
   switch (mode) {
-    case VMR_CORE_UNION:
-      hipLaunchKernelGGL((k_core_peel<VMR_CORE_UNION>), grid, block, 0, h->stream, Ao, Ai, N, b.W, b.lG, km, values, cval, crank, summary);
-      break;
-    case VMR_CORE_TOTAL:
-      hipLaunchKernelGGL((k_core_peel<VMR_CORE_TOTAL>), grid, block, 0, h->stream, Ao, Ai, N, b.W, b.lG, km, values, cval, crank, summary);
-      break;
-    case VMR_CORE_IN:
-      hipLaunchKernelGGL((k_core_peel<VMR_CORE_IN>), grid, block, 0, h->stream, Ao, Ai, N, b.W, b.lG, km, values, cval, crank, summary);
-      break;
-    default:
-      hipLaunchKernelGGL((k_core_peel<VMR_CORE_OUT>), grid, block, 0, h->stream, Ao, Ai, N, b.W, b.lG, km, values, cval, crank, summary);
-      break;
+    case VMR_CORE_UNION: launch(std::integral_constant<int, VMR_CORE_UNION>{}); break;
+    case VMR_CORE_TOTAL: launch(std::integral_constant<int, VMR_CORE_TOTAL>{}); break;
+    case VMR_CORE_IN: launch(std::integral_constant<int, VMR_CORE_IN>{}); break;
+    default: launch(std::integral_constant<int, VMR_CORE_OUT>{}); break;
   }
   HIPCHK(h, hipGetLastError());
   return VMR_OK;
@@ -316,48 +277,35 @@ extern "C" int vmr_sample_cores(vmr_handle h, uint64_t seed, int n_samples, int 
   int rc;
   if ((rc = sampled_counts(h, fn, n_samples, n_trials))) return rc;
   if ((rc = core_args(h, fn, mode, k_min))) return rc;
-  const Geo& g = h->g;
-  if (top_k < 1 || top_k > g.N) {
-    char msg[256];
-    snprintf(msg, sizeof msg, "%s: top_k must be in [1, N = %d], got %d", fn, g.N, top_k);
-    return fail(h, VMR_EINVAL, msg);
-  }
-  if (!node_sum) return fail(h, VMR_EINVAL, "vmr_sample_cores: node_sum is NULL");
+  if ((rc = node_fold_args(h, fn, top_k, node_sum))) return rc;
   if ((rc = expected_begin(h, fn))) return rc;
-  const CoreShape b = core_shape(g);
+  const Geo& g = h->g;
+  const BitRows b = bit_rows(g);
   const size_t LN = b.LN;
   // the summary is kept on the device whether or not it is asked for: k_core_fold_counts reads the degeneracy from it
   SampledOut out[2] = {{summary, (size_t)g.L * 16, false, "vmr_sample_cores: the summary", nullptr},
                        {values, LN * 2, false, "vmr_sample_cores: the values", nullptr}};
   uint32_t* no_summary = nullptr;
   uint16_t* no_values = nullptr;
-  // device bytes per sample of a chunk: Y, the bit rows, the coreness as doubles and as 16-bit words, the ranks, the summary
-  const size_t per = b.ties + 2 * b.bits_b + LN * 14 + (size_t)g.L * 16;
+  // device bytes per sample of a chunk: the bit-row chunk, the coreness as doubles and as 16-bit words, the ranks, the summary;
+  // per call: the accumulators and this unit's two counters
+  const size_t per = b.per() + LN * 14 + (size_t)g.L * 16;
   size_t C;
-  if ((rc = chunk_samples(h, fn, (size_t)n_samples, per, LN * 36, &C))) return rc;
+  if ((rc = chunk_samples(h, fn, (size_t)n_samples, per, NodeFold::bytes(LN) + LN * 8, &C))) return rc;
   Tmp tm(h);
   uint8_t* Y = nullptr;
-  u64 *Ao = nullptr, *Ai = nullptr, *arank = nullptr;
-  double *cval = nullptr, *asum = nullptr, *asq = nullptr;
-  unsigned *crank = nullptr, *atop = nullptr, *amain = nullptr, *aleast = nullptr;
+  u64 *Ao = nullptr, *Ai = nullptr;
+  double* cval = nullptr;
+  unsigned *crank = nullptr, *amain = nullptr, *aleast = nullptr;
+  NodeFold fold;
   if (!summary && (rc = tm.get(&no_summary, C * g.L * 16, "vmr_sample_cores: the summary"))) return rc;
   if (!values && (rc = tm.get(&no_values, C * LN * 2, "vmr_sample_cores: the values"))) return rc;
-  if ((rc = tm.get(&Y, C * b.ties, "vmr_sample_cores: the samples")) ||
-      (rc = tm.get(&Ao, C * b.bits_b, "vmr_sample_cores: the out-neighbour bits")) ||
-      (rc = tm.get(&Ai, C * b.bits_b, "vmr_sample_cores: the in-neighbour bits")) ||
+  if ((rc = bit_rows_get(tm, b, C, fn, "samples", &Y, &Ao, &Ai)) ||
       (rc = tm.get(&cval, C * LN * 8, "vmr_sample_cores: the values as doubles")) ||
-      (rc = tm.get(&crank, C * LN * 4, "vmr_sample_cores: the ranks")) ||
-      (rc = tm.get(&asum, LN * 8, "vmr_sample_cores: the node sums")) ||
-      (rc = tm.get(&asq, LN * 8, "vmr_sample_cores: the node sums of squares")) ||
-      (rc = tm.get(&arank, LN * 8, "vmr_sample_cores: the node rank sums")) ||
-      (rc = tm.get(&atop, LN * 4, "vmr_sample_cores: the node top counts")) ||
+      (rc = tm.get(&crank, C * LN * 4, "vmr_sample_cores: the ranks")) || (rc = fold.begin(h, tm, fn, LN, top_k)) ||
       (rc = tm.get(&amain, LN * 4, "vmr_sample_cores: the node main-core counts")) ||
       (rc = tm.get(&aleast, LN * 4, "vmr_sample_cores: the node k-core counts")))
     return rc;
-  HIPCHK(h, hipMemsetAsync(asum, 0, LN * 8, h->stream));
-  HIPCHK(h, hipMemsetAsync(asq, 0, LN * 8, h->stream));
-  HIPCHK(h, hipMemsetAsync(arank, 0, LN * 8, h->stream));
-  HIPCHK(h, hipMemsetAsync(atop, 0, LN * 4, h->stream));
   HIPCHK(h, hipMemsetAsync(amain, 0, LN * 4, h->stream));
   HIPCHK(h, hipMemsetAsync(aleast, 0, LN * 4, h->stream));
   rc = sampled_chunks(h, tm, (size_t)n_samples, C, seed, n_trials, Y, out, [&](size_t, int c) -> int {
@@ -366,23 +314,16 @@ extern "C" int vmr_sample_cores(vmr_handle h, uint64_t seed, int n_samples, int 
     unsigned short* cv = values ? out[1].as<unsigned short>() : no_values;
     if ((rc2 = tri_pack_chunk(h, Y, c, Ao, Ai))) return rc2;
     if ((rc2 = core_chunk(h, b, c, mode, k_min, Ao, Ai, cv, cval, crank, csum))) return rc2;
-    hipLaunchKernelGGL(k_node_fold, dim3(grid_for(LN, 256, 0xffffffffu)), dim3(256), 0, h->stream, cval, crank, c, LN, (unsigned)top_k, asum, asq,
-                       arank, atop);
-    HIPCHK(h, hipGetLastError());
+    if ((rc2 = fold.add(h, cval, crank, c))) return rc2;
     hipLaunchKernelGGL(k_core_fold_counts, dim3(grid_for(LN, 256, 0xffffffffu)), dim3(256), 0, h->stream, cv, csum, c, g.L, g.N, (unsigned)k_min,
                        amain, aleast);
     HIPCHK(h, hipGetLastError());
     return VMR_OK;
   });
   if (rc) return rc;
-  HIPCHK(h, hipMemcpyAsync(node_sum, asum, LN * 8, hipMemcpyDeviceToHost, h->stream));
-  if (node_sumsq) HIPCHK(h, hipMemcpyAsync(node_sumsq, asq, LN * 8, hipMemcpyDeviceToHost, h->stream));
-  if (node_rank_sum) HIPCHK(h, hipMemcpyAsync(node_rank_sum, arank, LN * 8, hipMemcpyDeviceToHost, h->stream));
-  if (node_top) HIPCHK(h, hipMemcpyAsync(node_top, atop, LN * 4, hipMemcpyDeviceToHost, h->stream));
   if (node_main) HIPCHK(h, hipMemcpyAsync(node_main, amain, LN * 4, hipMemcpyDeviceToHost, h->stream));
   if (node_atleast) HIPCHK(h, hipMemcpyAsync(node_atleast, aleast, LN * 4, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return VMR_OK;
+  return fold.finish(h, node_sum, node_sumsq, node_rank_sum, node_top);
 }
 
 extern "C" int vmr_network_cores(vmr_handle h, const uint8_t* Y, int n, int mode, int k_min, uint16_t* values, uint32_t* summary) {
@@ -394,8 +335,9 @@ extern "C" int vmr_network_cores(vmr_handle h, const uint8_t* Y, int n, int mode
   if (!Y) return fail(h, VMR_EINVAL, "vmr_network_cores: Y is NULL");
   if (!values) return fail(h, VMR_EINVAL, "vmr_network_cores: values is NULL");
   HIPCHK(h, hipSetDevice(h->device));
-  const CoreShape b = core_shape(h->g);
-  const size_t per = b.ties + 2 * b.bits_b + b.LN * 2 + (size_t)h->g.L * 16;
+  const Geo& g = h->g;
+  const BitRows b = bit_rows(g);
+  const size_t per = b.per() + b.LN * 2 + (size_t)g.L * 16;
   size_t C;
   if ((rc = chunk_samples(h, fn, (size_t)n, per, 0, &C, "network"))) return rc;
   Tmp tm(h);
@@ -403,20 +345,14 @@ extern "C" int vmr_network_cores(vmr_handle h, const uint8_t* Y, int n, int mode
   u64 *Ao = nullptr, *Ai = nullptr;
   unsigned short* cv = nullptr;
   unsigned* csum = nullptr;
-  if ((rc = tm.get(&Yd, C * b.ties, "vmr_network_cores: the networks")) ||
-      (rc = tm.get(&Ao, C * b.bits_b, "vmr_network_cores: the out-neighbour bits")) ||
-      (rc = tm.get(&Ai, C * b.bits_b, "vmr_network_cores: the in-neighbour bits")) ||
-      (rc = tm.get(&cv, C * b.LN * 2, "vmr_network_cores: the values")) ||
-      (summary && (rc = tm.get(&csum, C * h->g.L * 16, "vmr_network_cores: the summary"))))
+  if ((rc = bit_rows_get(tm, b, C, fn, "networks", &Yd, &Ao, &Ai)) || (rc = tm.get(&cv, C * b.LN * 2, "vmr_network_cores: the values")) ||
+      (summary && (rc = tm.get(&csum, C * g.L * 16, "vmr_network_cores: the summary"))))
     return rc;
-  for (size_t s0 = 0; s0 < (size_t)n; s0 += C) {
-    const size_t c = std::min<size_t>(C, (size_t)n - s0);
-    HIPCHK(h, hipMemcpyAsync(Yd, Y + s0 * b.ties, c * b.ties, hipMemcpyHostToDevice, h->stream));
-    if ((rc = tri_pack_chunk(h, Yd, (int)c, Ao, Ai))) return rc;
-    if ((rc = core_chunk(h, b, (int)c, mode, k_min, Ao, Ai, cv, nullptr, nullptr, csum))) return rc;
-    HIPCHK(h, hipMemcpyAsync(values + s0 * b.LN, cv, c * b.LN * 2, hipMemcpyDeviceToHost, h->stream));
-    if (summary) HIPCHK(h, hipMemcpyAsync(summary + s0 * h->g.L * 4, csum, c * h->g.L * 16, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-  }
-  return VMR_OK;
+  return uploaded_chunks(h, b, (size_t)n, C, Y, Yd, Ao, Ai, [&](size_t s0, int c) -> int {
+    int rc2;
+    if ((rc2 = core_chunk(h, b, c, mode, k_min, Ao, Ai, cv, nullptr, nullptr, csum))) return rc2;
+    HIPCHK(h, hipMemcpyAsync(values + s0 * b.LN, cv, (size_t)c * b.LN * 2, hipMemcpyDeviceToHost, h->stream));
+    if (summary) HIPCHK(h, hipMemcpyAsync(summary + s0 * g.L * 4, csum, (size_t)c * g.L * 16, hipMemcpyDeviceToHost, h->stream));
+    return VMR_OK;
+  });
 }

@@ -50,6 +50,26 @@ __device__ __forceinline__ u64 wave_sum_ull(u64 v) {
   for (int o = 32; o > 0; o >>= 1) v += (u64)__shfl_xor((long long)v, o, 64);
   return v;
 }
+__device__ __forceinline__ unsigned wave_sum_u(unsigned v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += (unsigned)__shfl_xor((int)v, o, 64);
+  return v;
+}
+__device__ __forceinline__ unsigned wave_min_u(unsigned v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = min(v, (unsigned)__shfl_xor((int)v, o, 64));
+  return v;
+}
+__device__ __forceinline__ unsigned wave_max_u(unsigned v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, o, 64));
+  return v;
+}
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+  return v;
+}
 
 // the workgroup's sum in thread 0: the waves in index order (every thread calls it; red holds a slot per wave)
 __device__ __forceinline__ u64 block_sum_ull(u64 v, u64* red) {

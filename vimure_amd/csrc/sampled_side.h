@@ -11,6 +11,13 @@
 // The transposed tile.  What needs tie (j, i) next to tie (i, j) -- mutual pairs, in-neighbours -- walks a strip of 64 rows tile by
 // tile, four waves per workgroup, wave w on rows 4 it + w with lane = column, and reads the tile (bj, bi) transposed through LDS
 // (tile_transposed): both reads of global memory are along rows.
+//
+// The bit rows.  The units that walk neighbourhoods (triads.hip, connectivity.hip, centrality.hip, betweenness.hip, cores.hip) pack
+// a chunk's Y[c][L][N][N] into two bitsets of 64-bit words, W = ceil(N / 64) per row: Aout[c][L][N][W] (row i: the targets of i)
+// and Ain[c][L][N][W] (row i: the sources of i, the rows of A^T), A = (Y > 0) with the diagonal bit cleared and the bits at and
+// above N zero (tri_pack_chunk, triads.hip).  A row is walked by G = 1 << lG lanes, the largest power of two <= min(W, 64), that
+// stride its W words, 64 / G rows side by side.  BitRows holds these numbers, bit_rows_get the three buffers of a chunk;
+// uploaded_chunks is the chunk loop of the calls that take the caller's networks in place of samples.
 #ifndef VMR_SAMPLED_SIDE_H
 #define VMR_SAMPLED_SIDE_H
 #include "read_side.h"
@@ -82,6 +89,60 @@ static inline int chunk_samples(vmr_ctx* h, const char* fn, size_t n, size_t per
     return fail(h, VMR_EINVAL, msg);
   }
   return VMR_OK;
+}
+
+// The shape of a bit-row chunk on a handle (the layout is in the head of this file), what its kernels are launched with.
+struct BitRows {
+  int W, lG;           // words per row; log2 of the lanes that stride a row: the largest power of two <= min(W, 64)
+  size_t LN, ties;     // L N; bytes of Y per sample
+  size_t bits_b;       // bytes of one set of bit rows per sample
+  size_t per() const { return ties + 2 * bits_b; }   // device bytes per sample of a chunk: Y, Aout and Ain
+};
+static inline BitRows bit_rows(const Geo& g) {
+  BitRows b;
+  b.W = (g.N + 63) / 64;
+  b.lG = 0;
+  while ((2 << b.lG) <= b.W && b.lG < 6) ++b.lG;
+  b.LN = (size_t)g.L * g.N;
+  b.ties = b.LN * g.N;
+  b.bits_b = b.LN * b.W * 8;
+  return b;
+}
+
+// Y, Aout and Ain for a chunk of C, from tm; what: "samples" or "networks"
+static inline int bit_rows_get(Tmp& tm, const BitRows& b, size_t C, const char* fn, const char* what, uint8_t** Y, u64** Ao, u64** Ai) {
+  const std::string f = std::string(fn) + ": the ";
+  int rc;
+  if ((rc = tm.get(Y, C * b.ties, (f + what).c_str())) || (rc = tm.get(Ao, C * b.bits_b, (f + "out-neighbour bits").c_str())) ||
+      (rc = tm.get(Ai, C * b.bits_b, (f + "in-neighbour bits").c_str())))
+    return rc;
+  return VMR_OK;
+}
+
+// The chunk loop over n networks the caller supplies, Y[n][L][N][N] in host memory, in chunks of C: per chunk of c networks from
+// network s0 uploads them to Yd, packs them into Ao and Ai, runs run(s0, c) -- the unit's kernels and its copies to the host, on
+// the handle's stream; VMR_OK or what ends the call -- and waits for the stream.
+template <class Run>
+static int uploaded_chunks(vmr_ctx* h, const BitRows& b, size_t n, size_t C, const uint8_t* Y, uint8_t* Yd, u64* Ao, u64* Ai, Run run) {
+  int rc;
+  for (size_t s0 = 0; s0 < n; s0 += C) {
+    const size_t c = std::min<size_t>(C, n - s0);
+    HIPCHK(h, hipMemcpyAsync(Yd, Y + s0 * b.ties, c * b.ties, hipMemcpyHostToDevice, h->stream));
+    if ((rc = tri_pack_chunk(h, Yd, (int)c, Ao, Ai))) return rc;
+    if ((rc = run(s0, (int)c))) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  }
+  return VMR_OK;
+}
+
+// f(std::integral_constant<int, KPT>) with KPT = 1, 2, 4 or 8, the smallest that is >= kpt: the nodes a thread of a 256-thread
+// workgroup keeps in registers, for the kernels that take them as a template argument (kpt <= 8: N <= 2048)
+template <class F>
+static inline void with_kpt(int kpt, F f) {
+  if (kpt <= 1) f(std::integral_constant<int, 1>{});
+  else if (kpt <= 2) f(std::integral_constant<int, 2>{});
+  else if (kpt <= 4) f(std::integral_constant<int, 4>{});
+  else f(std::integral_constant<int, 8>{});
 }
 
 // one output of a sampled call: `bytes` per sample, sample-major

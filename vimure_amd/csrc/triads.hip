@@ -6,10 +6,9 @@
 // and U = A | A^T:  transitive, cyclic, two_paths, triangles_u, wedges_u, edges_u (include/vimure_hip.h has the definitions) and,
 // per node, the triangles of U through it and its degree in U.
 //
-// Layout.  A chunk's Y[c][L][N][N] bytes are packed into two bitsets of 64-bit words, W = ceil(N / 64) per row:
-// Aout[c][L][N][W] (row i: the targets of i) and Ain[c][L][N][W] (row i: the sources of i, i.e. the rows of A^T) -- k_tri_pack,
+// Layout.  A chunk's Y[c][L][N][N] bytes are packed into the bit rows Aout and Ain (sampled_side.h has the layout) by k_tri_pack,
 // the strip walk of sampled_side.h: a wave's ballot over 64 consecutive bytes of a row is one word of Aout, the transposed tile
-// gives the word of Ain.  The diagonal bit is cleared there, the bits at and above N are zero.
+// gives the word of Ain.
 // k_tri_count: one wave per (node i, layer, sample).  It lists the neighbours of i in U (block of TRI_BLK words at a time: a
 // wave scan of the words' popcounts gives every lane its place in the wave's LDS list), then walks the list 64 / G neighbours per
 // step, G = the largest power of two <= min(W, 64) lanes striding over the W words of a neighbour's rows:
@@ -307,27 +306,23 @@ extern "C" int vmr_sample_triads(vmr_handle h, uint64_t seed, int n_samples, int
   if ((rc = sampled_begin(h, "vmr_sample_triads", n_samples, n_trials))) return rc;
   const Geo& g = h->g;
   if (g.N > 65536) return fail(h, VMR_EINVAL, "vmr_sample_triads: the triangles through a node are 32-bit counts: N <= 65536");
-  const int W = (g.N + 63) / 64;
-  const size_t ties = (size_t)g.L * g.N * g.N, bits_b = (size_t)g.L * g.N * W * 8, node_b = (size_t)g.L * g.N * 4;
+  const BitRows b = bit_rows(g);
+  const size_t node_b = b.LN * 4;
   SampledOut out[3] = {{counts, (size_t)g.L * VMR_TRIAD_NSTAT * 8, true, "vmr_sample_triads: the counts"},
                        {node_tri, node_b, false, "vmr_sample_triads: the node triangles"},
                        {node_deg, node_b, false, "vmr_sample_triads: the node degrees"}};
-  const size_t per = ties + 2 * bits_b + out[0].bytes + (node_tri ? node_b : 0) + (node_deg ? node_b : 0);   // device bytes per sample of a chunk
+  const size_t per = b.per() + out[0].bytes + (node_tri ? node_b : 0) + (node_deg ? node_b : 0);   // device bytes per sample of a chunk
   size_t C;
   if ((rc = chunk_samples(h, "vmr_sample_triads", (size_t)n_samples, per, 0, &C))) return rc;
   Tmp tm(h);
   uint8_t* Y = nullptr;
-  unsigned long long *Ao = nullptr, *Ai = nullptr;
-  if ((rc = tm.get(&Y, C * ties, "vmr_sample_triads: the samples")) || (rc = tm.get(&Ao, C * bits_b, "vmr_sample_triads: the out-neighbour bits")) ||
-      (rc = tm.get(&Ai, C * bits_b, "vmr_sample_triads: the in-neighbour bits")))
-    return rc;
-  int lG = 0;   // lanes per neighbour: the largest power of two <= min(W, 64)
-  while ((2 << lG) <= W && lG < 6) ++lG;
+  u64 *Ao = nullptr, *Ai = nullptr;
+  if ((rc = bit_rows_get(tm, b, C, "vmr_sample_triads", "samples", &Y, &Ao, &Ai))) return rc;
   const unsigned nquad = (unsigned)((g.N + 3) / 4);
   rc = sampled_chunks(h, tm, (size_t)n_samples, C, seed, n_trials, Y, out, [&](size_t, int c) -> int {
     int rc2;
     if ((rc2 = tri_pack_chunk(h, Y, c, Ao, Ai))) return rc2;
-    hipLaunchKernelGGL(k_tri_count, dim3(nquad, (unsigned)g.L, (unsigned)c), dim3(256), 0, h->stream, Ao, Ai, g.N, g.L, W, lG,
+    hipLaunchKernelGGL(k_tri_count, dim3(nquad, (unsigned)g.L, (unsigned)c), dim3(256), 0, h->stream, Ao, Ai, g.N, g.L, b.W, b.lG,
                        out[0].as<unsigned long long>(), out[1].as<int32_t>(), out[2].as<int32_t>());
     HIPCHK(h, hipGetLastError());
     return VMR_OK;

@@ -98,6 +98,7 @@ EDGE_COLUMNS = (("l", np.int32), ("i", np.int32), ("j", np.int32), ("y", np.uint
                 ("n_rep", np.uint32), ("total", np.uint64), ("n_mask", np.uint32), ("ego", np.uint32), ("alter", np.uint32),
                 ("y_T", np.uint8), ("n_rep_T", np.uint32), ("total_T", np.uint64))
 _TORCH_NAME = {"uint32": "int32", "uint64": "int64"}
+_CORE_STATS = ("degeneracy", "main_core_size", "core_sum", "kcore_size")   # the columns of the k-core calls' summary
 
 
 def _f64(a):
@@ -527,17 +528,58 @@ class CaviEngine:
             out.update(zip(_lib.CONN_NODE_NAMES, na))
         return out
 
+    @staticmethod
+    def _name_code(value, names, what, error):
+        """The code of a direction or mode given by name; a name that is none of `names` is refused here."""
+        if isinstance(value, str):
+            if value not in names:
+                raise error(f"{what} must be one of {names}, got {value!r}")
+            return names.index(value)
+        return int(value)
+
     def _centrality_args(self, q, direction):
         """(q float64 [L], the direction's code) for the centrality calls; what is not a number or a name is refused here."""
         try:
             qa = np.ascontiguousarray(np.broadcast_to(np.asarray(q, dtype=np.float64), (self.L,)))
         except (TypeError, ValueError):
             raise CentralityArgumentError(f"q must be a scalar or {self.L} numbers, one per layer") from None
-        if isinstance(direction, str):
-            if direction not in _lib.CENT_DIRECTIONS:
-                raise CentralityArgumentError(f"direction must be one of {_lib.CENT_DIRECTIONS}, got {direction!r}")
-            direction = _lib.CENT_DIRECTIONS.index(direction)
-        return qa, int(direction)
+        return qa, self._name_code(direction, _lib.CENT_DIRECTIONS, "direction", CentralityArgumentError)
+
+    def _node_outputs(self, S, stats, stat_dtype, values_dtype, counters=()):
+        """What a call of the node-score fold writes: (pointers, result).  pointers, in the calls' order: node_sum, node_sumsq
+        (float64 [L, N]), node_rank_sum (uint64), node_top and the unit's `counters` (uint32), the summary `stat_dtype` [S, L,
+        len(stats)] and the values `values_dtype` [S, L, N] (None: not asked for).  result() is the call's dict: the integers as
+        int64, a `stats` name for each column of the summary, `values` when asked for."""
+        S, LN = max(int(S), 0), (self.L, self.N)
+        sums = {"node_sum": np.zeros(LN, np.float64), "node_sumsq": np.zeros(LN, np.float64)}
+        ints = {"node_rank_sum": np.zeros(LN, np.uint64), "node_top": np.zeros(LN, np.uint32)}
+        for k in counters:
+            ints[k] = np.zeros(LN, np.uint32)
+        sm = np.zeros((S, self.L, len(stats)), stat_dtype)
+        vals = None if values_dtype is None else np.zeros((S,) + LN, values_dtype)
+        stat_out = np.float64 if stat_dtype is np.float64 else np.int64
+
+        def result():
+            out = dict(sums)
+            for k, a in ints.items():
+                out[k] = a.astype(np.int64)
+            for q, name in enumerate(stats):
+                out[name] = sm[..., q].astype(stat_out)
+            if vals is not None:
+                out["values"] = vals
+            return out
+        ptrs = [a.ctypes.data for a in sums.values()] + [a.ctypes.data for a in ints.values()]
+        return ptrs + [sm.ctypes.data, None if vals is None else vals.ctypes.data], result
+
+    def _network_ties(self, Y, error):
+        """(ties uint8 [n, L, N, N], one) for the `network_*` calls: Y [L, N, N] (one: True) or [n, L, N, N], an entry > 0 a tie."""
+        Ya = np.asarray(Y)
+        one = Ya.ndim == 3
+        if one:
+            Ya = Ya[None]
+        if Ya.ndim != 4 or Ya.shape[1:] != (self.L, self.N, self.N):
+            raise error(f"Y has shape {np.shape(Y)}, the engine's networks {(self.L, self.N, self.N)}")
+        return np.ascontiguousarray(Ya > 0, dtype=np.uint8), one
 
     def sample_centrality(self, seed, n_samples, q, T, direction="out", top_k=10, n_trials=1, values=False):
         """Diffusion centrality of n_samples posterior samples, computed on the device (vmr_sample_centrality): sample s is
@@ -548,22 +590,11 @@ class CaviEngine:
         (#{s : rank < top_k}), `total`, `max` float64 [S, L] (sum_v c[v], max_v c[v]); with values=True also `values` float64
         [S, L, N].  Every number is the same from run to run and for any chunking.  N is at most `_lib.CENT_NMAX`.  A refused
         argument raises `CentralityArgumentError`."""
-        S = int(n_samples)
         qa, d = self._centrality_args(q, direction)
-        LN = (self.L, self.N)
-        ns, nq = np.zeros(LN, np.float64), np.zeros(LN, np.float64)
-        nr, ntop = np.zeros(LN, np.uint64), np.zeros(LN, np.uint32)
-        sm = np.zeros((max(S, 0), self.L, 2), np.float64)
-        vals = np.zeros((max(S, 0),) + LN, np.float64) if values else None
-        self._check(self.lib.vmr_sample_centrality(self._h, int(seed) & (2 ** 64 - 1), S, int(n_trials), qa.ctypes.data, int(T), d, int(top_k),
-                                                   ns.ctypes.data, nq.ctypes.data, nr.ctypes.data, ntop.ctypes.data, sm.ctypes.data,
-                                                   vals.ctypes.data if values else None),
-                    CentralityArgumentError)
-        out = {"node_sum": ns, "node_sumsq": nq, "node_rank_sum": nr.astype(np.int64), "node_top": ntop.astype(np.int64),
-               "total": np.ascontiguousarray(sm[..., 0]), "max": np.ascontiguousarray(sm[..., 1])}
-        if values:
-            out["values"] = vals
-        return out
+        ptrs, result = self._node_outputs(n_samples, ("total", "max"), np.float64, np.float64 if values else None)
+        self._check(self.lib.vmr_sample_centrality(self._h, int(seed) & (2 ** 64 - 1), int(n_samples), int(n_trials), qa.ctypes.data, int(T), d,
+                                                   int(top_k), *ptrs), CentralityArgumentError)
+        return result()
 
     def mean_centrality(self, q, T, direction="out"):
         """The diffusion centrality of the posterior MEAN network (vmr_mean_centrality), no sampling: float64 [L, N],
@@ -575,15 +606,6 @@ class CaviEngine:
         self._check(self.lib.vmr_mean_centrality(self._h, qa.ctypes.data, int(T), d, out.ctypes.data), CentralityArgumentError)
         return out
 
-    @staticmethod
-    def _betweenness_direction(direction):
-        """The direction's code for the betweenness calls; a name that is none is refused here."""
-        if isinstance(direction, str):
-            if direction not in _lib.BTW_DIRECTIONS:
-                raise BetweennessArgumentError(f"direction must be one of {_lib.BTW_DIRECTIONS}, got {direction!r}")
-            return _lib.BTW_DIRECTIONS.index(direction)
-        return int(direction)
-
     def sample_betweenness(self, seed, n_samples, direction="directed", top_k=10, n_trials=1, values=False):
         """Betweenness centrality of n_samples posterior samples, computed on the device (vmr_sample_betweenness): sample s is
         `self.sample(seed + s, n_trials)`, A = (Y > 0) with the diagonal cleared, the search graph A ("directed") or A | A.T
@@ -593,48 +615,22 @@ class CaviEngine:
         [L, N] (sum_s b, sum_s b^2), `node_rank_sum` int64 [L, N], `node_top` int64 [L, N] (#{s : rank < top_k}), `total`, `max`
         float64 [S, L] (sum_v b[v], max_v b[v]); with values=True also `values` float64 [S, L, N].  Every number is the same from
         run to run and for any chunking.  N is at most `_lib.BTW_NMAX`.  A refused argument raises `BetweennessArgumentError`."""
-        S = int(n_samples)
-        d = self._betweenness_direction(direction)
-        LN = (self.L, self.N)
-        ns, nq = np.zeros(LN, np.float64), np.zeros(LN, np.float64)
-        nr, ntop = np.zeros(LN, np.uint64), np.zeros(LN, np.uint32)
-        sm = np.zeros((max(S, 0), self.L, 2), np.float64)
-        vals = np.zeros((max(S, 0),) + LN, np.float64) if values else None
-        self._check(self.lib.vmr_sample_betweenness(self._h, int(seed) & (2 ** 64 - 1), S, int(n_trials), d, int(top_k), ns.ctypes.data,
-                                                    nq.ctypes.data, nr.ctypes.data, ntop.ctypes.data, sm.ctypes.data,
-                                                    vals.ctypes.data if values else None),
+        d = self._name_code(direction, _lib.BTW_DIRECTIONS, "direction", BetweennessArgumentError)
+        ptrs, result = self._node_outputs(n_samples, ("total", "max"), np.float64, np.float64 if values else None)
+        self._check(self.lib.vmr_sample_betweenness(self._h, int(seed) & (2 ** 64 - 1), int(n_samples), int(n_trials), d, int(top_k), *ptrs),
                     BetweennessArgumentError)
-        out = {"node_sum": ns, "node_sumsq": nq, "node_rank_sum": nr.astype(np.int64), "node_top": ntop.astype(np.int64),
-               "total": np.ascontiguousarray(sm[..., 0]), "max": np.ascontiguousarray(sm[..., 1])}
-        if values:
-            out["values"] = vals
-        return out
+        return result()
 
     def network_betweenness(self, Y, direction="directed"):
         """The betweenness of `sample_betweenness` of networks the caller supplies (vmr_network_betweenness), by the same kernels:
         Y [L, N, N] -> float64 [L, N], or [n, L, N, N] -> [n, L, N]; an entry > 0 is a tie, the diagonal is ignored.  The engine
         gives the shape and the device only: no state is needed and rho is not touched.  A refused argument raises
         `BetweennessArgumentError`."""
-        d = self._betweenness_direction(direction)
-        Ya = np.asarray(Y)
-        one = Ya.ndim == 3
-        if one:
-            Ya = Ya[None]
-        if Ya.ndim != 4 or Ya.shape[1:] != (self.L, self.N, self.N):
-            raise BetweennessArgumentError(f"Y has shape {np.shape(Y)}, the engine's networks {(self.L, self.N, self.N)}")
-        ties = np.ascontiguousarray(Ya > 0, dtype=np.uint8)
+        d = self._name_code(direction, _lib.BTW_DIRECTIONS, "direction", BetweennessArgumentError)
+        ties, one = self._network_ties(Y, BetweennessArgumentError)
         out = np.zeros((ties.shape[0], self.L, self.N), np.float64)
         self._check(self.lib.vmr_network_betweenness(self._h, ties.ctypes.data, ties.shape[0], d, out.ctypes.data), BetweennessArgumentError)
         return out[0] if one else out
-
-    @staticmethod
-    def _cores_mode(mode):
-        """The mode's code for the k-core calls; a name that is none is refused here."""
-        if isinstance(mode, str):
-            if mode not in _lib.CORE_MODES:
-                raise CoresArgumentError(f"mode must be one of {_lib.CORE_MODES}, got {mode!r}")
-            return _lib.CORE_MODES.index(mode)
-        return int(mode)
 
     def sample_cores(self, seed, n_samples, mode="union", k_min=0, top_k=10, n_trials=1, values=False):
         """The k-core decomposition of n_samples posterior samples, computed on the device (vmr_sample_cores): sample s is
@@ -648,47 +644,26 @@ class CaviEngine:
         [S, L] (max_v core, the nodes that attain it, sum_v core, #{v : core >= k_min}); with values=True also `values` uint16
         [S, L, N].  Every number is the same from run to run and for any chunking.  N is at most `_lib.CORE_NMAX`.  A refused
         argument raises `CoresArgumentError`."""
-        S = int(n_samples)
-        md = self._cores_mode(mode)
-        LN = (self.L, self.N)
-        ns, nq = np.zeros(LN, np.float64), np.zeros(LN, np.float64)
-        nr = np.zeros(LN, np.uint64)
-        ntop, nmain, nat = np.zeros(LN, np.uint32), np.zeros(LN, np.uint32), np.zeros(LN, np.uint32)
-        sm = np.zeros((max(S, 0), self.L, 4), np.uint32)
-        vals = np.zeros((max(S, 0),) + LN, np.uint16) if values else None
-        self._check(self.lib.vmr_sample_cores(self._h, int(seed) & (2 ** 64 - 1), S, int(n_trials), md, int(k_min), int(top_k), ns.ctypes.data,
-                                              nq.ctypes.data, nr.ctypes.data, ntop.ctypes.data, nmain.ctypes.data, nat.ctypes.data,
-                                              sm.ctypes.data, vals.ctypes.data if values else None),
+        md = self._name_code(mode, _lib.CORE_MODES, "mode", CoresArgumentError)
+        ptrs, result = self._node_outputs(n_samples, _CORE_STATS, np.uint32, np.uint16 if values else None, counters=("node_main", "node_atleast"))
+        self._check(self.lib.vmr_sample_cores(self._h, int(seed) & (2 ** 64 - 1), int(n_samples), int(n_trials), md, int(k_min), int(top_k), *ptrs),
                     CoresArgumentError)
-        out = {"node_sum": ns, "node_sumsq": nq, "node_rank_sum": nr.astype(np.int64), "node_top": ntop.astype(np.int64),
-               "node_main": nmain.astype(np.int64), "node_atleast": nat.astype(np.int64)}
-        for q, name in enumerate(("degeneracy", "main_core_size", "core_sum", "kcore_size")):
-            out[name] = sm[..., q].astype(np.int64)
-        if values:
-            out["values"] = vals
-        return out
+        return result()
 
     def network_cores(self, Y, mode="union", k_min=0, summary=False):
         """The coreness of `sample_cores` of networks the caller supplies (vmr_network_cores), by the same kernel: Y [L, N, N] ->
         uint16 [L, N], or [n, L, N, N] -> [n, L, N]; an entry > 0 is a tie, the diagonal is ignored.  summary=True: returns
         (values, dict of `degeneracy`, `main_core_size`, `core_sum`, `kcore_size`, int64 [L] or [n, L]).  The engine gives the
         shape and the device only: no state is needed and rho is not touched.  A refused argument raises `CoresArgumentError`."""
-        md = self._cores_mode(mode)
-        Ya = np.asarray(Y)
-        one = Ya.ndim == 3
-        if one:
-            Ya = Ya[None]
-        if Ya.ndim != 4 or Ya.shape[1:] != (self.L, self.N, self.N):
-            raise CoresArgumentError(f"Y has shape {np.shape(Y)}, the engine's networks {(self.L, self.N, self.N)}")
-        ties = np.ascontiguousarray(Ya > 0, dtype=np.uint8)
+        md = self._name_code(mode, _lib.CORE_MODES, "mode", CoresArgumentError)
+        ties, one = self._network_ties(Y, CoresArgumentError)
         out = np.zeros((ties.shape[0], self.L, self.N), np.uint16)
         sm = np.zeros((ties.shape[0], self.L, 4), np.uint32) if summary else None
         self._check(self.lib.vmr_network_cores(self._h, ties.ctypes.data, ties.shape[0], md, int(k_min), out.ctypes.data,
                                                sm.ctypes.data if summary else None), CoresArgumentError)
         if not summary:
             return out[0] if one else out
-        smd = {name: (sm[0, :, q] if one else sm[..., q]).astype(np.int64)
-               for q, name in enumerate(("degeneracy", "main_core_size", "core_sum", "kcore_size"))}
+        smd = {name: (sm[0, :, q] if one else sm[..., q]).astype(np.int64) for q, name in enumerate(_CORE_STATS)}
         return (out[0] if one else out), smd
 
     def _mixing_args(self, groups, C):

@@ -6,6 +6,7 @@ labels into the engine's group codes.
 import numpy as np
 
 from .netstats import _ratio
+from .node_scores import quantile_row
 
 
 def groups_from_frame(meta, column, id="pid"):
@@ -145,15 +146,6 @@ class MixingStats:
                 out["jaccard:%d" % l2] = self.jaccard[..., l2]
         return out
 
-    @staticmethod
-    def _row(v, q):
-        v = np.asarray(v, dtype=np.float64)
-        v = v[~np.isnan(v)]
-        row = {"mean": v.mean() if v.size else np.nan, "std": v.std() if v.size else np.nan}
-        qs = np.quantile(v, q) if v.size else np.full(len(q), np.nan)
-        row.update({"q%g" % x: float(y) for x, y in zip(q, qs)})
-        return row
-
     def summary(self, q=(0.025, 0.5, 0.975)):
         """DataFrame with one row per (layer, statistic): mean, std (population) and the quantiles q over the samples (NaN
         samples left out)."""
@@ -163,7 +155,7 @@ class MixingStats:
         for l in range(self.L):
             for name, arr in self.statistics().items():
                 row = {"layer": l, "statistic": name}
-                row.update(self._row(arr[:, l], q))
+                row.update(quantile_row(arr[:, l], q))
                 rows.append(row)
         return pd.DataFrame(rows, columns=["layer", "statistic", "mean", "std"] + ["q%g" % x for x in q])
 
@@ -179,7 +171,7 @@ class MixingStats:
             for a in range(self.C):
                 for b in range(self.C):
                     row = {"layer": l, "from": self.labels[a], "to": self.labels[b]}
-                    row.update(self._row(self.mix[:, l, a, b], q))
+                    row.update(quantile_row(self.mix[:, l, a, b], q))
                     if self.expected is not None and "mix" in self.expected:
                         row["expected"] = float(self.expected["mix"][l, a, b])
                     rows.append(row)

@@ -9,6 +9,7 @@ selection (:428-437, :925-942) and the read-out methods (:1062-1214).
 What does NOT happen here: any CAVI arithmetic.  The sweeps and the ELBO run in
 libvimure_hip.so (`vimure_amd.engine.CaviEngine`); without it `fit` raises.
 """
+import contextlib
 import time
 import warnings
 
@@ -614,12 +615,8 @@ class VimureModel(TransformerMixin, BaseEstimator):
         if not hasattr(self, "gamma_shp_f"):
             raise ValueError("the model has not been fitted: call fit(..., keep_engine=True) first, or fit it and pass X=")
         code, thr = self._edge_method(method, threshold)
-        eng, tmp = self._ppc_engine(X, R)
-        try:
+        with self._read_engine(X, R) as eng:
             t = eng.edge_table(method=code, threshold=thr, select=select, layer=layer)
-        finally:
-            if tmp:
-                eng.close()
         return pd.DataFrame({
             "layer": np.asarray(t["l"], np.int64), "source": np.asarray(t["i"], np.int64), "target": np.asarray(t["j"], np.int64),
             "y": np.asarray(t["y"], np.int64), "probability": np.asarray(t["prob"], np.float64),
@@ -682,6 +679,16 @@ class VimureModel(TransformerMixin, BaseEstimator):
             raise
         return eng, True
 
+    @contextlib.contextmanager
+    def _read_engine(self, X, R):
+        """The engine of `_ppc_engine` for the length of a read-out; a temporary one is closed on the way out."""
+        eng, tmp = self._ppc_engine(X, R)
+        try:
+            yield eng
+        finally:
+            if tmp:
+                eng.close()
+
     def calculate_mean_poisson(self, X=None, R=None, layer=None, device=False):
         """Expected reports of the best realisation over the support of R -- the reference's `_calculate_mean_poisson`
         (model.py:1220-1293) computed on the GPU (vmr_mean_poisson): a SparseTensor of shape (L, N, N, M) whose subs are the
@@ -689,12 +696,8 @@ class VimureModel(TransformerMixin, BaseEstimator):
         reference keeps R.subs' order instead -- and vals = sum_k rho_f (G_exp_theta_f G_exp_lambda_f + G_exp_nu_f X^T).
         X None: the engine kept by fit(keep_engine=True); else X (and R, default the fit's) go to a temporary engine, as in
         `fit`.  layer: that layer only.  device=True: subs and vals are torch tensors on the GPU."""
-        eng, tmp = self._ppc_engine(X, R)
-        try:
+        with self._read_engine(X, R) as eng:
             subs, vals = eng.mean_poisson(layer=layer, device=device)
-        finally:
-            if tmp:
-                eng.close()
         shape = (self.L, self.N, self.N, self.M)
         if not device:
             return SparseTensor(subs, vals, shape=shape)
@@ -706,12 +709,8 @@ class VimureModel(TransformerMixin, BaseEstimator):
         """AUC of the expected reports against the observed ones (X > 0) over the support of R: `utils.calculate_AUC(mp, X,
         mask=R)` (reference utils.py:40-66), exact, on the GPU (vmr_report_auc); of one layer or of the whole tensor.  NaN with
         a warning when the support holds no positive or no negative.  Engine as in `calculate_mean_poisson`."""
-        eng, tmp = self._ppc_engine(X, R)
-        try:
+        with self._read_engine(X, R) as eng:
             auc, n_pos, n_neg = eng.report_auc(layer=layer)
-        finally:
-            if tmp:
-                eng.close()
         if n_pos == 0 or n_neg == 0:
             warnings.warn("No %s reports in the support: the AUC is undefined" % ("positive" if n_pos == 0 else "negative"),
                           UserWarning)
@@ -739,17 +738,13 @@ class VimureModel(TransformerMixin, BaseEstimator):
             if Y_true.shape != (self.L, self.N, self.N):
                 raise ValueError(f"Y_true has shape {Y_true.shape}, the fitted model's networks {(self.L, self.N, self.N)}")
             ref_edges = (Y_true > 0).sum(axis=(1, 2))
-        eng, tmp = self._ppc_engine(X, R)
-        try:
+        with self._read_engine(X, R) as eng:
             counts = eng.sample_stats(seed, n_samples, n_trials=n_trials, Y_ref=Y_true, degrees=degrees)
             expected = eng.expected_stats()
             tri = exp_tri = None
             if triads:
                 tri = eng.sample_triads(seed, n_samples, n_trials=n_trials, nodes=bool(local_clustering))
                 exp_tri = eng.expected_triads()
-        finally:
-            if tmp:
-                eng.close()
         if Y_true is not None and ref_edges is None:
             ref_edges = (Y_true > 0).sum(dim=(1, 2)).cpu().numpy()
         return NetworkStats(self.N, counts, expected=expected, ref_edges=ref_edges, seed=seed, n_trials=n_trials, triads=tri,
@@ -782,14 +777,10 @@ class VimureModel(TransformerMixin, BaseEstimator):
                 raise ValueError("groups labels no node")
         elif not overlap:
             raise ValueError("nothing to compute: no groups and overlap=False")
-        eng, tmp = self._ppc_engine(X, R)
-        try:
+        with self._read_engine(X, R) as eng:
             C = None if codes is None else len(labels)
             counts = eng.sample_mixing(seed, n_samples, groups=codes, C=C, n_trials=n_trials, skip_diagonal=skip_diagonal, overlap=overlap)
             expected = eng.expected_mixing(groups=codes, C=C, skip_diagonal=skip_diagonal, overlap=overlap)
-        finally:
-            if tmp:
-                eng.close()
         return MixingStats(self.N, counts, codes=codes, labels=labels, expected=expected, skip_diagonal=skip_diagonal, seed=seed,
                            n_trials=n_trials)
 
@@ -806,12 +797,8 @@ class VimureModel(TransformerMixin, BaseEstimator):
         from .connectivity import ConnectivityStats
         if seed is None:
             seed = self.seed
-        eng, tmp = self._ppc_engine(X, R)
-        try:
+        with self._read_engine(X, R) as eng:
             counts = eng.sample_connectivity(seed, n_samples, n_trials=n_trials, hist=True, nodes=bool(nodes))
-        finally:
-            if tmp:
-                eng.close()
         return ConnectivityStats(self.N, counts, seed=seed, n_trials=n_trials)
 
     def posterior_centrality(self, q=None, T=3, direction="out", n_samples=100, seed=None, n_trials=1, top_k=10, values=False,
@@ -831,15 +818,11 @@ class VimureModel(TransformerMixin, BaseEstimator):
         from .centrality import CentralityStats, default_q
         if seed is None:
             seed = self.seed
-        eng, tmp = self._ppc_engine(X, R)
-        try:
+        with self._read_engine(X, R) as eng:
             if q is None:
                 q = default_q(self.N, eng.expected_stats()["edges"])
             counts = eng.sample_centrality(seed, n_samples, q, T, direction=direction, top_k=top_k, n_trials=n_trials, values=bool(values))
             plug_in = eng.mean_centrality(q, T, direction=direction)
-        finally:
-            if tmp:
-                eng.close()
         return CentralityStats(self.N, counts, np.broadcast_to(np.asarray(q, dtype=np.float64), (self.L,)).copy(), T, direction=direction,
                                top_k=top_k, plug_in=plug_in, seed=seed, n_trials=n_trials)
 
@@ -856,13 +839,9 @@ class VimureModel(TransformerMixin, BaseEstimator):
         from .betweenness import BetweennessStats
         if seed is None:
             seed = self.seed
-        eng, tmp = self._ppc_engine(X, R)
-        try:
+        with self._read_engine(X, R) as eng:
             counts = eng.sample_betweenness(seed, n_samples, direction=direction, top_k=top_k, n_trials=n_trials, values=bool(values))
             inferred = eng.network_betweenness(self.get_inferred_model(), direction=direction)
-        finally:
-            if tmp:
-                eng.close()
         return BetweennessStats(self.N, counts, direction=direction, top_k=top_k, inferred=inferred, seed=seed, n_trials=n_trials)
 
     def posterior_cores(self, mode="union", k=None, n_samples=100, seed=None, n_trials=1, top_k=10, values=False, X=None, R=None):
@@ -884,15 +863,11 @@ class VimureModel(TransformerMixin, BaseEstimator):
         from .cores import CoreStats
         if seed is None:
             seed = self.seed
-        eng, tmp = self._ppc_engine(X, R)
-        try:
+        with self._read_engine(X, R) as eng:
             inferred = eng.network_cores(self.get_inferred_model(), mode=mode)
             if k is None:
                 k = int(inferred.max(axis=1).min())
             counts = eng.sample_cores(seed, n_samples, mode=mode, k_min=k, top_k=top_k, n_trials=n_trials, values=bool(values))
-        finally:
-            if tmp:
-                eng.close()
         return CoreStats(self.N, counts, mode=mode, k_min=k, top_k=top_k, inferred=inferred, seed=seed, n_trials=n_trials)
 
     def posterior_predictive_check(self, n_rep=100, seed=None, params="draw", n_trials=1, by_reporter=False, X=None, R=None):
@@ -914,14 +889,10 @@ class VimureModel(TransformerMixin, BaseEstimator):
         theta, lam, eta, redraws = draw_parameters(self.gamma_shp_f, self.gamma_rte_f, self.phi_shp_f, self.phi_rte_f, self.nu_shp_f,
                                                    self.nu_rte_f, n_rep, seed, params=params)
         seed_y, seed_x = seed, seed + 2 ** 32
-        eng, tmp = self._ppc_engine(X, R)
-        try:
+        with self._read_engine(X, R) as eng:
             rep = eng.ppc_replicates(theta, lam, eta, seed_y, seed_x, n_trials=n_trials, by_reporter=by_reporter)
             obs = eng.ppc_observed(by_reporter=by_reporter)
             support = [eng.mean_poisson_size(layer=l) for l in range(self.L)]
-        finally:
-            if tmp:
-                eng.close()
         rep, rep_m = rep if by_reporter else (rep, None)
         obs, obs_m = obs if by_reporter else (obs, None)
         return PredictiveCheck(obs, rep, observed_by_reporter=obs_m, replicated_by_reporter=rep_m, support=support, seed_y=seed_y,
@@ -951,14 +922,10 @@ class VimureModel(TransformerMixin, BaseEstimator):
         heur = np.array([0.54 * float(self.G_exp_nu) - 0.01]) if np.isfinite(getattr(self, "G_exp_nu", np.nan)) else None
         dev = getattr(self, "_engine", None) if getattr(self, "_rho_f", None) is None else None
         if X is not None or dev is not None:
-            eng, tmp = self._ppc_engine(X, R)
-            try:
+            with self._read_engine(X, R) as eng:
                 res = eng.score_truth(Y_true, thresholds=thr, score=score, skip_diagonal=skip_diagonal, auc=auc)
                 hh = None if heur is None else eng.score_truth(Y_true, thresholds=heur, score=score, skip_diagonal=skip_diagonal,
                                                                auc=False, outputs=("hist",))
-            finally:
-                if tmp:
-                    eng.close()
         else:
             if R is not None:
                 raise ValueError("R= is taken with X= only")
@@ -984,12 +951,8 @@ class VimureModel(TransformerMixin, BaseEstimator):
         code, thr = self._edge_method(method, threshold)
         if layer is not None and not 0 <= int(layer) < self.L:
             raise ValueError(f"layer {layer} out of range [0, {self.L})")
-        eng, tmp = self._ppc_engine(X, R)
-        try:
+        with self._read_engine(X, R) as eng:
             res = eng.reporter_table(method=code, threshold=thr, layer=layer)
-        finally:
-            if tmp:
-                eng.close()
         rows = slice(None) if layer is None else slice(int(layer), int(layer) + 1)
         shp, rte = np.asarray(self.gamma_shp_f, dtype=np.float64)[rows], np.asarray(self.gamma_rte_f, dtype=np.float64)[rows]
         interval = None
@@ -1015,13 +978,9 @@ class VimureModel(TransformerMixin, BaseEstimator):
             raise ValueError("the model has not been fitted: call fit(..., keep_engine=True) first, or fit it and pass X=")
         if xt is None and X is not None and self.mutuality and not (isinstance(X, pd.DataFrame) or type(X).__name__ == "Graph"):
             xt = mirror_counts(X, subs)
-        eng, tmp = self._ppc_engine(X, R)
-        try:
+        with self._read_engine(X, R) as eng:
             theta, lam, eta = plug_in_tables(self, eng, estimate)
             return eng.heldout_loglik(subs, x, xt, theta=theta, lam=lam, eta=eta)
-        finally:
-            if tmp:
-                eng.close()
 
     def surprising_reports(self, top=100, threshold=None, select="both", estimate="mean", layer=None, max_rows=10_000_000, X=None,
                            R=None):
@@ -1049,17 +1008,13 @@ class VimureModel(TransformerMixin, BaseEstimator):
             raise ValueError("the model has not been fitted: call fit(..., keep_engine=True) first, or fit it and pass X=")
         if layer is not None and not 0 <= int(layer) < self.L:
             raise ValueError(f"layer {layer} out of range [0, {self.L})")
-        eng, tmp = self._ppc_engine(X, R)
-        try:
+        with self._read_engine(X, R) as eng:
             theta, lam, eta = plug_in_tables(self, eng, estimate)
             if threshold is not None:
                 return ReportScores(eng.report_scores(theta, lam, eta, float(threshold), select=sel, layer=layer), estimate=estimate)
             agg = eng.report_scores(theta, lam, eta, np.inf, select=sel, layer=layer, edges=grid_edges(), rows=False, by_reporter=False)
             thr, _ = threshold_for_top(agg["hist"], agg["edges"], top, sel, max_rows=max_rows)
             res = eng.report_scores(theta, lam, eta, thr, select=sel, layer=layer)
-        finally:
-            if tmp:
-                eng.close()
         res.update(top_rows(res, top))
         res["hist"], res["edges"] = agg["hist"], agg["edges"]
         return ReportScores(res, estimate=estimate, top=int(top))
@@ -1105,8 +1060,7 @@ class VimureModel(TransformerMixin, BaseEstimator):
         if layer is not None and not 0 <= int(layer) < self.L:
             raise ValueError(f"layer {layer} out of range [0, {self.L})")
         tabs = self.influence_tables()
-        eng, tmp = self._ppc_engine(X, R)
-        try:
+        with self._read_engine(X, R) as eng:
             if top is None:
                 min_tv = np.inf if min_shift is None else float(min_shift)
                 return ReporterInfluence(eng.reporter_influence(*tabs, method=code, threshold=thr, select=sel, min_tv=min_tv, layer=layer))
@@ -1114,9 +1068,6 @@ class VimureModel(TransformerMixin, BaseEstimator):
                                          rows=False)
             min_tv, _ = min_tv_for_top(agg["hist"], agg["edges"], top, max_rows=max_rows)
             res = eng.reporter_influence(*tabs, method=code, threshold=thr, select=0, min_tv=min_tv, layer=layer)
-        finally:
-            if tmp:
-                eng.close()
         res.update(top_rows(res, top))
         res["hist"], res["edges"] = agg["hist"], agg["edges"]
         return ReporterInfluence(res, top=int(top))
