@@ -125,7 +125,10 @@ def test_values_against_the_restatement_coo_handle():
 @pytest.mark.parametrize("N", [5, 63, 64, 65, 129])
 def test_word_boundaries(N):
     """L = 2, K = 3 and W = ceil(N / 64) = 1, 1, 1, 2, 3 words per bit row; rho puts 1 - 3 / N on "no tie" and splits the rest:
-    above the percolation threshold, where shortest paths are long and many pairs have several."""
+    above the percolation threshold, where shortest paths are long and many pairs have several.  These are the boundaries of the
+    first three words only: one or two lanes per row, one node per thread.  The wider shapes -- 8 and 16 lanes, a second trip of
+    the word stride behind them, three to five nodes per thread on the rungs 4 and 8 -- are held in
+    tests/test_hip_graph_shapes.py."""
     L, K, S = 2, 3, 8
     rho = np.empty((L, N, N, K))
     rho[..., 0] = 1.0 - 3.0 / N

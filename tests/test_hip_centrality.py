@@ -107,7 +107,9 @@ def _coo_engine_with_rho(rho, M=2):
 @pytest.mark.parametrize("N", [5, 63, 64, 65, 129])
 def test_word_boundaries(N):
     """L = 2, K = 3 and W = ceil(N / 64) = 1, 1, 1, 2, 3 words per bit row; rho puts 1 - 1.5 / N on "no tie" and splits the rest:
-    the percolation threshold, where few nodes have distinct walk counts and many tie."""
+    the percolation threshold, where few nodes have distinct walk counts and many tie.  These are the boundaries of the first
+    three words only: one or two lanes per row, one node per thread.  The wider shapes -- 8 and 16 lanes, a second trip of the word
+    stride behind them, three to five nodes per thread on the rungs 4 and 8 -- are held in tests/test_hip_graph_shapes.py."""
     L, K, S = 2, 3, 8
     rho = np.empty((L, N, N, K))
     rho[..., 0] = 1.0 - 1.5 / N

@@ -80,7 +80,10 @@ def _engine_with_rho(rho, seed, M=4):
 @pytest.mark.parametrize("N", [5, 63, 64, 65, 129])
 def test_word_and_source_block_boundaries(N):
     """L = 2, K = 3 and W = ceil(N / 64) = 1, 1, 1, 2, 3 words per bit row and source blocks per layer; rho puts 1 - 1.5 / N on
-    "no tie" and splits the rest: the percolation threshold, where components, reach and path lengths all vary."""
+    "no tie" and splits the rest: the percolation threshold, where components, reach and path lengths all vary.  These are the
+    boundaries of the first three words only: one or two lanes per row, one node per thread.  The wider shapes -- 8, 16 and 32
+    lanes, a second trip of the word stride, three to eight nodes per thread, the node bound -- are held in
+    tests/test_hip_graph_shapes.py."""
     L, K, S = 2, 3, 8
     rho = np.empty((L, N, N, K))
     rho[..., 0] = 1.0 - 1.5 / N

@@ -100,7 +100,9 @@ def _check_networks(N, Ys, k_min=1):
 @pytest.mark.parametrize("N", [63, 64, 65, 129, 257])
 def test_word_boundaries(N):
     """W = ceil(N / 64) = 1, 1, 2, 3, 5 words per bit row, a thread owns one or two nodes: random digraphs with 2 and with N / 4
-    ties per node, random diagonal entries, a planted clique that holds the last node."""
+    ties per node, random diagonal entries, a planted clique that holds the last node.  These are the boundaries of the first
+    five words only: one to four lanes per row.  8 and 16 lanes, a second trip of the word stride behind them and three to five
+    nodes per thread are held in tests/test_hip_graph_shapes.py."""
     sparse, dense = random_planted(N, 2.0, 6, N), random_planted(N, N / 4.0, 3, 2 * N)
     assert sparse.diagonal().any() and dense.diagonal().any()
     assert core_peel(adjacency(dense), "union")[0].max() >= N // 4 and core_peel(adjacency(sparse), "union")[0][N - 1] == 5

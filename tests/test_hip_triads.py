@@ -76,7 +76,10 @@ def _random_engine(N, seed, L=2, M=4, K=3):
 @pytest.mark.parametrize("N", [5, 63, 64, 65, 129])
 def test_word_boundaries(N):
     """L = 2, K = 3 and W = ceil(N / 64) = 1, 1, 1, 2, 3 words per bit row: one partial word, one short of a word, an exact
-    word, one spare bit, a third word holding one bit.  The samples of a random state carry edges on their diagonal."""
+    word, one spare bit, a third word holding one bit.  The samples of a random state carry edges on their diagonal.  These are
+    the boundaries of the first three words only: the register path with one and two words, two lanes striding three.  The
+    register path with 4 to 32 words, 8 to 64 lanes with a second trip, more than one block of 32 words and the second trip of
+    the degree loop are held in tests/test_hip_graph_shapes.py."""
     eng = _random_engine(N, 100 + N)
     try:
         Ys = np.asarray([eng.sample(7 + s) for s in range(8)])
