@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Randomised parity sweep (GPU box): random shapes, K, mutuality, mask kinds, count ranges and engine shapes against the
-coordinate-list oracle -- three sweeps with the ELBO each, state compared at the end.  `python tools/fuzz_parity.py [n] [seed] [wide|long|range|seq]`.
+coordinate-list oracle -- three sweeps with the ELBO each, state compared at the end.  `python tools/fuzz_parity.py [n] [seed] [wide|long|range|seq] [plain]`.
+plain (with the standard family, wide or long): some of the three sweeps without the ELBO, consecutive ones as one step(n) or not.
 long: many reports per tie with mirrored counts (the sweep's general body, ties sorted by the second key, level-0 rounds), two passes
 and far lists forced at random.
 range: the rho update where the reference's raw exponentials leave the range of a double (tests/exp_range_util.py: all-zero rows,
@@ -18,8 +19,30 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 PRI = (0.1, 0.1, 10.0, 10.0, 0.5, 1.0)
 
 
-def one(case, g, wide=False, long_=False):
-    """wide: the inputs beyond the specialised kernels -- K up to 70 (the reference's default K = max(X) + 1 gives such K) and counts
+def plain_schedule(case):
+    """The calls of a `plain` case: [(sweeps, want_elbo)], three sweeps in all.  Its own generator (the case draw stays as it is):
+    which sweeps evaluate the ELBO -- at least one does not -- and whether consecutive plain sweeps go as one step(n), whose inner
+    rhos are never written."""
+    gp = np.random.RandomState(1000003 + case)
+    while True:
+        flags = [bool(gp.rand() < 0.5) for _ in range(3)]
+        if not all(flags):
+            break
+    group = bool(gp.rand() < 0.5)
+    calls = []
+    for f in flags:
+        if not f and group and calls and not calls[-1][1]:
+            calls[-1] = (calls[-1][0] + 1, False)
+        else:
+            calls.append((1, f))
+    return calls
+
+
+def one(case, g, wide=False, long_=False, plain=False, oracle_only=False):
+    """plain: the three sweeps follow `plain_schedule(case)` -- ELBO sweeps compare their ELBO, plain ones nothing; after the last
+    sweep the stand-alone ELBO and the state are compared.  A case whose oracle ELBO is NaN at any sweep is no plain case: None.
+    oracle_only (no GPU): the case draw and the oracle alone -- True, or None for such a case (how the committed seeds were chosen).
+    wide: the inputs beyond the specialised kernels -- K up to 70 (the reference's default K = max(X) + 1 gives such K) and counts
     beyond 11 bits / table rows beyond 2^20 (two-word entries) -- which the general kernels (csrc/sweep_gen.hip) take."""
     from oracle import cavi_coo
     from vimure_amd import CaviEngine
@@ -95,6 +118,18 @@ def one(case, g, wide=False, long_=False):
         use_coo = M <= 8192 and (xmax > 255 or (fmt != "dense" and g.rand() < 0.4))   # the coordinate-list entry point (vmr_create_coo)
         if use_coo:
             desc += " [coo]"
+        if oracle_only:
+            sx = np.nonzero(X)
+            gs = np.random.RandomState(case)
+            pr = gs.rand(L, N, N, K) + 0.05
+            pr /= pr.sum(-1, keepdims=True)
+            init = (0.5 + gs.rand(L, M), 0.5 + gs.rand(L, M), 1 + gs.rand(L, K), 1 + gs.rand(L, K), 0.7, 1.0 + float(X.sum(dtype=np.int64)), pr)
+            c = cavi_coo.CooRef((sx, X[sx]), None if R is None else np.nonzero(R), (L, N, N, M), K, mut, PRI, *init)
+            for it in range(3):
+                c.cavi_step()
+                if np.isnan(c.elbo()):
+                    return None
+            return True
         try:
             if use_coo:
                 sx0 = np.nonzero(X)
@@ -114,7 +149,34 @@ def one(case, g, wide=False, long_=False):
         eng.set_priors(*PRI)
         eng.set_state(*init)
         ok = True
-        for it in range(3):
+        if plain:
+            desc += f" plain={plain_schedule(case)}"
+            want_e, nan_at = [], None      # the oracle first: its ELBO after every sweep decides whether this is a plain case
+            for n, want in plain_schedule(case):
+                for _ in range(n):
+                    c.cavi_step()
+                    ec = c.elbo()
+                    nan_at = len(want_e) + 1 if (np.isnan(ec) and nan_at is None) else nan_at
+                    want_e.append(ec)
+            if nan_at is not None:
+                print(desc, f"-> no plain case: the oracle's ELBO is NaN at sweep {nan_at}", flush=True)
+                eng.close()
+                return None
+            it = 0
+            for n, want in plain_schedule(case):
+                it += n
+                ec = want_e[it - 1]
+                e = eng.step(n, want_elbo=want)
+                if want and not abs(e - ec) <= 1e-9 * max(1.0, abs(ec)):
+                    ok = False
+                    print(desc, f"-> ELBO mismatch at sweep {it}: {e} vs {ec}", flush=True)
+                    break
+            if ok:
+                e = eng.elbo()
+                if not abs(e - ec) <= 1e-9 * max(1.0, abs(ec)):
+                    ok = False
+                    print(desc, f"-> stand-alone ELBO mismatch after sweep {it}: {e} vs {ec}", flush=True)
+        for it in range(0 if plain else 3):
             c.cavi_step()
             ec = c.elbo()
             try:
@@ -284,7 +346,8 @@ def main():
     seq = len(sys.argv) > 3 and sys.argv[3] == "seq"
     g = np.random.RandomState(seed)
     t0 = time.time()
-    res = [(one_seq(i, g) if seq else one_range(i, g) if range_ else one(i, g, wide, long_)) for i in range(n)]
+    plain = "plain" in sys.argv[3:]
+    res = [(one_seq(i, g) if seq else one_range(i, g) if range_ else one(i, g, wide, long_, plain)) for i in range(n)]
     bad = sum(1 for r in res if r is not None and not r)
     print(f"{n} cases, {bad} failed, {sum(1 for r in res if r is None)} skipped, {time.time() - t0:.0f} s", flush=True)
     sys.exit(1 if bad else 0)
