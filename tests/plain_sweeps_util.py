@@ -9,7 +9,7 @@ smallest handle of each regime, `SCHEDULES` the call orders that expose what a p
 them call by call on an oracle with the rules of `tests.call_sequence_util.SeqModel` (the ELBO's nu factor is that model's).
 
 `shape_of` restates `sl_smem`, the shrink loop of `sl_shape`, `sl_tpb_max` / `sl_wpe` (vimure_amd/csrc/sweep_sl.h) and the level
-choice of `create_tail` (`best`, `waves`; vimure_amd/csrc/vimure_hip.hip) from their header comments and formulas, so that a case
+choice of `create_tail` (`best`, `waves`; vimure_amd/csrc/create.hip) from their header comments and formulas, so that a case
 can say on the host which levels each variant keeps in LDS.
 
 tests/test_plain_sweeps_host.py holds every case to its class, the two oracles to each other and shows three forgetful models

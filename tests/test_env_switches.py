@@ -28,14 +28,14 @@ def _read_opts_body(src):
 def test_getenv_only_in_read_opts():
     srcs = _sources()
     hits = [(name, src.count("getenv(")) for name, src in srcs.items() if "getenv(" in src]
-    assert [name for name, _ in hits] == ["vimure_hip.hip"], hits
-    src = srcs["vimure_hip.hip"]
+    assert [name for name, _ in hits] == ["create.hip"], hits
+    src = srcs["create.hip"]
     a, b = _read_opts_body(src)
     assert "getenv(" not in src[:a] + src[b:]
 
 
 def test_every_switch_has_a_row_in_the_integration_table():
-    src = _sources()["vimure_hip.hip"]
+    src = _sources()["create.hip"]
     a, b = _read_opts_body(src)
     names = set(re.findall(r'"(VMR_[A-Z0-9_]+)"', src[a:b]))
     assert len(names) >= 20, names

@@ -1,6 +1,6 @@
-// Accuracy of the rho pass' table-driven exp / log (exp_tab, log_tab of vimure_hip.hip, compiled from that file) against
-// the host's libm in long double.  Build: hipcc -O3 --offload-arch=gfx950 -DVMR_DEV -Iinclude tools/micro/tab_math_accuracy.hip
-#include "../../vimure_amd/csrc/vimure_hip.hip"
+// Accuracy of the rho pass' table-driven exp / log (exp_tab, log_tab of vmr_internal.h, compiled from that file) against
+// the host's libm in long double.  Build: hipcc -O3 --offload-arch=gfx950 -Iinclude tools/micro/tab_math_accuracy.hip
+#include "../../vimure_amd/csrc/vmr_internal.h"
 #include <stdio.h>
 __global__ void k_tab(const double* x, double* ye, double* yl, int n) {
   __shared__ double xt[64], lt[256];

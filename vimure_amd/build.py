@@ -3,6 +3,7 @@
 The library is a handful of translation units (vimure_amd/csrc): objects are compiled in parallel into csrc/_obj and only
 those whose source or headers changed are rebuilt; the sweep kernel is one object per number of categories K (-DVMR_K).
 `VMR_DEV=1` builds K = 2 only (fast iteration on a kernel)."""
+import glob
 import os
 import subprocess
 from concurrent.futures import ThreadPoolExecutor
@@ -15,11 +16,7 @@ LIB = os.environ.get("VMR_LIB_OUT", os.path.join(HERE, "libvimure_hip.so"))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 HOST_SRC = os.path.join(CSRC, "host_init.c")
 HOST_LIB = os.path.join(HERE, "libvimure_host.so")
-HEADERS = [os.path.join(CSRC, "vmr_internal.h"), os.path.join(CSRC, "sweep_sl.h"), os.path.join(CSRC, "sweep_gen.h"),
-           os.path.join(CSRC, "sample_draw.h"), os.path.join(CSRC, "report_draw.h"), os.path.join(CSRC, "ppc_layer.h"), os.path.join(CSRC, "rho_row.h"),
-           os.path.join(CSRC, "report_lik.h"), os.path.join(CSRC, "read_side.h"), os.path.join(CSRC, "sampled_side.h"), os.path.join(CSRC, "node_fold.h"),
-           os.path.join(CSRC, "sl_balance.h"),
-           os.path.join(ROOT, "include", "vimure_hip.h")]
+HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(ROOT, "include", "vimure_hip.h")]   # every object depends on every header
 KS = (2, 3, 4, 5, 6, 7, 8)
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
 
@@ -27,7 +24,10 @@ FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-I" + os.path.j
 def units(dev=False):
     """(object name, source, extra flags) of every translation unit."""
     extra = ["-DVMR_DEV"] if dev else []
-    u = [("vimure_hip", os.path.join(CSRC, "vimure_hip.hip"), extra),
+    u = [("vimure_hip", os.path.join(CSRC, "vimure_hip.hip"), extra),   # the engine proper: finalize kernels, launch logic, fit loops, the API
+         ("sweep_tiles", os.path.join(CSRC, "sweep_tiles.hip"), extra),  # the dense tile path: k_hist, k_rho, geometry and LDS sizes
+         ("create", os.path.join(CSRC, "create.hip"), extra),          # vmr_create, the shared tail of both creators, vmr_destroy
+         ("create_coo", os.path.join(CSRC, "create_coo.hip"), extra),  # vmr_create_coo: coordinate lists straight to report lists
          ("sorted_lists", os.path.join(CSRC, "sorted_lists.hip"), extra),
          ("sweep_gen", os.path.join(CSRC, "sweep_gen.hip"), extra),   # the general kernels: any K, wide entries
          ("generate", os.path.join(CSRC, "generate.hip"), extra),     # the synthetic generators on the device
@@ -90,7 +90,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.run(cmd, check=True)
-    workers = max(1, min(len(todo), int(os.environ.get("VMR_BUILD_JOBS", os.cpu_count() or 1))))
+    jobs = os.environ.get("VMR_BUILD_JOBS") or os.environ.get("MAX_JOBS") or os.cpu_count() or 1   # (a shared machine: its CPU count is not ours)
+    workers = max(1, min(len(todo), int(jobs)))
     if todo:
         with ThreadPoolExecutor(max_workers=workers) as ex:
             list(ex.map(run, todo))

@@ -147,6 +147,15 @@ typedef int (*sl_launch_batch_fn)(vmr_ctx* h, hipStream_t st, int mode, int allf
                                   int tpb, size_t smem);
 sl_launch_batch_fn vmr_sl_batch_launcher(int K);
 
+// vimure_hip.hip
+#define SP_LDS_MAX (160 * 1024)
+// Launch shape of one sweep over the sorted lists: the handle's block size and table levels, shrunk until the workgroup fits in LDS
+SlShape sl_shape(const vmr_ctx* h, bool update, bool elbo, bool hist);
+// the handle's arrays as the arguments of one launch of that shape (do_hist, sum_a: SlArgs)
+SlArgs sl_args(const vmr_ctx* h, const SlShape& sh, int do_hist, int sum_a = 0);
+// launches through the K's object; VMR_EINVAL when this build holds no kernel for the handle's K
+int sl_launch(vmr_ctx* h, int mode, const SlShape& sh, SlArgs& a);
+
 // sorted_lists.hip
 // Builds perm, rs, E (and ebase, n_slots) from tie-major entries.  rp [L][T+1]: per-tie report counts (overwritten by their
 // exclusive scan); nl[l]: reports of layer l; etmp_all: every layer's entries tie-major (layer l at offset sum nl[<l]) or null,

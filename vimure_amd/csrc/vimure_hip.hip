@@ -2,411 +2,38 @@
 //
 // Implements the reference's hot path (latentnetworks/vimure, src/python/vimure/model.py:
 // _update_CAVI :623-660, _update_cache :662-696, _update_gamma :698-727, _update_phi :729-761,
-// _update_rho :763-818, _update_nu :820-830, __ELBO :948-1019) as FP64 streaming passes over a
-// dense uint8 report tensor X[L,N,N,Mp] and a bit-packed reporter mask R, behind the C-ABI of
-// include/vimure_hip.h.  Design notes, data layout and byte accounting: DESIGN.md.
+// _update_rho :763-818, _update_nu :820-830, __ELBO :948-1019) behind the C-ABI of include/vimure_hip.h.
+// Design notes, data layout and byte accounting: DESIGN.md.
 //
-// One sweep touches X once:  k_gamma_mask (partial mask rows) -> k_fin_gamma -> k_rho -> k_fin_rho.
-//   k_rho          "tile-pair" sweep over X: a workgroup stages the (I,J) tile of ties and its mirror (J,I) in
-//                  LDS so that X[l,j,i,m] (the reference's data_T_vals) is an LDS byte read; the non-zero counts
-//                  of the pair are compacted into wave-local queues and walked twice: per-tie sums for the rho
-//                  update, then the sufficient statistics H[l,y,m,k] of the new rho (and the ELBO data terms).
-//   k_hist         the same sweep building H from the current rho (start of a realisation).
+// This file is the engine proper: the set-state kernels, the mask sums, the finalize kernels, the launch logic of a sweep
+// (launch_hist / launch_gamma / launch_phi / launch_rho), step_n, the fit loops, the lockstep batch, and the state, read-out
+// and profile API.  What a sweep launches lives in units of its own:
+//   sweep_sl.hip     the sweep kernel over the sorted report lists, one object per K (sweep_sl.h)     -- the default format
+//   sweep_gen.hip    the general kernels: any K, wide entries (sweep_gen.h)
+//   sweep_tiles.hip  the dense tile path: k_hist, k_rho, the geometry and the LDS sizes (sweep_tiles.h)
+// and what makes a handle does too:
+//   create.hip       vmr_create, the shared tail of both creators, vmr_destroy (create.h)
+//   create_coo.hip   vmr_create_coo
+//   sorted_lists.hip the sorted report lists and the permutation kernels of the boundary functions
+//
+// One sweep:  mask sums A -> k_fin_gamma -> the rho pass (which rebuilds the statistics H) -> k_fin_rho.
 //   k_gamma_mask   A[l,m,k] = sum_ij R rho: mask words become the EXEC mask of K v_add_f64 (lane <-> reporter).
-//   k_fin_*        one workgroup per layer: gamma, phi, nu from H and A, the Gamma expectations
-//                  (digamma/log/exp), ELBO assembly -- no host round trip inside a sweep.
+//   k_mask_lists   the same sums from the mask lists of partial rows that hold few reporters.
+//   k_fin_*        gamma, phi, nu from H and A, the Gamma expectations (digamma/log/exp), ELBO assembly -- no host round
+//                  trip inside a sweep.
+//   k_far_hist     the statistics of the reports of the levels beyond the LDS ones (Geo::farl).
 #include "vmr_internal.h"
 #include "sweep_sl.h"
 #include "sweep_gen.h"
+#include "sweep_tiles.h"
+#include "create.h"
 #include "sample_draw.h"
 
 thread_local std::string g_create_err;
 
-
-
-// Non-zero-byte flags of a 16-byte chunk, 16 bits spread over a dword: bit 8*b + i (+4 when hi) is set
-// iff byte b of dword i is non-zero.  Two chunks (hi = 0/1) share one dword, four one 64-bit word.
-template <int SH>   // SH = 0 or 4
-__device__ __forceinline__ unsigned nz_flags16(uint4 v) {
-  const unsigned M = 0x7f7f7f7fu;
-  unsigned t0 = ((v.x & M) + M) | v.x, t1 = ((v.y & M) + M) | v.y;
-  unsigned t2 = ((v.z & M) + M) | v.z, t3 = ((v.w & M) + M) | v.w;   // bit 7 of each byte = byte != 0
-  unsigned f = (t0 >> (7 - SH)) & (0x01010101u << SH);
-  f |= (t1 >> (6 - SH)) & (0x02020202u << SH);
-  f |= (t2 >> (5 - SH)) & (0x04040404u << SH);
-  f |= (t3 >> (4 - SH)) & (0x08080808u << SH);
-  return f;
-}
-// flag position (0..63 in a 64-bit word of four chunks) -> chunk-in-word (0..3) and byte-in-chunk (0..15)
-__device__ __forceinline__ void flag_pos(int bit, int& chunk, int& byte) {
-  const int lo = bit & 31;                       // position inside the dword of a chunk pair
-  chunk = ((bit >> 5) << 1) | ((lo >> 2) & 1);   // dword half, then the +4 flag
-  byte = ((lo & 3) << 2) | (lo >> 3);            // dword i = lo & 3, byte b = lo >> 3  ->  4*i + b
-}
-
-// decode pair index p -> (I,J), I <= J, row-major over the upper triangle of an nb x nb grid
-__device__ __forceinline__ void pair_decode(long long p, int nb, int& I, int& J) {
-  double d = (2.0 * nb + 1.0);
-  long long i = (long long)((d - sqrt(d * d - 8.0 * (double)p)) * 0.5);
-  if (i < 0) i = 0;
-  if (i > nb - 1) i = nb - 1;
-  auto off = [&](long long r) { return r * nb - r * (r - 1) / 2; };
-  while (i > 0 && off(i) > p) --i;
-  while (i < nb - 1 && off(i + 1) <= p) ++i;
-  I = (int)i;
-  J = (int)(i + (p - off(i)));
-}
-
-// Register-staged stream of tile pairs.  The 16-B chunks a thread stages are the same slots of
-// every tile pair, so their byte offsets from the two sub-tile bases (I,J) / (J,I) and their LDS
-// offsets are computed once; fetch() is one saddr+voffset global_load_dwordx4 per slot and the
-// loads stay in flight while the previous tile pair is processed.  Reads never need a bounds
-// check: X is allocated with b*N+b rows of slack, and rows outside the network are never used.
-template <int PF>
-struct TileStream {
-  uint4 buf[PF];
-  unsigned goff[PF];
-  unsigned loff[PF];
-  unsigned valid, second;   // bit u: slot exists / belongs to the mirrored sub-tile
-  __device__ __forceinline__ void init(const Geo& g) {
-    valid = 0; second = 0;
-    const int bb = g.b * g.b;
-#pragma unroll
-    for (int u = 0; u < PF; ++u) {
-      int q = threadIdx.x + u * TPB;
-      int tau = q / g.nchunk, c = q - tau * g.nchunk;
-      bool ok = tau < g.nt, sec = tau >= bb;
-      int v = sec ? tau - bb : tau;
-      int p = v >> g.lb, qq = v & (g.b - 1);
-      goff[u] = ok ? (unsigned)((p * g.N + qq) * g.Mp + c * 16) : 0u;
-      loff[u] = ok ? (unsigned)(tau * g.stride + c * 16) : 0u;
-      valid |= (ok ? 1u : 0u) << u;
-      second |= (sec ? 1u : 0u) << u;
-    }
-  }
-  __device__ __forceinline__ void fetch(const uint8_t* __restrict__ Xl, const Geo& g, int I0, int J0) {
-    const uint8_t* baseA = Xl + ((size_t)I0 * g.N + J0) * g.Mp;
-    const uint8_t* baseB = Xl + ((size_t)J0 * g.N + I0) * g.Mp;
-#pragma unroll
-    for (int u = 0; u < PF; ++u) {
-      // (assign every slot unconditionally: a conditionally written array would live in scratch)
-      uint4 v = make_uint4(0, 0, 0, 0);
-      if ((valid >> u) & 1u) {
-        const uint8_t* base = ((second >> u) & 1u) ? baseB : baseA;
-        v = *reinterpret_cast<const uint4*>(base + goff[u]);
-      }
-      buf[u] = v;
-    }
-  }
-  __device__ __forceinline__ void store(unsigned char* xt) {
-#pragma unroll
-    for (int u = 0; u < PF; ++u)
-      if ((valid >> u) & 1u) *reinterpret_cast<uint4*>(xt + loff[u]) = buf[u];
-  }
-};
-
-// The same staging for the tile pair's mask rows (64-bit words), 3 words per thread at most.
-struct MaskStream {
-  uint64_t buf[3];
-  unsigned goff[3];
-  unsigned valid, second;
-  __device__ __forceinline__ void init(const Geo& g) {
-    valid = 0; second = 0;
-    const int bb = g.b * g.b;
-#pragma unroll
-    for (int u = 0; u < 3; ++u) {
-      int q = threadIdx.x + u * TPB;
-      int tau = q / g.W, w = q - tau * g.W;
-      bool ok = tau < g.nt, sec = tau >= bb;
-      int v = sec ? tau - bb : tau;
-      int p = v >> g.lb, qq = v & (g.b - 1);
-      goff[u] = ok ? (unsigned)((p * g.N + qq) * g.W + w) : 0u;
-      valid |= (ok ? 1u : 0u) << u;
-      second |= (sec ? 1u : 0u) << u;
-    }
-  }
-  __device__ __forceinline__ void fetch(const uint64_t* __restrict__ Rl, const Geo& g, int I0, int J0) {
-    const uint64_t* baseA = Rl + ((size_t)I0 * g.N + J0) * g.W;
-    const uint64_t* baseB = Rl + ((size_t)J0 * g.N + I0) * g.W;
-#pragma unroll
-    for (int u = 0; u < 3; ++u) {
-      uint64_t v = 0ull;
-      if ((valid >> u) & 1u) v = (((second >> u) & 1u) ? baseB : baseA)[goff[u]];
-      buf[u] = v;
-    }
-  }
-  __device__ __forceinline__ void store(uint64_t* rw) {
-#pragma unroll
-    for (int u = 0; u < 3; ++u)
-      if ((valid >> u) & 1u) rw[threadIdx.x + u * TPB] = buf[u];
-  }
-};
-
-// Weights of the cache refresh (model.py:685-693) without a divide per report:
-//   w1 = z1/(z1 + z2) = 1/(1 + c y),  c[m][k] = G_nu / (G_theta[m] G_lambda[k])  (LDS table, built per launch)
-//   w2 = z2/(z1 + z2) = c y w1.
-// y = 0 gives exactly 1; a z1 that underflows to 0 gives c = inf and w1 = 0 (the reference's den==0 -> 1 rule).
-template <int K>
-__device__ __forceinline__ void build_ct(double* ct, const double* Gth, const double (&Gla)[K], double gnu, int Mp) {
-  for (int m = threadIdx.x; m < Mp; m += TPB) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      double z1 = Gth[m] * Gla[k];
-      ct[(size_t)m * K + k] = (z1 == 0.0) ? (double)INFINITY : gnu / z1;
-    }
-  }
-}
-template <int K>
-__device__ __forceinline__ void weights(double (&w)[K], double (&cy)[K], const double* ct, int m, unsigned y) {
-  const double dy = (double)y;
-  const double* p = ct + (size_t)m * K;
-  if (K == 2) {   // one reciprocal for both categories: 1/a0 = a1/(a0 a1)
-    const double c0 = p[0], c1 = p[1];
-    if (c0 < (double)INFINITY && c1 < (double)INFINITY) {
-      cy[0] = c0 * dy; cy[1] = c1 * dy;
-      const double a0 = 1.0 + cy[0], a1 = 1.0 + cy[1];
-      const double r = fast_rcp(a0 * a1);
-      w[0] = a1 * r; w[1] = a0 * r;   // y = 0: a0 = a1 = 1 and r = 1 exactly
-      return;
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    const double c = p[k];
-    cy[k] = c * dy;
-    const double r = fast_rcp(1.0 + cy[k]);
-    w[k] = (y == 0) ? ((c < (double)INFINITY) ? 1.0 : 0.0) : r;
-  }
-}
-
-// the same weights from cb = G_nu / G_theta_m and 1 / G_lambda_k (report lists: one table entry per reporter)
-template <int K>
-__device__ __forceinline__ void weights_cb(double (&w)[K], double cb, const double (&iGla)[K], unsigned y) {
-  const double dy = (double)y;
-  double c[K];
-#pragma unroll
-  for (int k = 0; k < K; ++k) c[k] = cb * iGla[k];
-  if (K == 2) {   // one reciprocal for both categories: 1/a0 = a1/(a0 a1)
-    if (c[0] < (double)INFINITY && c[1] < (double)INFINITY) {
-      const double a0 = 1.0 + c[0] * dy, a1 = 1.0 + c[1] * dy;
-      const double r = fast_rcp(a0 * a1);
-      w[0] = a1 * r; w[1] = a0 * r;   // y = 0: a0 = a1 = 1 and r = 1 exactly
-      return;
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    const double r = fast_rcp(1.0 + c[k] * dy);
-    w[k] = (y == 0) ? ((c[k] < (double)INFINITY) ? 1.0 : 0.0) : r;
-  }
-}
-
-
-// Per-tie accumulators a report may feed (reduced over the wave when a heavy share is processed cooperatively)
-struct NoAcc {
-  __device__ __forceinline__ void zero() {}
-  __device__ __forceinline__ void wave_reduce() {}
-};
-
-#define QCAP 6   // a lane queues at most this many non-zero dwords; larger shares are "heavy"
-
-// The non-zero counts of the tile rows owned by one wave.  Lane (tau, s) owns the 16-B chunks {s, s+S, ..}
-// of row tau.
-//   build(): phase 1 (no divergence): one flag per DWORD of the lane's chunks (v_min_u32 + v_lshl_or); then the
-//            flags of all 64 lanes are compacted into a wave-local LDS queue of (lane, dword) entries
-//            (ballot/mbcnt prefix sums) -- without it a wave runs max-over-lanes(non-zeros) trips at ~30 % lane
-//            utilisation.  Heavy shares (a true tie is reported by most reporters: ~100 non-zeros in a row whose
-//            neighbours have 2-5) are not queued.
-//   walk():  every lane takes queue entries; f(tau_e, m, x, acc) handles one report of tie slot tau_e,
-//            commit(tau_e, acc) adds acc to that tie's sums.  Heavy shares: all lanes take one dword each, sums
-//            come back through a wave reduction.  walk() may be called several times per build().
-// Both must be called by every lane of the wave (act = false for lanes without a tie).
-struct TileScan {
-  unsigned lo, hi, tot;
-  bool heavy, simple;
-
-  __device__ __forceinline__ void build(const unsigned char* xt, const Geo& g, int tau, int s, bool act,
-                                        unsigned short* wq) {
-    const int S = g.S, nchunk = g.nchunk;
-    const unsigned char* row = xt + tau * g.stride;
-    lo = 0; hi = 0; tot = 0; heavy = false;
-    simple = (nchunk + S - 1) / S > 12;   // huge M (b = 1): plain chunk-by-chunk walk, nothing to build
-    if (simple) return;
-    // phase 1: bit 4*j + i <-> dword i of chunk s + j*S   (lo: chunks 0..7, hi: chunks 8..11)
-    if (act) {
-#pragma unroll
-      for (int j = 0; j < 12; ++j) {
-        if (j * S < nchunk) {   // wave-uniform
-          const int c = s + j * S;
-          const int cl = c < nchunk ? c : nchunk - 1;
-          const uint4 v = *reinterpret_cast<const uint4*>(row + cl * 16);
-          unsigned f4 = min(v.x, 1u) | (min(v.y, 1u) << 1) | (min(v.z, 1u) << 2) | (min(v.w, 1u) << 3);
-          f4 = c < nchunk ? f4 : 0u;
-          if (j < 8) lo |= f4 << (4 * j); else hi |= f4 << (4 * (j - 8));
-        }
-      }
-    }
-    const int cnt = __popc(lo) + __popc(hi);   // non-zero dwords of the share
-    if (g.dbg & 4) { lo = (cnt == 0x7fffffff) ? 1u : 0u; hi = 0; return; }   // timing experiment: phase 1 only
-    const int lane = threadIdx.x & 63;
-    heavy = cnt > QCAP;
-    const unsigned cl_ = heavy ? 0u : (unsigned)cnt;   // 0..QCAP (< 8)
-    unsigned pre = 0;
-#pragma unroll
-    for (int b = 0; b < 3; ++b) {
-      const uint64_t bal = __ballot((cl_ >> b) & 1u);
-      pre += __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u)) << b;
-      tot += (unsigned)__popcll(bal) << b;
-    }
-    if (!heavy) {
-      unsigned l2 = lo, h2 = hi, j = pre;
-      while (l2 | h2) {
-        int p;
-        if (l2) { p = __builtin_ctz(l2); l2 &= l2 - 1; } else { p = 32 + __builtin_ctz(h2); h2 &= h2 - 1; }
-        wq[j++] = (unsigned short)((lane << 6) | p);
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
-  }
-
-  template <class TieAcc, class F, class C>
-  __device__ __forceinline__ void walk(const unsigned char* xt, const Geo& g, int tau, int s, bool act,
-                                       const unsigned short* wq, F&& f, C&& commit) const {
-    const int S = g.S, nchunk = g.nchunk;
-    if (simple) {
-      if (!act) return;
-      const unsigned char* row = xt + tau * g.stride;
-      TieAcc a;
-      a.zero();
-      for (int c = s; c < nchunk; c += S) {
-        unsigned nzm = nz_flags16<0>(*reinterpret_cast<const uint4*>(row + c * 16));
-        while (nzm) {
-          int bit = __builtin_ctz(nzm), ch, by;
-          nzm &= nzm - 1;
-          flag_pos(bit, ch, by);
-          f(tau, c * 16 + by, (unsigned)row[c * 16 + by], a);
-        }
-      }
-      commit(tau, a);
-      return;
-    }
-    const int lane = threadIdx.x & 63;
-    const int wave_base = threadIdx.x & ~63;
-    for (unsigned e0 = 0; e0 < tot; e0 += 64) {   // wave-uniform trip count
-      const unsigned e = e0 + lane;
-      if (e < tot) {
-        const unsigned ent = wq[e];
-        const int ls = ent >> 6, p = ent & 63;
-        const int tau_e = (wave_base | ls) >> g.lS, s_e = ls & (S - 1);
-        const int off = (s_e + (p >> 2) * S) * 16 + (p & 3) * 4;
-        unsigned d = *reinterpret_cast<const unsigned*>(xt + tau_e * g.stride + off);
-        TieAcc a;
-        a.zero();
-        while (d) {
-          const int sh = __builtin_ctz(d) & ~7;
-          const unsigned x = (d >> sh) & 0xffu;
-          d &= ~(0xffu << sh);
-          f(tau_e, off + (sh >> 3), x, a);
-        }
-        commit(tau_e, a);
-      }
-    }
-    // heavy shares: lane p < 48 takes dword p of the share
-    uint64_t hm = __ballot(heavy);
-    while (hm) {
-      const int h = __builtin_ctzll(hm);
-      hm &= hm - 1;
-      const int tau_h = (wave_base | h) >> g.lS, s_h = h & (S - 1);
-      const unsigned lo_h = __builtin_amdgcn_readlane((int)lo, h), hi_h = __builtin_amdgcn_readlane((int)hi, h);
-      TieAcc a;
-      a.zero();
-      const bool mine = lane < 32 ? ((lo_h >> lane) & 1u) : (lane < 48 ? ((hi_h >> (lane - 32)) & 1u) : false);
-      if (mine) {
-        const int off = (s_h + (lane >> 2) * S) * 16 + (lane & 3) * 4;
-        unsigned d = *reinterpret_cast<const unsigned*>(xt + tau_h * g.stride + off);
-        while (d) {
-          const int sh = __builtin_ctz(d) & ~7;
-          const unsigned x = (d >> sh) & 0xffu;
-          d &= ~(0xffu << sh);
-          f(tau_h, off + (sh >> 3), x, a);
-        }
-      }
-      a.wave_reduce();
-      if (lane == 0) commit(tau_h, a);
-    }
-    __builtin_amdgcn_wave_barrier();
-  }
-};
-
 // ------------------------------------------------------------------------------------------
-// set-up kernels
+// set-state kernels
 // ------------------------------------------------------------------------------------------
-__global__ void k_pack_x(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, size_t rows, int M, int Mp) {
-  // one 16-byte output chunk per thread
-  size_t nchunk = Mp / 16, total = rows * nchunk;
-  for (size_t q = blockIdx.x * (size_t)blockDim.x + threadIdx.x; q < total; q += (size_t)gridDim.x * blockDim.x) {
-    size_t r = q / nchunk; int c = (int)(q - r * nchunk);
-    unsigned char b[16];
-#pragma unroll
-    for (int u = 0; u < 16; ++u) { int m = c * 16 + u; b[u] = (m < M) ? src[r * M + m] : 0; }
-    *reinterpret_cast<uint4*>(dst + r * Mp + c * 16) = *reinterpret_cast<uint4*>(b);
-  }
-}
-
-__global__ void k_pack_r(const uint8_t* __restrict__ src, uint64_t* __restrict__ dst, size_t rows, int M, int W) {
-  size_t total = rows * W;
-  for (size_t q = blockIdx.x * (size_t)blockDim.x + threadIdx.x; q < total; q += (size_t)gridDim.x * blockDim.x) {
-    size_t r = q / W; int w = (int)(q - r * W);
-    uint64_t bits = 0;
-    for (int u = 0; u < 64; ++u) {
-      int m = w * 64 + u;
-      bool on = (m < M) && (src == nullptr || src[r * M + m] != 0);
-      bits |= (uint64_t)on << u;
-    }
-    dst[q] = bits;
-  }
-}
-
-// coverage flag per tie + sum(X)
-__global__ void k_stats(const uint8_t* __restrict__ X, const uint64_t* __restrict__ Rb, uint8_t* __restrict__ cov,
-                        uint8_t* __restrict__ rcls,
-                        unsigned long long* sumx, unsigned* xmax, unsigned long long* npartial, size_t rows, int Mp,
-                        int W, int M) {
-  unsigned long long local = 0, lpart = 0, lempty = 0;
-  unsigned lmax = 0;
-  for (size_t r = blockIdx.x * (size_t)blockDim.x + threadIdx.x; r < rows; r += (size_t)gridDim.x * blockDim.x) {
-    bool anyx = false, anyr = false;
-    const uint4* p = reinterpret_cast<const uint4*>(X + r * Mp);
-    for (int c = 0; c < Mp / 16; ++c) {
-      uint4 v = p[c];
-      if (v.x | v.y | v.z | v.w) {
-        anyx = true;
-        unsigned d[4] = {v.x, v.y, v.z, v.w};
-        for (int u = 0; u < 4; ++u) {
-          local += (d[u] & 0xff) + ((d[u] >> 8) & 0xff) + ((d[u] >> 16) & 0xff) + (d[u] >> 24);
-          lmax = max(lmax, max(max(d[u] & 0xff, (d[u] >> 8) & 0xff), max((d[u] >> 16) & 0xff, d[u] >> 24)));
-        }
-      }
-    }
-    bool full = true;
-    for (int w = 0; w < W; ++w) {
-      const uint64_t bits = Rb[r * W + w];
-      const int rem = M - w * 64;
-      const uint64_t fm = rem >= 64 ? ~0ull : ((1ull << rem) - 1ull);
-      anyr |= bits != 0;
-      full = full && (bits == fm);
-    }
-    cov[r] = (anyx && anyr) ? 1 : 0;
-    rcls[r] = !anyr ? 0 : (full ? 1 : 2);
-    if (anyr && !full) ++lpart;
-    if (!anyr) ++lempty;
-  }
-  if (local) atomicAdd(sumx, local);
-  if (lpart) atomicAdd(npartial, lpart);
-  if (lempty) atomicAdd(npartial + 1, lempty);   // [1]: rows with no reporter at all
-  if (lmax) atomicMax(xmax, lmax);
-}
-
 __global__ void k_init_rho(const double* __restrict__ pr, double* __restrict__ rho, double* __restrict__ logpr,
                            size_t n, double eps) {
   for (size_t q = blockIdx.x * (size_t)blockDim.x + threadIdx.x; q < n; q += (size_t)gridDim.x * blockDim.x) {
@@ -619,562 +246,9 @@ __global__ __launch_bounds__(TPB) void k_gamma_mask(const uint64_t* __restrict__
   }
 }
 
-// ------------------------------------------------------------------------------------------
-// Sufficient statistics of the reports:  H[l,y,m,k] = sum over ties t of x * rho_k(t), taken over the non-zero
-// counts x = X[l,t,m] whose mirrored count X^T[l,t,m] equals y (y = 0 always when mutuality is off).
-// Everything the gamma, phi and nu updates need from X is linear in rho with weights that depend on (m, y, k) only:
-//   gamma_shp[l,m] = alpha + sum_{y,k} w1_k(m,y) H    (model.py:698-703, 832-859; w1 with the OLD parameters)
-//   phi_shp[l,k]   = alpha + sum_{m,y} w1_k(m,y) H    (model.py:731-733, 861-887; w1 with the NEW E[log theta])
-//   nu_shp         = alpha + sum_{l,m,y>0,k} w2_k(m,y) H   (model.py:822-825; H of the NEW rho)
-// so one pass over X per sweep (the rho pass, which rebuilds H from the new rho) replaces three.  H is tiny
-// ([L][Y][Mp][K] doubles, Y = max count + 1); mirror counts 0..HC-1 are accumulated in LDS, the rest with global
-// f64 atomics.  k_hist builds H from the current rho (start of a fit, sub-step tests).
-// ------------------------------------------------------------------------------------------
-
-struct HistArgs {
-  const uint8_t* X; const double* rho; double* Hg;
-  int Gl;   // workgroups per layer of this launch
-};
-
-// common per-tile bookkeeping of the tile-pair kernels
-struct TileIter {
-  int I, J, nb, b, lb, bb, N;
-  __device__ __forceinline__ void init(const Geo& g, long long p0) {
-    nb = g.nb; b = g.b; lb = g.lb; bb = g.b * g.b; N = g.N;
-    pair_decode(p0, nb, I, J);
-  }
-  __device__ __forceinline__ void next() { if (++J == nb) { ++I; J = I; } }
-  __device__ __forceinline__ bool diag() const { return I == J; }
-  // tie slot tau -> (i,j); false when the slot is unused in this pair or lies outside the network
-  __device__ __forceinline__ bool coords(int tau, int& i, int& j) const {
-    const bool second = tau >= bb;
-    const int u = second ? tau - bb : tau;
-    const int p = u >> lb, q = u & (b - 1);
-    i = (second ? J : I) * b + p;
-    j = (second ? I : J) * b + q;
-    return tau < (diag() ? bb : 2 * bb) && i < N && j < N;
-  }
-  __device__ __forceinline__ int mirror(int tau) const {
-    const bool second = tau >= bb;
-    const int u = second ? tau - bb : tau;
-    const int m = ((u & (b - 1)) << lb) | (u >> lb);
-    return diag() ? m : (second ? m : bb + m);
-  }
-};
-
-// one report into H: LDS cache for small mirror counts, global atomics beyond
-template <int K>
-__device__ __forceinline__ void hist_add(double* Hc, double* Hl /*this workgroup's copy [Y][Mp][K]*/, int Mp, int m, unsigned y,
-                                         double dx, const double* r, unsigned hc) {
-  if (y < hc) {
-    double* d = Hc + ((size_t)y * Mp + m) * K;
-#pragma unroll
-    for (int k = 0; k < K; ++k) atomicAdd(&d[k], dx * r[k]);
-  } else {
-    double* d = Hl + ((size_t)y * Mp + m) * K;
-#pragma unroll
-    for (int k = 0; k < K; ++k) atomicAdd(&d[k], dx * r[k]);
-  }
-}
-__device__ __forceinline__ void hist_flush(const double* Hc, double* Hl, int n) {
-  for (int q = threadIdx.x; q < n; q += TPB) {
-    const double v = Hc[q];
-    if (v != 0.0) atomicAdd(&Hl[q], v);
-  }
-}
-
-template <int K, bool MUT, int PF>
-__global__ __launch_bounds__(TPB, VMR_LB_COUNTS) void k_hist(HistArgs a, Geo g) {
-  extern __shared__ __align__(16) unsigned char smem[];
-  unsigned char* xt = smem;
-  double* rt = reinterpret_cast<double*>(smem + (size_t)g.nt * g.stride);   // rho of the pair's ties [nt][K]
-  double* Hc = rt + (size_t)g.nt * K;                                        // [HC][Mp][K]
-  const int nHc = g.hc * g.Mp * K;
-  unsigned short* wq = reinterpret_cast<unsigned short*>(Hc + nHc) + (threadIdx.x >> 6) * (64 * QCAP);
-  const int l = blockIdx.x / a.Gl, gb = blockIdx.x - l * a.Gl;
-  const long long p0 = (long long)gb * g.P / a.Gl, p1 = (long long)(gb + 1) * g.P / a.Gl;
-  for (int q = threadIdx.x; q < nHc; q += TPB) Hc[q] = 0.0;
-  double* Hl = a.Hg + ((size_t)l * NH + (gb % NH)) * g.Y * g.Mp * K;
-  TileIter it;
-  it.init(g, p0);
-  const int tau = threadIdx.x >> g.lS, s = threadIdx.x & (g.S - 1);
-  const uint8_t* Xl = a.X + (size_t)l * g.N * g.N * g.Mp;
-  const double* rl = a.rho + (size_t)l * g.N * g.N * K;
-  TileStream<PF> ts;
-  ts.init(g);
-  double rn[K];   // rho of this lane's tie in the NEXT pair (prefetched like the X chunks)
-  auto fetch_rho = [&]() {
-    int i, j;
-    const bool ok = it.coords(tau, i, j);
-#pragma unroll
-    for (int k = 0; k < K; ++k) rn[k] = ok ? rl[((size_t)i * g.N + j) * K + k] : 0.0;
-  };
-  if (p0 < p1) { ts.fetch(Xl, g, it.I * g.b, it.J * g.b); fetch_rho(); }
-  __syncthreads();
-  for (long long p = p0; p < p1; ++p) {
-    ts.store(xt);
-    int i, j;
-    const bool act = it.coords(tau, i, j);
-    if (s == 0 && tau < g.nt) {
-#pragma unroll
-      for (int k = 0; k < K; ++k) rt[tau * K + k] = rn[k];
-    }
-    const TileIter cur = it;
-    __syncthreads();
-    it.next();
-    if (p + 1 < p1) { ts.fetch(Xl, g, it.I * g.b, it.J * g.b); fetch_rho(); }   // flies while this pair is scanned
-    TileScan sc;
-    sc.build(xt, g, tau, s, act, wq);
-    sc.walk<NoAcc>(xt, g, tau, s, act, wq,
-      [&](int te, int m, unsigned x, NoAcc&) {
-        const unsigned y = MUT ? (unsigned)xt[cur.mirror(te) * g.stride + m] : 0u;
-        hist_add<K>(Hc, Hl, g.Mp, m, y, (double)x, rt + te * K, (unsigned)g.hc);
-      },
-      [&](int, const NoAcc&) {});
-    __syncthreads();
-  }
-  hist_flush(Hc, Hl, nHc);
-}
-
-// ------------------------------------------------------------------------------------------
-// rho (+ H of the new rho, + ELBO data terms)   model.py:763-818, 889-923; ELBO :948-995, :1013
-// slotR[slot][4]: [1] ELBO linear+entropy terms, [2] ELBO log terms,
-//                 [3] sum_t (sum_k rho_k) Q_t  (multiplied by -E[nu] in k_fin_rho)
-// Walk 1 over the pair's non-zero counts collects U_k per tie; after the per-tie update the same queue is
-// walked again with the NEW rho to rebuild H (and, on ELBO sweeps, the log terms and the mirror sums Q).
-// ------------------------------------------------------------------------------------------
-struct RhoArgs {
-  const uint8_t* X; const uint64_t* Rb; double* rho; const double* logpr; const double* par;
-  double* slotR;
-  const double* lutg;   // nibble LUT of E[theta], [L][W*256]
-  double* Hg;
-  double* slotF;
-  int Gl;
-};
-
-template <int K>
-struct SumU {
-  double U[K];
-  __device__ __forceinline__ void zero() {
-#pragma unroll
-    for (int k = 0; k < K; ++k) U[k] = 0.0;
-  }
-  __device__ __forceinline__ void wave_reduce() {
-#pragma unroll
-    for (int k = 0; k < K; ++k) U[k] = wave_sum(U[k]);
-  }
-};
-struct SumQ {   // ELBO walk: the mirror tie's masked count
-  unsigned q;
-  __device__ __forceinline__ void zero() { q = 0u; }
-  __device__ __forceinline__ void wave_reduce() {
-#pragma unroll
-    for (int o2 = 32; o2 > 0; o2 >>= 1) q += __shfl_xor(q, o2, 64);
-  }
-};
-
-template <int K, bool MUT, bool UPDATE, bool ELBO, int PF>
-__global__ __launch_bounds__(TPB, ELBO ? 2 : VMR_LB_RHO) void k_rho(RhoArgs a, Geo g) {   // ELBO variants: 2 resident (LDS), so 256 VGPRs
-  extern __shared__ __align__(16) unsigned char smem[];
-  unsigned char* xt = smem;
-  size_t off = (size_t)g.nt * g.stride;
-  uint64_t* rw = reinterpret_cast<uint64_t*>(smem + off); off += (size_t)g.nt * g.W * 8;
-  double* wsum = reinterpret_cast<double*>(smem + off); off += (size_t)g.W * 8;
-  double* lth = reinterpret_cast<double*>(smem + off); off += (size_t)g.Mp * 8;
-  double* red = reinterpret_cast<double*>(smem + off); off += 8 * 8;
-  double* ct = reinterpret_cast<double*>(smem + off); off += MUT ? (size_t)g.Mp * K * 8 : 0;
-  double* ut = reinterpret_cast<double*>(smem + off); off += (size_t)g.nt * K * 8;    // U per tie; exp(rho) in the ELBO walk
-  double* rt = reinterpret_cast<double*>(smem + off); off += (size_t)g.nt * K * 8;    // (new) rho per tie
-  const bool do_hist = UPDATE && !g.two_pass;
-  const int nHc = do_hist ? g.hc * g.Mp * K : 0;
-  double* Hc = reinterpret_cast<double*>(smem + off); off += (size_t)nHc * 8;
-  double* Gth = reinterpret_cast<double*>(smem + off); off += ELBO ? (size_t)g.Mp * 8 : 0;
-  unsigned* qs = reinterpret_cast<unsigned*>(smem + off); off += ELBO ? (size_t)g.nt * 4 : 0;
-  unsigned short* wq = reinterpret_cast<unsigned short*>(smem + off) + (threadIdx.x >> 6) * (64 * QCAP);
-  const ParOff o = par_off(g.L, g.Mp, g.K);
-  const int l = blockIdx.x / a.Gl, gb = blockIdx.x - l * a.Gl;
-  const long long p0 = (long long)gb * g.P / a.Gl, p1 = (long long)(gb + 1) * g.P / a.Gl;
-  for (int m = threadIdx.x; m < g.Mp; m += TPB) {
-    lth[m] = a.par[o.l_th + (size_t)l * g.Mp + m];
-    if (ELBO) Gth[m] = a.par[o.G_th + (size_t)l * g.Mp + m];
-  }
-  for (int q = threadIdx.x; q < nHc; q += TPB) Hc[q] = 0.0;
-  // lut[n][e] = sum of E[theta_m] over the set bits e of reporters 4n..4n+3 (global, L1/L2 resident);
-  // wsum[w] = sum over the 64 reporters of word w (shortcut for all-ones words)
-  const double* lut = a.lutg + (size_t)l * g.W * 256;
-  for (int w = threadIdx.x; w < g.W; w += TPB) {
-    double v = 0.0;
-    for (int n = 0; n < 16; ++n) v += lut[(w * 16 + n) * 16 + 15];
-    wsum[w] = v;
-  }
-  double Ela[K], lla[K], Gla[K];
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    Ela[k] = a.par[o.E_la + l * K + k]; lla[k] = a.par[o.l_la + l * K + k]; Gla[k] = a.par[o.G_la + l * K + k];
-  }
-  // UPDATE: the weights use the current G_nu; stand-alone ELBO: the stale one (model.py:970)
-  const double gnu = a.par[o.sc + (UPDATE ? SC_G_NU : SC_G_NU_STALE)];
-  const double eps = g.eps;
-  double e_lin = 0.0, e_q = 0.0, e_log = 0.0;
-  double accF[K];   // sum of the new rho over this workgroup's ties whose mask row is all ones
-#pragma unroll
-  for (int k = 0; k < K; ++k) accF[k] = 0.0;
-  const int lastrem = g.M - (g.W - 1) * 64;
-  const uint64_t lastfull = lastrem >= 64 ? ~0ull : ((1ull << lastrem) - 1ull);
-  if (MUT) build_ct<K>(ct, a.par + o.G_th + (size_t)l * g.Mp, Gla, gnu, g.Mp);
-  double* Hl = a.Hg + ((size_t)l * NH + (gb % NH)) * g.Y * g.Mp * K;
-
-  TileIter it;
-  it.init(g, p0);
-  const int tau = threadIdx.x >> g.lS, s = threadIdx.x & (g.S - 1);
-  const size_t T = (size_t)g.N * g.N;
-  const uint8_t* Xl = a.X + (size_t)l * T * g.Mp;
-  const uint64_t* Rl = a.Rb + (size_t)l * T * g.W;
-  double* rl = a.rho + (size_t)l * T * K;
-  const double* lpl = a.logpr + (size_t)l * T * K;
-  TileStream<PF> ts;
-  ts.init(g);
-  MaskStream ms;
-  ms.init(g);
-  double lpn[K], rn[K];   // log prior (and rho, ELBO-only) of this lane's tie in the NEXT pair
-  auto fetch_tie = [&]() {
-    int i, j;
-    const bool ok = it.coords(tau, i, j);
-    const size_t t_ = ok ? ((size_t)i * g.N + j) : 0;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      lpn[k] = ok ? lpl[t_ * K + k] : 0.0;
-      rn[k] = (!UPDATE && ok) ? rl[t_ * K + k] : 0.0;
-    }
-  };
-  if (p0 < p1) { ts.fetch(Xl, g, it.I * g.b, it.J * g.b); ms.fetch(Rl, g, it.I * g.b, it.J * g.b); fetch_tie(); }
-  __syncthreads();
-  for (long long p = p0; p < p1; ++p) {
-    ts.store(xt);
-    ms.store(rw);
-    int i, j;
-    const bool act = it.coords(tau, i, j);
-    const size_t tg = act ? ((size_t)i * g.N + j) : 0;
-    const TileIter cur = it;
-    double lp[K], r[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) { lp[k] = lpn[k]; r[k] = rn[k]; }
-    if (UPDATE && s == 0 && tau < g.nt) {
-#pragma unroll
-      for (int k = 0; k < K; ++k) ut[tau * K + k] = 0.0;
-    }
-    __syncthreads();
-    it.next();
-    if (p + 1 < p1) { ts.fetch(Xl, g, it.I * g.b, it.J * g.b); ms.fetch(Rl, g, it.I * g.b, it.J * g.b); fetch_tie(); }
-    double Tt = 0.0;
-    int rowfull = 1;
-    if (act) {
-      // T = sum_m R E[theta_m] (model.py:766-792): whole-word shortcut, else nibble look-ups
-      const uint64_t* rwt = rw + (size_t)tau * g.W;
-      for (int w = s; w < g.W; w += g.S) {
-        uint64_t bits = rwt[w];
-        rowfull &= (bits == (w == g.W - 1 ? lastfull : ~0ull)) ? 1 : 0;
-        if (bits == ~0ull) { Tt += wsum[w]; continue; }
-        for (int n = 0; bits != 0; ++n, bits >>= 4) Tt += lut[((w * 16 + n) << 4) + (unsigned)(bits & 15u)];
-      }
-    }
-    Tt = group_sum(Tt, g.S);
-    if (UPDATE && g.fuse_full) {
-      for (int o2 = g.S >> 1; o2 > 0; o2 >>= 1) rowfull &= __shfl_xor(rowfull, o2, 64);
-    }
-    TileScan sc;
-    sc.build(xt, g, tau, s, act, wq);
-    if (UPDATE) {
-      sc.walk<SumU<K>>(xt, g, tau, s, act, wq,
-        [&](int te, int m, unsigned x, SumU<K>& acc) {
-          const double dx = (double)x, lt = lth[m];
-          if (MUT) {
-            double w[K], cy[K];
-            weights<K>(w, cy, ct, m, (unsigned)xt[cur.mirror(te) * g.stride + m]);
-#pragma unroll
-            for (int k = 0; k < K; ++k) acc.U[k] += (lt + lla[k]) * (dx * w[k]);
-          } else {
-#pragma unroll
-            for (int k = 0; k < K; ++k) acc.U[k] += (lt + lla[k]) * dx;
-          }
-        },
-        [&](int te, const SumU<K>& t) {   // the tie's sums live in LDS; a tie belongs to one wave
-#pragma unroll
-          for (int k = 0; k < K; ++k) atomicAdd(&ut[te * K + k], t.U[k]);
-        });
-      double sum = 0.0;
-#pragma unroll
-      for (int k = 0; k < K; ++k) {
-        const double u = (tau < g.nt) ? ut[tau * K + k] : 0.0;
-        r[k] = exp((lp[k] + u) - Tt * Ela[k]);   // no max-subtraction, as model.py:807
-        sum += r[k];
-      }
-      if (sum > 0.0) {   // model.py:808-811; a true divide: 1/sum overflows when sum is subnormal
-#pragma unroll
-        for (int k = 0; k < K; ++k) r[k] /= sum;
-      }
-      if (act && s == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-          rl[tg * K + k] = r[k];
-          accF[k] += (g.fuse_full && rowfull) ? r[k] : 0.0;
-        }
-      }
-    }
-    if (s == 0 && tau < g.nt) {
-#pragma unroll
-      for (int k = 0; k < K; ++k) {
-        rt[tau * K + k] = r[k];
-        if (ELBO) ut[tau * K + k] = exp(r[k]);   // exp(rho), model.py:971 (U is consumed)
-      }
-      if (ELBO) qs[tau] = 0u;
-    }
-    if (ELBO) __syncthreads(); else __builtin_amdgcn_wave_barrier();   // Q crosses waves, the rest is wave-local
-    // walk 2: H of the new rho; ELBO log terms and mirror sums
-    if (do_hist || ELBO) sc.walk<SumQ>(xt, g, tau, s, act, wq,
-      [&](int te, int m, unsigned x, SumQ& acc) {
-        const double dx = (double)x;
-        const int mt = cur.mirror(te);
-        const unsigned y = MUT ? (unsigned)xt[mt * g.stride + m] : 0u;
-        if (do_hist) hist_add<K>(Hc, Hl, g.Mp, m, y, dx, rt + te * K, (unsigned)g.hc);
-        if (ELBO) {
-          const bool in_r = (rw[te * g.W + (m >> 6)] >> (m & 63)) & 1ull;
-          double inner = 0.0;
-          if (in_r) {
-            const double z2 = gnu * (double)y, gt = Gth[m];
-            const double* er = ut + te * K;
-#pragma unroll
-            for (int k = 0; k < K; ++k) inner += er[k] * (gt * Gla[k] + z2);
-          }
-          e_log += dx * log(inner + eps);
-          if (MUT && ((rw[mt * g.W + (m >> 6)] >> (m & 63)) & 1ull)) acc.q += x;   // R[mirror] X^T[mirror]
-        }
-      },
-      [&](int te, const SumQ& t) {   // Q of the MIRROR tie: sum_m R[mirror,m] X[this,m]
-        if (ELBO && t.q) atomicAdd(&qs[cur.mirror(te)], t.q);
-      });
-    if (ELBO) {
-      __syncthreads();
-      if (act && s == 0) {
-        double sr = 0.0, se = 0.0, ent = 0.0;
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-          sr += r[k]; se += r[k] * Ela[k];
-          ent += r[k] * lp[k] - r[k] * log(r[k] + eps);   // model.py:1306-1313
-        }
-        e_lin += ent - se * Tt;
-        e_q += sr * (double)qs[tau];
-      }
-    }
-    __syncthreads();
-  }
-  if (do_hist) hist_flush(Hc, Hl, nHc);
-  if (UPDATE && g.fuse_full) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      double v = block_sum(accF[k], red);
-      if (threadIdx.x == 0) atomicAdd(&a.slotF[((size_t)l * NSLOT + (gb % NSLOT)) * K + k], v);
-    }
-  }
-  if (ELBO) {
-    double v1 = block_sum(e_lin, red);
-    double v2 = block_sum(e_log, red);
-    double v3 = block_sum(e_q, red);
-    if (threadIdx.x == 0) {
-      double* out = a.slotR + (size_t)(blockIdx.x % NSLOT) * 4;
-      atomicAdd(&out[1], v1); atomicAdd(&out[2], v2); atomicAdd(&out[3], v3);
-    }
-  }
-}
-
-// ==========================================================================================
-// Report lists (the default data format when X is sparse, which it is: 1.5-5 % of the counts are non-zero)
-//
-// X is a tensor of COUNTS of which a few per cent are non-zero; every update touches only those, and the only
-// thing the mutuality terms need besides a report is the mirrored count X[l,j,i,m].  vmr_create therefore turns
-// the dense tensor into one 4-byte entry per non-zero count (layout and limits: sweep_sl.h), sorted by the ties'
-// report counts and laid out in steps of 64 ties (sorted_lists.hip); rcls[l][t] = class of the tie's mask row (0 empty,
-// 1 all ones, 2 partial; not read when every row is all ones), Qt[l][t] = sum_m R[t,m] X[mirror(t),m] (the ELBO's mirror
-// sum, a constant of the data).  A sweep reads 4 B per report + rho/log-prior instead of 1 B per (tie, reporter).  The
-// dense tensor is freed once the lists exist.  (Rounds 1-2 kept steps of 64 CONSECUTIVE ties with a scattered rest --
-// k_rho_sp, removed in round 3: DESIGN.md section 2.)
-// ==========================================================================================
-__device__ __forceinline__ unsigned nz_bytes(uint4 v) {
-  const unsigned M = 0x7f7f7f7fu;
-  unsigned t0 = (((v.x & M) + M) | v.x) & ~M, t1 = (((v.y & M) + M) | v.y) & ~M;
-  unsigned t2 = (((v.z & M) + M) | v.z) & ~M, t3 = (((v.w & M) + M) | v.w) & ~M;
-  return __popc(t0) + __popc(t1) + __popc(t2) + __popc(t3);
-}
-
-// Per tie of one layer (16 lanes per row): rp[t] = its non-zero counts.  The layer total goes to *nnz.
-__global__ __launch_bounds__(256) void k_sp_count(const uint8_t* __restrict__ Xl, unsigned* __restrict__ rpl,
-                                                  unsigned long long* nnz, Geo g) {
-  __shared__ double red[8];
-  const int gl = threadIdx.x & 15;
-  unsigned long long mine = 0;
-  const size_t T = (size_t)g.N * g.N, Tr = (T + 15) / 16 * 16;
-  for (size_t t = ((size_t)blockIdx.x * 256 + threadIdx.x) >> 4; t < Tr; t += (size_t)gridDim.x * 16) {
-    unsigned c = 0;
-    if (t < T) {
-      const uint8_t* row = Xl + t * g.Mp;
-      for (int ch = gl; ch < g.nchunk; ch += 16) c += nz_bytes(*reinterpret_cast<const uint4*>(row + ch * 16));
-    }
-    c = group_sum_u(c, 16);
-    if (gl == 0 && t < T) { rpl[t] = c; mine += c; }
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) rpl[T] = 0u;
-  // block total (exact in double: < 2^53)
-  double v = block_sum((double)mine, red);
-  if (threadIdx.x == 0 && v > 0.0) atomicAdd(nnz, (unsigned long long)v);
-}
-
-// in-place exclusive scan of n u32 items in three launches (2048 items per workgroup)
-__global__ __launch_bounds__(256) void k_scan_local(unsigned* a, unsigned* bsum, size_t n) {
-  __shared__ unsigned sh[256];
-  const size_t base = (size_t)blockIdx.x * 2048 + (size_t)threadIdx.x * 8;
-  unsigned v[8], s = 0;
-#pragma unroll
-  for (int u = 0; u < 8; ++u) { unsigned t = (base + u < n) ? a[base + u] : 0u; v[u] = s; s += t; }
-  sh[threadIdx.x] = s;
-  __syncthreads();
-  for (int o2 = 1; o2 < 256; o2 <<= 1) {
-    unsigned t = (threadIdx.x >= (unsigned)o2) ? sh[threadIdx.x - o2] : 0u;
-    __syncthreads();
-    sh[threadIdx.x] += t;
-    __syncthreads();
-  }
-  const unsigned excl = sh[threadIdx.x] - s;
-#pragma unroll
-  for (int u = 0; u < 8; ++u) if (base + u < n) a[base + u] = v[u] + excl;
-  if (threadIdx.x == 255) bsum[blockIdx.x] = sh[255];
-}
-__global__ __launch_bounds__(256) void k_scan_bsum(unsigned* bsum, int nb) {
-  __shared__ unsigned sh[256];
-  unsigned carry = 0;
-  for (int c0 = 0; c0 < nb; c0 += 256) {
-    const int i = c0 + threadIdx.x;
-    const unsigned s = (i < nb) ? bsum[i] : 0u;
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (int o2 = 1; o2 < 256; o2 <<= 1) {
-      unsigned t = (threadIdx.x >= (unsigned)o2) ? sh[threadIdx.x - o2] : 0u;
-      __syncthreads();
-      sh[threadIdx.x] += t;
-      __syncthreads();
-    }
-    if (i < nb) bsum[i] = carry + sh[threadIdx.x] - s;
-    carry += sh[255];
-    __syncthreads();
-  }
-}
-__global__ __launch_bounds__(256) void k_scan_add(unsigned* a, const unsigned* __restrict__ bsum, size_t n) {
-  const size_t base = (size_t)blockIdx.x * 2048 + (size_t)threadIdx.x * 8;
-  const unsigned add = bsum[blockIdx.x];
-#pragma unroll
-  for (int u = 0; u < 8; ++u) if (base + u < n) a[base + u] += add;
-}
-// Write the entries of one layer (16 lanes per tie) and the mirror sums Qt.  rpl is the exclusive scan of the
-// per-tie counts: tie t's entries start at rpl[t], reporters ascending.
-template <bool MUT>
-__global__ __launch_bounds__(256) void k_sp_fill(const uint8_t* __restrict__ Xl, const uint64_t* __restrict__ Rl,
-                                                 const unsigned* __restrict__ rpl, unsigned* __restrict__ El, unsigned* __restrict__ El2 /*wide entries: the second words*/,
-                                                 unsigned* __restrict__ Qtl, Geo g) {
-  const int gl = threadIdx.x & 15;
-  const size_t T = (size_t)g.N * g.N, Tr = (T + 15) / 16 * 16;
-  for (size_t t = ((size_t)blockIdx.x * 256 + threadIdx.x) >> 4; t < Tr; t += (size_t)gridDim.x * 16) {
-    const bool ok = t < T;
-    const size_t tc = ok ? t : 0;
-    const size_t i = tc / g.N, j = tc - i * g.N, tm = j * g.N + i;
-    const uint8_t* row = Xl + tc * g.Mp;
-    const uint8_t* mrow = Xl + tm * g.Mp;
-    const uint64_t* rr = Rl + tc * g.W;
-    const uint64_t* rmr = Rl + tm * g.W;
-    size_t pos = rpl[tc];
-    unsigned q = 0;
-    for (int c0 = 0; c0 < g.nchunk; c0 += 16) {   // uniform over the 16 lanes
-      const int ch = c0 + gl;
-      uint4 v = make_uint4(0, 0, 0, 0), yv = make_uint4(0, 0, 0, 0);
-      if (ok && ch < g.nchunk) {
-        v = *reinterpret_cast<const uint4*>(row + ch * 16);
-        if (MUT) yv = *reinterpret_cast<const uint4*>(mrow + ch * 16);
-      }
-      const unsigned xs[4] = {v.x, v.y, v.z, v.w}, ys[4] = {yv.x, yv.y, yv.z, yv.w};
-      const unsigned n = nz_bytes(v);
-      unsigned incl = n;
-#pragma unroll
-      for (int o2 = 1; o2 < 16; o2 <<= 1) {
-        const unsigned up = __shfl_up(incl, o2, 16);
-        if (gl >= o2) incl += up;
-      }
-      const unsigned tot = __shfl(incl, 15, 16);
-      size_t w = pos + incl - n;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        unsigned dw = xs[u];
-        while (dw) {
-          const int sh = __builtin_ctz(dw) & ~7;
-          const unsigned x = (dw >> sh) & 0xffu;
-          dw &= ~(0xffu << sh);
-          const int m = ch * 16 + u * 4 + (sh >> 3);
-          const unsigned inr = (unsigned)((rr[m >> 6] >> (m & 63)) & 1ull);
-          unsigned y = 0;
-          if (MUT) {
-            y = (ys[u] >> sh) & 0xffu;
-            if ((rmr[m >> 6] >> (m & 63)) & 1ull) q += x;   // R[mirror,m] X[this,m]
-          }
-          if (El2) { El[w] = y * (unsigned)g.Mp + (unsigned)m; El2[w] = (x << 1) | inr; ++w; }
-          else El[w++] = (y * (unsigned)g.Mp + (unsigned)m) | (inr << 20) | (x << 21);   // (sweep_sl.h)
-        }
-      }
-      pos += tot;
-    }
-    q = group_sum_u(q, 16);
-    if (ok && gl == 0) Qtl[tm] = q;   // every tie is the mirror of exactly one tie
-  }
-}
-
-// ------------------------------------------------------------------------------------------
-// Mask lists: a partial mask row as the list of its reporters (u16), for masks whose partial rows hold few
-// reporters (the self-reporter mask of survey data: R[l,i,j,m] = 1 iff m is i or j, two per row).  Reading 4 bytes
-// per row instead of W words makes the mask sums A and the per-tie T of such data a few microseconds.
-// rq[l][t] (u32, N*N+1 per layer): first reporter of tie t's list, relative to rbase[l]; empty for rows that are
-// not partial.
-// ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_rm_count(const uint64_t* __restrict__ Rl, const uint8_t* __restrict__ cl,
-                                                  unsigned* __restrict__ rql, unsigned long long* total, unsigned* maxrow,
-                                                  size_t T, int W) {
-  __shared__ double red[8];
-  unsigned long long mine = 0;
-  unsigned mx = 0;
-  for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < T; t += (size_t)gridDim.x * 256) {
-    unsigned n = 0;
-    if (cl[t] == 2) for (int w = 0; w < W; ++w) n += (unsigned)__popcll(Rl[t * W + w]);
-    rql[t] = n;
-    mine += n;
-    mx = max(mx, n);
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) rql[T] = 0u;
-  double v = block_sum((double)mine, red);
-  if (threadIdx.x == 0 && v > 0.0) atomicAdd(total, (unsigned long long)v);
-  if (mx) atomicMax(maxrow, mx);
-}
-__global__ __launch_bounds__(256) void k_rm_fill(const uint64_t* __restrict__ Rl, const uint8_t* __restrict__ cl,
-                                                 const unsigned* __restrict__ rql, unsigned short* __restrict__ Rml, size_t T, int W) {
-  for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < T; t += (size_t)gridDim.x * 256) {
-    if (cl[t] != 2) continue;
-    size_t q = rql[t];
-    for (int w = 0; w < W; ++w) {
-      uint64_t bits = Rl[t * W + w];
-      while (bits) {
-        const int b_ = __builtin_ctzll(bits);
-        bits &= bits - 1;
-        Rml[q++] = (unsigned short)(w * 64 + b_);
-      }
-    }
-  }
-}
 // A[l,m,k] += rho[l,t,k] over the listed reporters of the partial rows (model.py:704-718, 742-749); all-ones rows
 // were summed by the rho pass.  One thread per tie, A of the workgroup in LDS, one global add per value at the end.
+// (The mask lists rq / Rm: create.hip, beside k_rm_count.)
 template <int K>
 __global__ __launch_bounds__(TPB) void k_mask_lists(const unsigned* __restrict__ rq, const unsigned short* __restrict__ Rm,
                                                     const unsigned long long* __restrict__ rbase, const uint8_t* __restrict__ rcls,
@@ -1271,7 +345,6 @@ __device__ __forceinline__ double h_at(const double* Hl0, size_t, size_t idx) { 
 #ifndef FIN_TPB
 #define FIN_TPB 512   // (1024: 128 registers, 16-33 spilled, +2 us per launch; 256: +5 us)
 #endif
-#define FG_G 16   // workgroups per layer of k_fin_gamma: each owns a range of reporters
 __device__ __forceinline__ double block_sum_fin(double v, double* red /*16*/) {   // result valid in thread 0
   v = wave_sum(v);
   __syncthreads();
@@ -1586,7 +659,6 @@ __device__ __forceinline__ double gamma_elbo_term(double pa, double pb, double q
 // nu from H of the new rho (model.py:694-696, 822-825: sum x w2_k rho_k) and/or ELBO assembly (model.py:997-1013).
 // One workgroup per layer adds its share to fin[0..1] with device-scope atomics; the workgroup that draws the
 // last ticket (fin[2]) finishes the scalars and clears the scratch.
-#define FR_G 16   // workgroups per layer of k_fin_rho
 __device__ __forceinline__ void fin_rho_body(double* par, double* Hg, const double* Cg, double* slotR, double* elbo_out,
                                              double* fin, int do_nu, int do_elbo, int fold, int skip_nu /* the pass finished nu itself */, const Geo& g,
                                              const int bx, const int gx, double* slots = nullptr /*deterministic mode: [gx][2] partial sums, summed in order*/) {
@@ -1763,24 +835,8 @@ __global__ __launch_bounds__(256) void k_sample(const double* __restrict__ rho, 
 // host side
 // ------------------------------------------------------------------------------------------
 
-static size_t shmem_ct(const Geo& g) { return g.mut ? (size_t)g.Mp * g.K * 8 : 0; }
-static size_t shmem_q() { return (size_t)(TPB / 64) * 64 * QCAP * 2; }
-static size_t shmem_hc(const Geo& g) { return (size_t)g.hc * g.Mp * g.K * 8; }
-static size_t shmem_hist(const Geo& g) {
-  return (size_t)g.nt * g.stride + (size_t)g.nt * g.K * 8 + shmem_hc(g) + shmem_q() + 16;
-}
-static size_t shmem_rho(const Geo& g, bool update, bool elbo) {
-  size_t n = (size_t)g.nt * g.stride + (size_t)g.nt * g.W * 8 + (size_t)g.W * 8 + (size_t)g.Mp * 8 + 64 + shmem_ct(g) +
-             2 * (size_t)g.nt * g.K * 8 + shmem_q();
-  if (update && !g.two_pass) n += shmem_hc(g);
-  if (elbo) n += (size_t)g.Mp * 8 + (size_t)g.nt * 4;
-  return n + 16;
-}
-
-#define SP_LDS_MAX (160 * 1024)
-
 // Launch shape of one sweep over the sorted lists: the handle's block size and table levels, shrunk until the workgroup fits in LDS
-static SlShape sl_shape(const vmr_ctx* h, bool update, bool elbo, bool hist) {
+SlShape sl_shape(const vmr_ctx* h, bool update, bool elbo, bool hist) {
   const Geo& g = h->g;
   SlShape s{std::max(64, std::min((update || elbo) ? h->sp_tpb : h->st_tpb, sl_tpb_max(g.K, elbo, h->all_full != 0, update)) & ~63), update ? g.yt : 0, hist ? g.hc : 0, 0};
   auto bytes = [&]() { return sl_smem(g, s.yt, s.hc, update, elbo, hist); };
@@ -1788,107 +844,15 @@ static SlShape sl_shape(const vmr_ctx* h, bool update, bool elbo, bool hist) {
   s.smem = bytes();
   return s;
 }
-static SlArgs sl_args(const vmr_ctx* h, const SlShape& sh, int do_hist, int sum_a = 0) {
+SlArgs sl_args(const vmr_ctx* h, const SlShape& sh, int do_hist, int sum_a) {
   return SlArgs{h->E, h->rs, h->ebase, h->perm, h->sy, h->cls_p, h->Qt_p, h->Rb, h->rq, h->Rm, h->rbase, h->rm2, h->rho, h->logpr, h->par, h->slotR,
                 h->lutg, h->Hg, h->slotF, h->slotA, 1, do_hist, sh.yt, sh.hc, sum_a, nullptr, nullptr, 0, 0, nullptr, h->lp0 ? 1 : 0, h->g.farl, (do_hist == 1 && h->g.two_pass && sh.hc >= 1) ? h->h0s : nullptr, (do_hist == 1 && h->g.two_pass && sh.hc >= 1 && h->h0s) ? h->x0p : nullptr,
                 (h->h0s && h->g.two_pass && !h->opt.no_lv0r) ? 1 : 0, h->E + h->n_slots, 0, h->lpd, h->lpb};   // (level 0 must be among the LDS levels: its deficits go there)
 }
-static int sl_launch(vmr_ctx* h, int mode, const SlShape& sh, SlArgs& a) {
+int sl_launch(vmr_ctx* h, int mode, const SlShape& sh, SlArgs& a) {
   sl_launch_fn fn = vmr_sl_launcher(h->g.K);
   if (!fn) return fail(h, VMR_EINVAL, "this build of libvimure_hip.so holds no sweep kernel for this K");
   return fn(h, mode, sh, a);
-}
-
-#ifdef VMR_DEV   // development build: K = 2 only (fast compile, ISA inspection)
-#define DISPATCH_K(K_, ...)                         \
-  switch (K_) {                                     \
-    case 2: { constexpr int KK = 2; __VA_ARGS__; } break; \
-    default: break;                                 \
-  }
-#else
-#define DISPATCH_K(K_, ...)                         \
-  switch (K_) {                                     \
-    case 2: { constexpr int KK = 2; __VA_ARGS__; } break; \
-    case 3: { constexpr int KK = 3; __VA_ARGS__; } break; \
-    case 4: { constexpr int KK = 4; __VA_ARGS__; } break; \
-    case 5: { constexpr int KK = 5; __VA_ARGS__; } break; \
-    case 6: { constexpr int KK = 6; __VA_ARGS__; } break; \
-    case 7: { constexpr int KK = 7; __VA_ARGS__; } break; \
-    case 8: { constexpr int KK = 8; __VA_ARGS__; } break; \
-    default: break;                                 \
-  }
-#endif
-// K and the prefetch depth (4, 8 or 12 sixteen-byte chunks per thread)
-#define DISPATCH_KP(K_, PF_, ...)                                     \
-  switch (PF_) {                                                      \
-    case 4: { constexpr int PP = 4; DISPATCH_K(K_, __VA_ARGS__); } break;   \
-    case 8: { constexpr int PP = 8; DISPATCH_K(K_, __VA_ARGS__); } break;   \
-    default: { constexpr int PP = 12; DISPATCH_K(K_, __VA_ARGS__); } break; \
-  }
-
-
-
-// ------------------------------------------------------------------------------------------
-// Geo::farl -- the reports of the levels beyond the LDS ones
-// ------------------------------------------------------------------------------------------
-// Geo::farl: every tie's reports of the levels beyond the LDS ones (row >= rows_near) are moved to the FRONT of its list -- one wave
-// per step, a lane walks its tie's column and swaps a far report with the first near one -- so that only the first nf rounds of a
-// step (nf = the most far reports any of its 64 ties has; stored in the high half of sy) ever take the pass' far-level code: left
-// where they fall, 2 % of far reports put one into two rounds of three.
-// slots read by a statistics pass that skips the rounds of level 0 only: sum over steps of 64 min(R, n1)  (vmr_kernel_bytes)
-__global__ __launch_bounds__(256) void k_stat_slots(const unsigned* __restrict__ rsl, const unsigned* __restrict__ syl, size_t NS, unsigned long long* __restrict__ out) {
-  unsigned long long v = 0;
-  for (size_t s = (size_t)blockIdx.x * 256 + threadIdx.x; s < NS; s += (size_t)gridDim.x * 256) {
-    const unsigned R = (rsl[s + 1] - rsl[s]) >> 6, n1 = syl[s] >> 16;
-    v += 64ull * (unsigned long long)min(R, n1);
-  }
-  if (v) atomicAdd(out, v);
-}
-// x0 != null: also the tie's summed counts of the near reports, by position (SlArgs::x0p).
-__global__ __launch_bounds__(256) void k_far_first(unsigned* __restrict__ E, const unsigned* __restrict__ rsl, unsigned* __restrict__ syl, size_t NS, unsigned rows_near,
-                                                   unsigned* __restrict__ x0) {
-  const int lane = threadIdx.x & 63;
-  for (size_t s = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6); s < NS; s += (size_t)gridDim.x * 4) {
-    const unsigned ea = rsl[s], R = (rsl[s + 1] - ea) >> 6;
-    unsigned* col = E + (size_t)ea + lane;
-    unsigned f = 0;   // far reports found so far = the slot the next one goes to
-    unsigned xs = 0;
-    for (unsigned r = 0; r < R; ++r) {
-      const unsigned e = col[(size_t)r * 64];
-      if (e != 0u && SL_YM(e) >= rows_near) {
-        if (f != r) { const unsigned o = col[(size_t)f * 64]; col[(size_t)f * 64] = e; col[(size_t)r * 64] = o; }
-        ++f;
-      } else xs += SL_X(e);
-    }
-    if (x0) x0[s * 64 + (unsigned)lane] = xs;
-#pragma unroll
-    for (int o2 = 32; o2 > 0; o2 >>= 1) f = max(f, (unsigned)__shfl_xor((int)f, o2, 64));
-    if (lane == 0) syl[s] = (syl[s] & 0xffffu) | (min(f, 0xffffu) << 16);
-  }
-}
-
-// One wave per step of the sorted lists: (position, entry) of every report whose mirror count is at least yfar, appended to the
-// layer's far list (order immaterial: their sums are float atomics anyway).
-__global__ __launch_bounds__(256) void k_far_collect(const unsigned* __restrict__ E, const unsigned* __restrict__ rsl, size_t NS, unsigned rows_near,
-                                                     unsigned* __restrict__ far_pos, unsigned* __restrict__ far_ent, unsigned long long* __restrict__ counter) {
-  const int lane = threadIdx.x & 63;
-  for (size_t s = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6); s < NS; s += (size_t)gridDim.x * 4) {
-    const unsigned ea = rsl[s], R = (rsl[s + 1] - ea) >> 6;
-    for (unsigned r = 0; r < R; ++r) {
-      const unsigned e = E[(size_t)ea + r * 64 + lane];
-      const bool far = e != 0u && SL_X(e) != 0u && SL_YM(e) >= rows_near;
-      const unsigned long long bal = __ballot(far);
-      if (bal == 0ull) continue;
-      unsigned long long base = 0ull;
-      if (lane == 0) base = atomicAdd(counter, (unsigned long long)__popcll(bal));
-      base = ((unsigned long long)(unsigned)__shfl((int)(unsigned)(base >> 32), 0, 64) << 32) | (unsigned)__shfl((int)(unsigned)base, 0, 64);
-      if (far) {
-        const unsigned long long at = base + (unsigned long long)__popcll(bal & ((1ull << lane) - 1ull));
-        far_pos[at] = (unsigned)(s * 64 + (unsigned)lane);
-        far_ent[at] = e;
-      }
-    }
-  }
 }
 
 // The statistics of the far reports: H[y][m][k] += x rho_k (k >= 1; the deficits of ties whose rho does not sum to 1 in slot 0)
@@ -2027,9 +991,21 @@ __global__ __launch_bounds__(256) void k_level0_total(const double* __restrict__
   s = block_sum_n(s, red);
   if (threadIdx.x == 0) h0s[(size_t)g.L * NSLOT * g.K + l] = s;
 }
+// the count-mode launch of vmr_create is done: its result becomes the constants (create.h)
+int take_counts(vmr_ctx* h) {
+  const Geo& g = h->g;
+  const size_t nit = (size_t)g.L * g.Y * g.Mp;
+  hipLaunchKernelGGL(k_take_counts, dim3((unsigned)std::min<size_t>(1024, (nit + TPB - 1) / TPB)), dim3(TPB), 0, h->stream, h->Hg, h->Cg, g);
+  CK(hipGetLastError());
+  if (h->h0s) {
+    hipLaunchKernelGGL(k_level0_total, dim3(g.L), dim3(256), 0, h->stream, h->Cg, h->h0s, g);
+    CK(hipGetLastError());
+  }
+  return VMR_OK;
+}
 
 // nu: -1 = no nu sum in this sweep; 0 = the raw sum to elbo_dev[1]; 1 = nu committed too (as launch_hist's)
-static int launch_far(vmr_ctx* h, int count, int nu) {
+int launch_far(vmr_ctx* h, int count, int nu) {
   const Geo& g = h->g;
   if (!g.farl || h->far_off.empty() || h->far_off.back() == 0ull) {
     if (nu >= 0 && g.farl) return fail(h, VMR_ESTATE, "far lists missing");   // (cannot happen: farl is only chosen with far reports)
@@ -2153,16 +1129,8 @@ static int launch_hist(vmr_ctx* h, int nu = -1) {
     if ((rcs = det_fold(h))) return rcs;
   } else {
     Prof p(h, VMR_KERNEL_GAMMA_COUNTS);
-    HistArgs a{h->X, h->rho, h->Hg, 1};
-    size_t sm = shmem_hist(g);
-    int rc = VMR_OK;
-    if (g.mut) {
-      DISPATCH_KP(g.K, g.pf, if ((rc = grid_per_layer(h, k_hist<KK, true, PP>, sm, &a.Gl))) return rc;
-                  hipLaunchKernelGGL((k_hist<KK, true, PP>), dim3(g.L * a.Gl), dim3(TPB), sm, h->stream, a, g));
-    } else {
-      DISPATCH_KP(g.K, g.pf, if ((rc = grid_per_layer(h, k_hist<KK, false, PP>, sm, &a.Gl))) return rc;
-                  hipLaunchKernelGGL((k_hist<KK, false, PP>), dim3(g.L * a.Gl), dim3(TPB), sm, h->stream, a, g));
-    }
+    int rc = tiles_hist(h);
+    if (rc) return rc;
   }
   HIPCHK(h, hipGetLastError());
   h->h_valid = true;
@@ -2290,9 +1258,7 @@ static int launch_rho(vmr_ctx* h, int mode, bool commit_nu, bool raw_nu = false,
     HIPCHK(h, hipGetLastError());
     return launch_fin_rho(h, 0, 1, 1);
   }
-  RhoArgs a{h->X, h->Rb, h->rho, h->logpr, h->par, h->slotR, h->lutg, h->Hg, h->slotF, 1};
   size_t sm = shmem_rho(g, mode != 2, mode != 0);
-  dim3 blk(TPB);
   int rc = VMR_OK;
   if (mode != 2 && !h->h_zero) {   // (after a fused k_fin_gamma both are zero already)
     if (g.fuse_full) HIPCHK(h, hipMemsetAsync(h->slotF, 0, (size_t)g.L * NSLOT * g.K * 8, h->stream));
@@ -2325,15 +1291,7 @@ static int launch_rho(vmr_ctx* h, int mode, bool commit_nu, bool raw_nu = false,
     if ((rc = det_fold(h))) return rc;
   } else {
     Prof p(h, mode == 2 ? VMR_KERNEL_ELBO : mode == 1 ? VMR_KERNEL_RHO_ELBO : VMR_KERNEL_RHO);
-#define LRHO(MUT_, UPD_, ELB_)                                                                  \
-  DISPATCH_KP(g.K, g.pf, if ((rc = grid_per_layer(h, k_rho<KK, MUT_, UPD_, ELB_, PP>, sm, &a.Gl))) return rc; \
-              hipLaunchKernelGGL((k_rho<KK, MUT_, UPD_, ELB_, PP>), dim3(g.L * a.Gl), blk, sm, h->stream, a, g))
-    if (g.mut) {
-      if (mode == 0) { LRHO(true, true, false); } else if (mode == 1) { LRHO(true, true, true); } else { LRHO(true, false, true); }
-    } else {
-      if (mode == 0) { LRHO(false, true, false); } else if (mode == 1) { LRHO(false, true, true); } else { LRHO(false, false, true); }
-    }
-#undef LRHO
+    if ((rc = tiles_rho(h, mode, sm))) return rc;
   }
   if (mode != 2) {
     h->f_valid = g.fuse_full != 0;
@@ -2351,1045 +1309,11 @@ static int launch_rho(vmr_ctx* h, int mode, bool commit_nu, bool raw_nu = false,
   return VMR_OK;
 }
 
-// lists_only: a vmr_create_coo handle, which never launches the dense tiles (their LDS bound does not limit M there)
-static int choose_geo(Geo& g, int ncu, std::string& err, bool lists_only) {
-  g.Mp = (g.M + 15) / 16 * 16;
-  g.nchunk = g.Mp / 16;
-  g.stride = (g.nchunk % 2 == 1) ? g.Mp : g.Mp + 16;
-  g.W = (g.M + 63) / 64;
-  const size_t budget = 48 * 1024;
-  // per-reporter LDS tables of the rho pass beside the tile pair (see shmem_rho): they cap the tile edge too
-  const size_t tables = (size_t)g.Mp * 8 * (2 + (g.mut ? g.K : 0)) + (size_t)g.W * 8 + shmem_q() + 256;
-  auto lds = [&](int b_) { return (size_t)2 * b_ * b_ * (g.stride + (size_t)g.W * 8 + 2 * g.K * 8 + 4) + tables; };
-  int b = 8;
-  while (b > 1 && ((size_t)2 * b * b * g.stride > budget || lds(b) > 160 * 1024)) b >>= 1;
-  if ((size_t)2 * b * b * g.stride > budget && !lists_only) { err = "M too large for the LDS tile (M <= ~24500 supported)"; return VMR_EINVAL; }
-  g.b = b; g.lb = (b == 8) ? 3 : (b == 4) ? 2 : (b == 2) ? 1 : 0;
-  g.nb = (g.N + b - 1) / b;
-  g.nt = 2 * b * b;
-  g.S = TPB / g.nt; if (g.S > 64) g.S = 64;
-  g.lS = 0; while ((1 << g.lS) < g.S) ++g.lS;
-  g.P = (long long)g.nb * (g.nb + 1) / 2;
-  g.Gl = 0;   // per launch, see grid_per_layer()
-  g.Y = 1;    // set by vmr_create once the largest count is known
-  g.hc = 0;
-  g.two_pass = 0;
-  g.farl = 0;
-  g.fuse_full = 0;
-  long long T = (long long)g.N * g.N;
-  long long gm = (long long)ncu * 8 / g.L; if (gm < 1) gm = 1;
-  long long maxgm = (T + 255) / 256; if (gm > maxgm) gm = maxgm; if (gm < 1) gm = 1;
-  g.Gm = (int)gm;
-  int need = (g.nt * g.nchunk + TPB - 1) / TPB;
-  g.pf = need <= 4 ? 4 : need <= 8 ? 8 : 12;
-  return VMR_OK;
-}
-
 extern "C" {
 
 const char* vmr_version(void) { return VMR_VERSION; }
 
 const char* vmr_last_error(vmr_handle h) { return h ? h->err.c_str() : g_create_err.c_str(); }
-
-}  // extern "C" (the create helpers are C++)
-
-// ------------------------------------------------------------------------------------------
-// vmr_create / vmr_create_coo
-// ------------------------------------------------------------------------------------------
-
-static void read_opts(VmrOpts& o) {
-  memset(&o, 0, sizeof o);   // (padding too: batch_kind compares records with memcmp)
-  auto set = [](const char* n) { return getenv(n) != nullptr; };
-  auto num = [](const char* n, int dflt) { const char* e = getenv(n); return e ? atoi(e) : dflt; };
-  if (const char* f = getenv("VMR_FORMAT")) o.format = !strcmp(f, "dense") ? 1 : !strcmp(f, "sparse") ? 2 : 0;
-  o.deterministic = num("VMR_DETERMINISTIC", 0) != 0;
-  o.graph = num("VMR_GRAPH", 0) != 0;
-  o.debug = num("VMR_DEBUG", 0);
-  o.levels = num("VMR_LEVELS", 64);
-  o.two_pass = num("VMR_TWO_PASS", 0);
-  o.farl = num("VMR_FARL", 0);
-  o.yt = set("VMR_YT") ? std::max(0, num("VMR_YT", 0)) : -1;
-  o.hc = set("VMR_HC") ? std::max(0, num("VMR_HC", 0)) : -1;
-  o.tpb = num("VMR_TPB", 0);
-  o.st_tpb = num("VMR_ST_TPB", 0);
-  o.no_level0 = set("VMR_NO_LEVEL0");
-  o.no_x0 = set("VMR_NO_X0");
-  o.no_lv0r = set("VMR_NO_LV0R");
-  o.no_level_sort = set("VMR_NO_LEVEL_SORT");
-  o.no_rlists = set("VMR_NO_RLISTS");
-  o.no_rm2 = set("VMR_NO_RM2");
-  o.no_lp0 = set("VMR_NO_LP0");
-  o.no_lpd = set("VMR_NO_LPD");
-  o.no_balance = set("VMR_NO_BALANCE");
-  o.always_store_rho = set("VMR_ALWAYS_STORE_RHO");
-  o.debug_lazy_rho = set("VMR_DEBUG_LAZY_RHO");
-  o.gen_hsum = num("VMR_GEN_HSUM", 0);
-  o.gen_no_lds_h = set("VMR_GEN_NO_LDS_H");
-  o.gen_dbg = num("VMR_GEN_DBG", 0);
-  o.netstats_chunk = std::max(0, num("VMR_NETSTATS_CHUNK", 0));
-  o.batch_fg = set("VMR_BATCH_FG") ? std::max(1, std::min(FG_G, num("VMR_BATCH_FG", 0))) : 0;
-  if (const char* t = getenv("VMR_DEBUG_TIMES")) snprintf(o.debug_times, sizeof o.debug_times, "%s", t);
-}
-
-// context, geometry, streams and the small per-dataset arrays
-static int create_ctx(vmr_ctx** out, hipDeviceProp_t* prop, int device, int L, int N, int M, int K, int mutuality, double eps, bool lists_only = false) {
-  if (L < 1 || N < 1 || M < 1) return fail(nullptr, VMR_EINVAL, "L, N, M must be positive");
-  if (K < 2 || K > KGEN_MAX) return fail(nullptr, VMR_EINVAL, "K must be in [2, 256]");
-  int ndev = 0;
-  CK(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev) return fail(nullptr, VMR_EINVAL, "no such HIP device");
-  CK(hipSetDevice(device));
-  CK(hipGetDeviceProperties(prop, device));
-  vmr_ctx* h = new vmr_ctx();
-  *out = h;
-  h->device = device;
-  Geo& g = h->g;
-  g.L = L; g.N = N; g.M = M; g.K = K; g.mut = mutuality ? 1 : 0; g.eps = eps;
-  g.gen = K > KMAX ? 1 : 0; g.wide = 0;   // (wide entries: decided once the largest count is known)
-  read_opts(h->opt);
-  g.dbg = h->opt.debug;
-  g.det = h->opt.deterministic ? 1 : 0; g.det_sh = 0; g.det_shr = 0; g.det_sha = 0;   // sorted report lists unless the older step layout is asked for
-  std::string err;
-  if (choose_geo(g, prop->multiProcessorCount, err, lists_only) != VMR_OK) return fail(nullptr, VMR_EINVAL, err.c_str());
-  memset(h->prof_ms, 0, sizeof h->prof_ms); memset(h->prof_n, 0, sizeof h->prof_n);
-  CK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  CK(hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
-  CK(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-  CK(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-  h->ncu = prop->multiProcessorCount;
-  h->use_graphs = h->opt.graph;   // (off by default: see vmr_ctx::graphs)
-  const size_t rows = (size_t)L * N * N;
-  CK(hipMalloc(&h->cov, rows));
-  CK(hipMalloc(&h->rcls, rows));
-  CK(hipMalloc(&h->sumx, 8));
-  CK(hipMemsetAsync(h->sumx, 0, 8, h->stream));
-  CK(hipMalloc(&h->xmax, 4));
-  CK(hipMemsetAsync(h->xmax, 0, 4, h->stream));
-  CK(hipMalloc(&h->npartial, 16));
-  CK(hipMemsetAsync(h->npartial, 0, 16, h->stream));
-  return VMR_OK;
-}
-
-// variational state and accumulation slots; reads back the data statistics (largest count, mask row classes)
-static int create_state(vmr_ctx* h, unsigned* xm_out) {
-  Geo& g = h->g;
-  const size_t rows = (size_t)g.L * g.N * g.N;
-  // (64 rows of zeroed slack: the sweep over the sorted lists reads whole 64-tie steps without masks)
-  CK(hipMalloc(&h->rho, (rows + 64) * g.K * 8));
-  CK(hipMalloc(&h->logpr, (rows + 64) * g.K * 8));
-  CK(hipMemsetAsync(h->rho + rows * g.K, 0, (size_t)64 * g.K * 8, h->stream));
-  CK(hipMemsetAsync(h->logpr + rows * g.K, 0, (size_t)64 * g.K * 8, h->stream));
-  ParOff o = par_off(g.L, g.Mp, g.K);
-  h->par_doubles = o.total;
-  CK(hipMalloc(&h->par, o.total * 8));
-  CK(hipMemsetAsync(h->par, 0, o.total * 8, h->stream));
-  const size_t nA = (size_t)g.L * NSLOT * g.W * 64 * g.K * 8;
-  CK(hipMalloc(&h->slotA, nA)); CK(hipMemsetAsync(h->slotA, 0, nA, h->stream));
-  CK(hipMalloc(&h->slotR, NSLOT * 4 * 8)); CK(hipMemsetAsync(h->slotR, 0, NSLOT * 4 * 8, h->stream));
-  g.fuse_full = 1;
-  CK(hipMalloc(&h->slotF, (size_t)g.L * NSLOT * g.K * 8));
-  CK(hipMemsetAsync(h->slotF, 0, (size_t)g.L * NSLOT * g.K * 8, h->stream));
-  CK(hipStreamSynchronize(h->stream));   // the stream is non-blocking: a plain hipMemcpy does not wait for it
-  unsigned xm = 0;
-  unsigned long long np2[2] = {0, 0};
-  CK(hipMemcpy(&xm, h->xmax, 4, hipMemcpyDeviceToHost));
-  CK(hipMemcpy(np2, h->npartial, 16, hipMemcpyDeviceToHost));
-  h->n_partial = np2[0];
-  h->all_full = (np2[0] == 0 && np2[1] == 0) ? 1 : 0;
-  g.Y = g.mut ? (int)xm + 1 : 1;   // mirror counts 0..max(X)
-  *xm_out = xm;
-  return VMR_OK;
-}
-
-int scan_u32(vmr_ctx* h, unsigned* a, unsigned* bsum, size_t n) {
-  const unsigned nb = (unsigned)((n + 2047) / 2048);
-  hipLaunchKernelGGL(k_scan_local, dim3(nb), dim3(256), 0, h->stream, a, bsum, n);
-  hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(256), 0, h->stream, bsum, (int)nb);
-  hipLaunchKernelGGL(k_scan_add, dim3(nb), dim3(256), 0, h->stream, a, bsum, n);
-  CK(hipGetLastError());
-  return VMR_OK;
-}
-
-
-// mask lists for partial rows that hold few reporters (self-reporter masks: two per row), from the bit-packed words
-static int mask_lists_from_words(vmr_ctx* h) {
-  Geo& g = h->g;
-  const int L = g.L, K = g.K;
-  const size_t T = (size_t)g.N * g.N, n = T + 1, rows = (size_t)L * T;
-  if (!(h->n_partial > 0) || h->opt.no_rlists) return VMR_OK;
-  unsigned long long* tot_dev = nullptr;
-  unsigned* max_dev = nullptr;
-  unsigned* bsum = nullptr;
-  CK(hipMalloc(&h->rq, (size_t)L * n * 4));
-  CK(hipMalloc(&tot_dev, (size_t)L * 8));
-  CK(hipMalloc(&max_dev, 4));
-  CK(hipMalloc(&bsum, (n + 2047) / 2048 * 4));
-  CK(hipMemsetAsync(tot_dev, 0, (size_t)L * 8, h->stream));
-  CK(hipMemsetAsync(max_dev, 0, 4, h->stream));
-  const unsigned rgrid = (unsigned)std::min<size_t>(4096, (T + 255) / 256);
-  for (int l = 0; l < L; ++l)
-    hipLaunchKernelGGL(k_rm_count, dim3(rgrid), dim3(256), 0, h->stream, h->Rb + (size_t)l * T * g.W,
-                       h->rcls + (size_t)l * T, h->rq + (size_t)l * n, tot_dev + l, max_dev, T, g.W);
-  CK(hipGetLastError());
-  CK(hipStreamSynchronize(h->stream));
-  std::vector<unsigned long long> rl_(L), rb_(L);
-  unsigned maxrow = 0;
-  CK(hipMemcpy(rl_.data(), tot_dev, (size_t)L * 8, hipMemcpyDeviceToHost));
-  CK(hipMemcpy(&maxrow, max_dev, 4, hipMemcpyDeviceToHost));
-  h->rm_maxrow = maxrow;
-  CK(hipFree(tot_dev));
-  CK(hipFree(max_dev));
-  bool ok32 = true;
-  h->n_rm = 0;
-  for (int l = 0; l < L; ++l) { rb_[l] = h->n_rm; h->n_rm += rl_[l]; ok32 = ok32 && rl_[l] < 0xffffffffull; }
-  // worth it when a list row is at most a quarter of the row's mask words (and rows are short: one lane walks a row) -- and
-  // for small networks whatever the bytes: the sweep's pass sums the lists on its way, a launch less per sweep where the
-  // launches are what a sweep costs
-  const double list_bytes = 2.0 * (double)h->n_rm + 4.0 * (double)rows, word_bytes = (double)h->n_partial * g.W * 8.0;
-  if (ok32 && maxrow <= 64 && (list_bytes * 4.0 <= word_bytes || g.N <= 1024) && (size_t)g.Mp * K * 8 <= 160 * 1024) {   // (A[Mp][K] of k_mask_lists lives in LDS)
-    for (int l = 0; l < L; ++l) { int rc = scan_u32(h, h->rq + (size_t)l * n, bsum, n); if (rc) return rc; }
-    CK(hipMalloc(&h->rbase, (size_t)L * 8));
-    CK(hipMemcpyAsync(h->rbase, rb_.data(), (size_t)L * 8, hipMemcpyHostToDevice, h->stream));
-    CK(hipMalloc(&h->Rm, ((size_t)h->n_rm + 64) * 2));
-    for (int l = 0; l < L; ++l)
-      hipLaunchKernelGGL(k_rm_fill, dim3(rgrid), dim3(256), 0, h->stream, h->Rb + (size_t)l * T * g.W,
-                         h->rcls + (size_t)l * T, h->rq + (size_t)l * n, h->Rm + rb_[l], T, g.W);
-    CK(hipGetLastError());
-    CK(hipStreamSynchronize(h->stream));
-  } else {
-    CK(hipFree(h->rq));
-    h->rq = nullptr;
-    h->n_rm = 0;
-  }
-  CK(hipFree(bsum));
-  return VMR_OK;
-}
-
-// sorted lists: the per-tie arrays the sweeps read, by position (the tie-order originals stay for the mask kernels)
-// reports per level (mirror count) of the sorted lists: hist[y], y clamped to 64; empty slots (x = 0, not in R) are skipped
-__global__ __launch_bounds__(256) void k_level_hist(const unsigned* __restrict__ E, unsigned long long n, int Mp, unsigned long long* __restrict__ hist) {
-  __shared__ unsigned long long sh[65];
-  for (int i = threadIdx.x; i < 65; i += 256) sh[i] = 0;
-  __syncthreads();
-  for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256) {
-    const unsigned e = E[i];
-    if (e == 0u) continue;
-    const unsigned y = SL_YM(e) / (unsigned)Mp;
-    atomicAdd(&sh[y < 64u ? y : 64u], 1ull);
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < 65; i += 256) if (sh[i]) atomicAdd(&hist[i], sh[i]);
-}
-
-// Geo::farl: (position, entry) of the reports of levels >= g.hc, layer by layer (k_far_collect)
-static int build_far_lists(vmr_ctx* h) {
-  const Geo& g = h->g;
-  const size_t T = (size_t)g.N * g.N, NS = (T + 63) / 64;
-  unsigned long long* cnt = nullptr;
-  unsigned long long* hd = nullptr;
-  struct Tmp { unsigned long long*& a; unsigned long long*& b; ~Tmp() { if (a) (void)hipFree(a); if (b) (void)hipFree(b); } } tmp_guard{cnt, hd};   // (freed on every way out)
-  CK(hipMalloc(&cnt, 8));
-  std::vector<unsigned long long> hist(65, 0);
-  CK(hipMalloc(&hd, 65 * 8));
-  CK(hipMemsetAsync(hd, 0, 65 * 8, h->stream));
-  hipLaunchKernelGGL(k_level_hist, dim3(1024), dim3(256), 0, h->stream, h->E, h->n_slots, g.Mp, hd);
-  CK(hipGetLastError());
-  CK(hipMemcpyAsync(hist.data(), hd, 65 * 8, hipMemcpyDeviceToHost, h->stream));
-  CK(hipStreamSynchronize(h->stream));
-  unsigned long long far = 0;
-  for (int y = std::min(g.hc, 64); y < 65; ++y) far += hist[y];   // (an upper bound: empty slots of a level count too)
-  CK(hipMalloc(&h->far_pos, (size_t)(far + 64) * 4));
-  CK(hipMalloc(&h->far_ent, (size_t)(far + 64) * 4));
-  h->far_off.assign(g.L + 1, 0ull);
-  std::vector<unsigned long long> eb(g.L);
-  CK(hipMemcpy(eb.data(), h->ebase, (size_t)g.L * 8, hipMemcpyDeviceToHost));
-  for (int l = 0; l < g.L; ++l) {
-    hipLaunchKernelGGL(k_far_first, dim3((unsigned)std::min<size_t>(8192, (NS + 3) / 4)), dim3(256), 0, h->stream, h->E + eb[l], h->rs + (size_t)l * (NS + 1),
-                       h->sy + (size_t)l * NS, NS, (unsigned)g.hc * (unsigned)g.Mp, (unsigned*)nullptr);
-    CK(hipGetLastError());
-    { const int rcb = sl_balance_layer(h, l, eb[l], (unsigned)g.hc * (unsigned)g.Mp); if (rcb) return rcb; }   // (before the positions are recorded)
-    CK(hipMemsetAsync(cnt, 0, 8, h->stream));
-    hipLaunchKernelGGL(k_far_collect, dim3((unsigned)std::min<size_t>(8192, (NS + 3) / 4)), dim3(256), 0, h->stream, h->E + eb[l], h->rs + (size_t)l * (NS + 1), NS,
-                       (unsigned)g.hc * (unsigned)g.Mp, h->far_pos + h->far_off[l], h->far_ent + h->far_off[l], cnt);
-    CK(hipGetLastError());
-    unsigned long long n = 0;
-    CK(hipMemcpyAsync(&n, cnt, 8, hipMemcpyDeviceToHost, h->stream));
-    CK(hipStreamSynchronize(h->stream));
-    h->far_off[l + 1] = h->far_off[l] + n;
-    if (h->far_off[l + 1] > far) return fail(nullptr, VMR_EHIP, "far lists: more reports than counted");
-  }
-  CK(hipMalloc(&h->far_base, (size_t)(g.L + 1) * 8));
-  CK(hipMemcpy(h->far_base, h->far_off.data(), (size_t)(g.L + 1) * 8, hipMemcpyHostToDevice));
-  return VMR_OK;
-}
-
-// the mask lists of at most two reporters, packed by sorted position (SlArgs::rm2)
-__global__ __launch_bounds__(256) void k_rm2(const unsigned* __restrict__ perm, const unsigned* __restrict__ rq, const unsigned short* __restrict__ Rm,
-                                             const unsigned long long* __restrict__ rbase, unsigned* __restrict__ out, size_t T, size_t NS, int L) {
-  const size_t n = (size_t)L * NS * 64;
-  for (size_t q = (size_t)blockIdx.x * 256 + threadIdx.x; q < n; q += (size_t)gridDim.x * 256) {
-    const size_t l = q / (NS * 64);
-    const unsigned tie = perm[q];
-    unsigned w = 0xffffffffu;
-    if (tie != 0xffffffffu) {
-      const unsigned q0 = rq[l * (T + 1) + tie], q1 = rq[l * (T + 1) + tie + 1];
-      const unsigned short* r = Rm + rbase[l];
-      const unsigned m0 = q1 > q0 ? r[q0] : 0xffffu, m1 = q1 > q0 + 1 ? r[q0 + 1] : 0xffffu;
-      w = m0 | (m1 << 16);
-    }
-    out[q] = w;
-  }
-}
-
-static int sl_finish(vmr_ctx* h) {
-  const Geo& g = h->g;
-  const size_t rows = (size_t)g.L * g.N * g.N;
-  int rc = VMR_OK;
-  if (!h->all_full) {
-    CK(hipMalloc(&h->cls_p, rows + 64));   // (64 entries of slack, as rho)
-    CK(hipMemsetAsync(h->cls_p + rows, 0, 64, h->stream));
-    if ((rc = sl_permute_u8(h, h->rcls, h->cls_p))) return rc;
-  }
-  if (g.mut && h->Qt) {
-    CK(hipMalloc(&h->Qt_p, (rows + 64) * 4));
-    CK(hipMemsetAsync(h->Qt_p + rows, 0, 64 * 4, h->stream));
-    if ((rc = sl_permute_u32(h, h->Qt, h->Qt_p))) return rc;
-    CK(hipStreamSynchronize(h->stream));
-    CK(hipFree(h->Qt)); h->Qt = nullptr;   // (only the sweeps read it)
-  }
-  return VMR_OK;
-}
-
-// VMR_DETERMINISTIC=1: the fixed-point scales (Geo::det_sh, det_shr) from the sum of all counts.  xbits: bits of the largest count
-// a single add into H can carry -- the sweep kernels convert such a term with the 1.5 * 2^52 trick, which holds |v| 2^sh < 2^51.
-static int det_scales(vmr_ctx* h, int xbits, int shr_max) {
-  Geo& g = h->g;
-  unsigned long long sx = 0;
-  CK(hipMemcpyAsync(&sx, h->sumx, 8, hipMemcpyDeviceToHost, h->stream));
-  CK(hipStreamSynchronize(h->stream));
-  int bits = 1;
-  while (bits < 62 && (sx >> bits) != 0ull) ++bits;
-  g.det_sh = std::max(0, std::min(51 - xbits, 61 - bits));   // (specialised kernels: counts of 11 bits, so <= 40)
-  const unsigned long long eb = 64ull * (sx + (unsigned long long)g.L * g.N * g.N * g.K);
-  int rbits = 1;
-  while (rbits < 62 && (eb >> rbits) != 0ull) ++rbits;
-  // Up to 34 the scale leaves room for eb itself (34: a term converted by the 1.5 * 2^52 trick, ELBO terms up to 2047 * |log eps| < 2^17).
-  // eb is no bound on what a partial can hold -- sum over ties of rho T E[lambda] grows with E[theta] -- so a finer scale (shr_max,
-  // where the terms are converted exactly) is taken only while 2^63 / 2^det_shr stays above 64 eb = 4096 (sum x + L N^2 K).
-  g.det_shr = std::max(std::min(34, std::max(0, 61 - rbits)), std::min(shr_max, 57 - rbits));
-  return VMR_OK;
-}
-
-// LDS shapes, the statistics / factor tables, scratch; for report lists the count-mode launch (constants C[l][y][m])
-static int create_tail(vmr_ctx* h, const hipDeviceProp_t& prop) {
-  Geo& g = h->g;
-  const int L = g.L, K = g.K;
-  g.ml = (h->sparse && h->rq) ? 1 : 0;
-  // (the self-reporter mask of survey data: lists of two; the general kernels take it on wide handles only, Mp > 8192)
-  if (g.ml && (!g.gen || g.Mp > 8192) && h->rm_maxrow <= 2 && !h->opt.no_rm2) {
-    const size_t T_ = (size_t)g.N * g.N, NS_ = (T_ + 63) / 64, n_ = (size_t)L * NS_ * 64;
-    CK(hipMalloc(&h->rm2, n_ * 4));
-    hipLaunchKernelGGL(k_rm2, dim3((unsigned)std::min<size_t>(4096, (n_ + 255) / 256)), dim3(256), 0, h->stream, h->perm, h->rq, h->Rm, h->rbase, h->rm2, T_, NS_, L);
-    CK(hipGetLastError());
-  }
-  if (g.gen) {
-    // the general kernels: one copy of H with every category, nothing in LDS, no constants C (sweep_gen.h)
-    g.ml = 0; g.hc = 0; g.yt = 0; g.two_pass = 0;
-    const double hb = (double)L * g.Y * g.Mp * K * 8.0;
-    size_t fr = 0, tot = 0;
-    CK(hipMemGetInfo(&fr, &tot));
-    if (hb > 0.5 * (double)fr) {
-      char msg[256];
-      snprintf(msg, sizeof msg, "the statistics table H[L][max count + 1][M][K] would take %.1f GB (largest count %d, M = %d, K = %d): more than half "
-               "of the device memory left", hb / 1e9, g.Y - 1, g.M, K);
-      return fail(nullptr, VMR_EINVAL, msg);
-    }
-    CK(hipMalloc(&h->Hg, (size_t)hb));
-    CK(hipMemsetAsync(h->Hg, 0, (size_t)hb, h->stream));
-    CK(hipMalloc(&h->gen_s1, (size_t)L * (g.Mp + K + 1) * 8));   // (zero between uses: the readers zero what they read)
-    CK(hipMemsetAsync(h->gen_s1, 0, (size_t)L * (g.Mp + K + 1) * 8, h->stream));
-    CK(hipMalloc(&h->elbo_dev, 8 * 8));
-    CK(hipMemsetAsync(h->elbo_dev, 0, 8 * 8, h->stream));
-    CK(hipMalloc(&h->nu_acc, (size_t)(3 + L) * 8));
-    CK(hipMemsetAsync(h->nu_acc, 0, (size_t)(3 + L) * 8, h->stream));
-    CK(hipMalloc(&h->lutg, (size_t)L * g.W * 256 * 8));
-    CK(hipMemsetAsync(h->lutg, 0, (size_t)L * g.W * 256 * 8, h->stream));
-    if (g.det) {
-      // VMR_DETERMINISTIC=1: H, the slots and gen_s1 hold the integer sums themselves (sweep_gen.hip), no shadow; the fixed point
-      // of H leaves room for the sum of all counts and for the largest count in one add
-      if (!h->sparse) return fail(nullptr, VMR_EINVAL, "VMR_DETERMINISTIC=1 needs the report lists (a sparse tensor)");
-      unsigned xm = 0;
-      CK(hipMemcpyAsync(&xm, h->xmax, 4, hipMemcpyDeviceToHost, h->stream));
-      CK(hipStreamSynchronize(h->stream));
-      int xbits = 1;
-      while (xbits < 32 && (xm >> xbits) != 0u) ++xbits;
-      int rc = det_scales(h, xbits, 34);
-      if (rc) return rc;
-      // sums of rho: a 64-bit cell (or a lane's sum) holds at most N^2 ties' worth; 2^-50 at most (the conversion trick, rho <= 1).
-      // (A fixed 2^-30 moved a K = 12 fit with many nearly empty categories 5e-8 from the default mode.)
-      const unsigned long long T_ = (unsigned long long)g.N * g.N;
-      int tbits = 1;
-      while (tbits < 62 && (T_ >> tbits) != 0ull) ++tbits;
-      g.det_sha = std::min(50, 62 - tbits);
-      CK(hipMalloc(&h->fr_slots, (size_t)L * FR_G * 2 * 8));
-      CK(hipMemsetAsync(h->fr_slots, 0, (size_t)L * FR_G * 2 * 8, h->stream));
-    }
-    CK(hipStreamSynchronize(h->stream));
-    return VMR_OK;
-  }
-  // LDS levels (mirror counts 0..) of the statistics H and, for report lists, of the factor table F.
-  g.hc = g.Y < HC_MAX ? g.Y : HC_MAX;
-  g.yt = 0;
-  g.two_pass = 0;
-  size_t need = 0;
-  if (h->sparse) {
-    // Sorted lists: the populous levels of F (read) and H (float atomics) in LDS, shared by all waves of a workgroup; no per-wave
-    // LDS at all.  One pass per sweep when every level of both fits at >= 16 waves per CU (or the levels beyond hold under 0.1 %
-    // of the reports), else the rho pass keeps F and a statistics pass rebuilds H (two passes over the entries).
-    const VmrOpts& o = h->opt;
-    const int want = std::max(1, std::min(g.Y, o.levels));   // as many levels as fit: with all of them in LDS nothing is "far"
-    // a variant's largest workgroup / waves per CU (registers): the statistics-only variant is lighter than the update's
-    auto cap_of = [&](bool upd) { return sl_tpb_max(K, false, h->all_full != 0, upd); };
-    auto wcu_of = [&](bool upd) { return 4 * sl_wpe(K, false, h->all_full != 0, upd); };
-    auto waves = [&](int tpb, int yt, int hc, bool upd, bool hist) {
-      const size_t b = sl_smem(g, yt, hc, upd, false, hist);
-      if (b > SP_LDS_MAX || tpb > cap_of(upd)) return 0;
-      const int nw = tpb / 64, wgs = std::min((int)(SP_LDS_MAX / b), wcu_of(upd) / nw);
-      return wgs * nw;
-    };
-    auto best = [&](bool upd, bool hist, int min_waves, int& lv_out, int& tpb_out) {
-      min_waves = std::min(min_waves, wcu_of(upd));
-      for (int lv = want; lv >= 1; --lv) {
-        int bw = 0, bt = 256;
-        for (int tpb : {1024, 768, 512, 256}) { const int w = waves(tpb, upd ? lv : 0, hist ? lv : 0, upd, hist); if (w > bw) { bw = w; bt = tpb; } }
-        if (bw >= min_waves) { lv_out = lv; tpb_out = bt; return true; }
-      }
-      return false;
-    };
-    int lv1 = 0, t1 = 256, lvr = 0, tr = 256, lvh = 0, th = 256;
-    bool want_farl = false;
-    bool one = best(true, true, 16, lv1, t1);
-    if (one && lv1 < want && g.N > 1024) {   // (small networks: one pass whatever the levels -- a sweep there costs its launches)
-      // Not every level fits beside the other table.  A report of a level beyond the LDS ones costs its whole 64-tie round the
-      // slow path (the factor formula, a global add), so one pass only pays while such reports are rare: count the reports
-      // per level.  (BASELINE config 5 -- M = 1000, K = 3: 3 levels of each fit, 2.5 % of the reports lie beyond, four rounds
-      // of five hold one; the two passes keep 6 levels of F and 9 of H.)
-      std::vector<unsigned long long> hist(65, 0);
-      unsigned long long* hd = nullptr;
-      CK(hipMalloc(&hd, 65 * 8));
-      CK(hipMemsetAsync(hd, 0, 65 * 8, h->stream));
-      hipLaunchKernelGGL(k_level_hist, dim3(1024), dim3(256), 0, h->stream, h->E, h->n_slots, g.Mp, hd);
-      CK(hipGetLastError());
-      CK(hipMemcpyAsync(hist.data(), hd, 65 * 8, hipMemcpyDeviceToHost, h->stream));
-      CK(hipStreamSynchronize(h->stream));
-      CK(hipFree(hd));
-      unsigned long long tot = 0, far = 0;
-      for (int y = 0; y < 65; ++y) { tot += hist[y]; if (y >= lv1) far += hist[y]; }
-      if ((double)far > (double)tot / 1024.0) {
-        // VMR_FARL=1 (round 4; off by default): still one pass while the far reports are a few per cent -- the pass takes their factors
-        // by formula and leaves their statistics to k_far_hist, which adds them from a compact list of exactly those reports, moved
-        // to the front of every tie's list (k_far_first).  Measured on a BASELINE config-5 layer: 3.44 ms per sweep against 3.53
-        // with two passes, and ELBO sweeps the other way round -- no gain over ten sweeps, so two passes stay.
-        // Not in the deterministic mode (its sums are the integer shadows').
-        if (g.mut && !g.det && o.farl && (double)far <= 0.125 * (double)tot) want_farl = true;
-        else one = false;
-      }
-    }
-    one = one && !o.two_pass;
-    if (one) { g.yt = g.hc = lv1; h->sp_tpb = h->st_tpb = t1; g.farl = want_farl ? 1 : 0; }
-    else {
-      g.two_pass = 1;
-      if (!best(true, false, 16, lvr, tr) && !best(true, false, 4, lvr, tr)) { lvr = 0; tr = 256; }
-      if (!best(false, true, 16, lvh, th) && !best(false, true, 4, lvh, th)) { lvh = 0; th = 256; }
-      g.yt = lvr; g.hc = lvh; h->sp_tpb = tr; h->st_tpb = th;
-    }
-    {   // small datasets: smaller workgroups, so that the steps spread over every CU
-      const long long NS = ((long long)g.N * g.N + 63) / 64;
-      for (int* t : {&h->sp_tpb, &h->st_tpb})
-        while (*t > 64 && NS * L < (long long)h->ncu * (*t / 64)) *t = std::max(64, (*t / 2) & ~63);   // (768 -> 384 -> 192 -> 64)
-    }
-    g.yt = std::max(0, std::min(g.Y, o.yt >= 0 ? o.yt : g.yt));
-    g.hc = std::max(0, std::min(g.Y, o.hc >= 0 ? o.hc : g.hc));
-    if (o.tpb >= 64 && o.tpb <= 1024 && o.tpb % 64 == 0) h->sp_tpb = o.tpb;
-    if (o.st_tpb >= 64 && o.st_tpb <= 1024 && o.st_tpb % 64 == 0) h->st_tpb = o.st_tpb;
-    for (int v = 0; v < 4; ++v) need = std::max(need, sl_shape(h, v != 3, v == 1 || v == 2, v == 0 || v == 1 || v == 3).smem);
-    if (g.two_pass && g.mut && !g.det && g.Y > 1 && !o.no_level0) {
-      // Two passes (a wide reporter dimension): the statistics pass is bound by its LDS adds, and at mirror count 0 -- more than half
-      // of the reports of a mutual network -- none is needed (SlArgs::h0s): every tie's reports of count >= 1 go first, sy's high half
-      // gets the first round of a step that holds level 0 only.
-      const size_t T_ = (size_t)g.N * g.N, NS_ = (T_ + 63) / 64;
-      std::vector<unsigned long long> eb(L);
-      CK(hipMemcpy(eb.data(), h->ebase, (size_t)L * 8, hipMemcpyDeviceToHost));
-      if (!o.no_x0) CK(hipMalloc(&h->x0p, (size_t)L * NS_ * 64 * 4));
-      for (int l = 0; l < L; ++l)
-        hipLaunchKernelGGL(k_far_first, dim3((unsigned)std::min<size_t>(8192, (NS_ + 3) / 4)), dim3(256), 0, h->stream, h->E + eb[l], h->rs + (size_t)l * (NS_ + 1),
-                           h->sy + (size_t)l * NS_, NS_, (unsigned)g.Mp, h->x0p ? h->x0p + (size_t)l * NS_ * 64 : nullptr);
-      CK(hipGetLastError());
-      for (int l = 0; l < L; ++l) { const int rcb = sl_balance_layer(h, l, eb[l], (unsigned)g.Mp); if (rcb) return rcb; }
-      if (h->x0p) {
-        unsigned long long* ss = nullptr;
-        CK(hipMalloc(&ss, 8));
-        CK(hipMemsetAsync(ss, 0, 8, h->stream));
-        for (int l = 0; l < L; ++l)
-          hipLaunchKernelGGL(k_stat_slots, dim3(256), dim3(256), 0, h->stream, h->rs + (size_t)l * (NS_ + 1), h->sy + (size_t)l * NS_, NS_, ss);
-        hipError_t es = hipMemcpyAsync(&h->stat_slots, ss, 8, hipMemcpyDeviceToHost, h->stream);
-        if (es == hipSuccess) es = hipStreamSynchronize(h->stream);
-        (void)hipFree(ss);
-        CK(es);
-      }
-      const size_t n0 = (size_t)L * NSLOT * K + L;
-      CK(hipMalloc(&h->h0s, n0 * 8));
-      CK(hipMemsetAsync(h->h0s, 0, n0 * 8, h->stream));
-    }
-    if (g.farl) {
-      // the far lists hold the reports of levels >= g.hc: every variant that adds to H must keep exactly the levels below in LDS
-      bool same = g.hc >= 1 && g.hc < g.Y;
-      for (int v : {0, 3}) same = same && sl_shape(h, v != 3, false, true).hc == g.hc;
-      h->elbo_split = sl_shape(h, true, true, true).hc != g.hc || sl_shape(h, true, true, true).yt != g.yt;   // (the fused ELBO variant also holds the logarithm table)
-      if (!same) g.farl = 0;   // (shapes forced through VMR_YT / VMR_HC / VMR_TPB: the pass then adds the far reports itself, global adds)
-      else { int rcf = build_far_lists(h); if (rcf) return rcf; }
-    }
-  } else {
-    if (shmem_rho(g, true, false) > 80000) {
-      g.two_pass = 1;
-      while (g.hc > 0 && shmem_hist(g) > 160000) --g.hc;
-    }
-    need = std::max(shmem_rho(g, true, true), shmem_hist(g));
-  }
-  // per-reporter tables live in LDS (dense tiles: E[log theta], the mutuality weights c[m,k], G_theta for the ELBO:
-  // (K + 2) * 8 bytes per reporter).  160 KB per workgroup on gfx950.
-  if (need > (size_t)prop.sharedMemPerBlock && need > 160 * 1024) {
-    char msg[256];
-    snprintf(msg, sizeof msg, "M = %d reporters with K = %d%s needs %zu bytes of LDS per workgroup (limit %d): "
-             "reduce M or K", g.M, K, g.mut ? " and mutuality" : "", need, 160 * 1024);
-    return fail(nullptr, VMR_EINVAL, msg);
-  }
-  CK(hipMalloc(&h->Hg, (size_t)L * NH * g.Y * g.Mp * K * 8));
-  CK(hipMemsetAsync(h->Hg, 0, (size_t)L * NH * g.Y * g.Mp * K * 8, h->stream));
-  CK(hipMalloc(&h->elbo_dev, 8 * 8));   // [0..3] results, [4..6] scratch of k_fin_rho
-  CK(hipMemsetAsync(h->elbo_dev, 0, 8 * 8, h->stream));
-  CK(hipMalloc(&h->nu_acc, (size_t)(3 + L) * 8));   // the nu update inside the pass (SlArgs::nu_acc)
-  CK(hipMemsetAsync(h->nu_acc, 0, (size_t)(3 + L) * 8, h->stream));
-  // k_fin_gamma: per layer 2 K sums and a ticket; behind them, for the deterministic mode, every workgroup's own 2 K sums
-  CK(hipMalloc(&h->fin_g, ((size_t)L * (2 * KMAX + 2) + (size_t)L * FG_G * 2 * KMAX) * 8));
-  CK(hipMemsetAsync(h->fin_g, 0, ((size_t)L * (2 * KMAX + 2) + (size_t)L * FG_G * 2 * KMAX) * 8, h->stream));
-  if (g.det) {
-    // VMR_DETERMINISTIC=1 (sorted report lists only): see SlArgs::det.  The fixed point of the count-weighted sums leaves
-    // room for the sum of all counts.
-    if (!h->sparse) return fail(nullptr, VMR_EINVAL, "VMR_DETERMINISTIC=1 needs the report lists (a sparse tensor with M <= 8192, counts <= 2047)");
-    int rc = det_scales(h, 11, 45);   // (packed entries: counts up to 2047; the ELBO terms are converted exactly, whatever their size)
-    if (rc) return rc;
-    // sums of rho: a 64-bit cell holds at most N^2 ties' worth, and one conversion a wave's 64 values (64 rho 2^42 < 2^51 up to rho = 4).
-    // (A fixed 2^-30 left gamma_rte 1.3e-9 from the reference where most rows of rho are all zero and a category's few tiny values
-    // meet a large E[lambda]: tests/test_hip_exp_range.py.)
-    const unsigned long long T_ = (unsigned long long)g.N * g.N;
-    int tbits = 1;
-    while (tbits < 62 && (T_ >> tbits) != 0ull) ++tbits;
-    g.det_sha = std::min(42, 62 - tbits);
-    const size_t nd = (size_t)L * g.Y * g.Mp * K + (size_t)L * g.W * 64 * K + (size_t)L * K + 5;
-    CK(hipMalloc(&h->det_buf, nd * 8));
-    CK(hipMemsetAsync(h->det_buf, 0, nd * 8, h->stream));
-    CK(hipMalloc(&h->fr_slots, (size_t)L * FR_G * 2 * 8));
-    CK(hipMemsetAsync(h->fr_slots, 0, (size_t)L * FR_G * 2 * 8, h->stream));
-  }
-  CK(hipMalloc(&h->lutg, (size_t)L * g.W * 256 * 8));
-  CK(hipMemsetAsync(h->lutg, 0, (size_t)L * g.W * 256 * 8, h->stream));
-  if (h->sparse) {
-    // the constants C[l][y][m] = sum of the counts per (mirror count, reporter): one statistics launch in count mode
-    CK(hipMalloc(&h->Cg, (size_t)L * g.Y * g.Mp * 8));
-    int rc = VMR_OK;
-    {
-      const SlShape sh = sl_shape(h, false, false, true);
-      SlArgs a = sl_args(h, sh, 2);
-      rc = sl_launch(h, 3, sh, a);
-      if (rc == VMR_OK && g.farl) rc = launch_far(h, 1, -1);
-    }
-    if (rc != VMR_OK) { g_create_err = h->err; return rc; }
-    CK(hipGetLastError());
-    const size_t nit = (size_t)L * g.Y * g.Mp;
-    hipLaunchKernelGGL(k_take_counts, dim3((unsigned)std::min<size_t>(1024, (nit + TPB - 1) / TPB)), dim3(TPB), 0, h->stream, h->Hg, h->Cg, g);
-    CK(hipGetLastError());
-    if (h->h0s) {
-      hipLaunchKernelGGL(k_level0_total, dim3(L), dim3(256), 0, h->stream, h->Cg, h->h0s, g);
-      CK(hipGetLastError());
-    }
-
-  }
-  CK(hipStreamSynchronize(h->stream));
-  return VMR_OK;
-}
-
-static int create_dense(vmr_ctx* h, const hipDeviceProp_t& prop, const uint8_t* X, const uint8_t* R, int data_on_device) {
-  Geo& g = h->g;
-  const int L = g.L, N = g.N, M = g.M;
-  const size_t T = (size_t)N * N, rows = (size_t)L * T, raw = rows * M;
-  const size_t slack = (size_t)g.b * N + g.b;   // tile streams may read (never use) rows past the last tie
-  CK(hipMalloc(&h->X, (rows + slack) * g.Mp));
-  CK(hipMemsetAsync(h->X + rows * g.Mp, 0, slack * g.Mp, h->stream));
-  CK(hipMalloc(&h->Rb, (rows + slack) * g.W * 8));
-  CK(hipMemsetAsync(h->Rb + rows * g.W, 0, slack * g.W * 8, h->stream));
-  {
-    uint8_t* tmp = nullptr;
-    const uint8_t* src = X;
-    if (!data_on_device) { CK(hipMalloc(&tmp, raw)); CK(hipMemcpyAsync(tmp, X, raw, hipMemcpyHostToDevice, h->stream)); src = tmp; }
-    hipLaunchKernelGGL(k_pack_x, dim3(4096), dim3(256), 0, h->stream, src, h->X, rows, M, g.Mp);
-    CK(hipGetLastError());
-    CK(hipStreamSynchronize(h->stream));
-    if (tmp) CK(hipFree(tmp));
-    tmp = nullptr; src = R;
-    if (R && !data_on_device) { CK(hipMalloc(&tmp, raw)); CK(hipMemcpyAsync(tmp, R, raw, hipMemcpyHostToDevice, h->stream)); src = tmp; }
-    hipLaunchKernelGGL(k_pack_r, dim3(4096), dim3(256), 0, h->stream, src, h->Rb, rows, M, g.W);
-    CK(hipGetLastError());
-    hipLaunchKernelGGL(k_stats, dim3(2048), dim3(256), 0, h->stream, h->X, h->Rb, h->cov, h->rcls, h->sumx, h->xmax, h->npartial, rows, g.Mp, g.W, M);
-    CK(hipGetLastError());
-    CK(hipStreamSynchronize(h->stream));
-    if (tmp) CK(hipFree(tmp));
-  }
-  unsigned xm = 0;
-  int rc = create_state(h, &xm);
-  if (rc) return rc;
-  // ---- data format: report lists unless X is dense enough that 1 B per (tie, reporter) is less to read ----
-  const bool force_dense = h->opt.format == 1, force_sparse = h->opt.format == 2;
-  // 13-bit reporter field; the sorted lists hold counts <= 2047 and (max count + 1) * Mp <= 2^20 table rows, the step layout counts <= 63
-  const bool packed_ok = g.Mp <= 8192 && xm <= SL_XMAX && (size_t)(xm + 1) * g.Mp <= SL_YM_ROWS;
-  // beyond KMAX categories there is no dense-tile kernel: the general kernels run on report lists, with wide entries where the
-  // packed ones cannot hold the tensor (a uint8 tensor always fits: 256 levels x Mp rows < 2^32)
-  const bool need_lists = g.K > KMAX;
-  if (need_lists && force_dense) return fail(nullptr, VMR_EINVAL, "VMR_FORMAT=dense: the dense tile kernels hold at most 8 categories");
-  // ... and so do tensors the dense tiles cannot hold at all (their per-reporter tables outgrow the LDS: M of several thousand)
-  bool dense_fits = true;
-  {
-    Geo t = g;   // (what create_tail would settle on for the dense tiles)
-    t.Y = g.Y; t.hc = t.Y < HC_MAX ? t.Y : HC_MAX;
-    if (shmem_rho(t, true, false) > 80000) { t.two_pass = 1; while (t.hc > 0 && shmem_hist(t) > 160000) --t.hc; }
-    dense_fits = std::max(shmem_rho(t, true, true), shmem_hist(t)) <= (size_t)160 * 1024;
-  }
-  const bool can_list = packed_ok || need_lists || force_sparse || !dense_fits;   // (VMR_FORMAT=sparse: wide entries for what the packed ones cannot hold)
-  if (!force_dense && can_list) {
-    g.wide = packed_ok ? 0 : 1;
-    unsigned* rp = nullptr;   // [L][T+1] per-tie entry offsets: only needed to place the entries
-    CK(hipMalloc(&rp, (size_t)L * (T + 1) * 4));
-    unsigned long long* nnz_dev = nullptr;
-    CK(hipMalloc(&nnz_dev, (size_t)L * 8));
-    CK(hipMemsetAsync(nnz_dev, 0, (size_t)L * 8, h->stream));
-    const unsigned cgrid = (unsigned)std::min<size_t>(8192, (T + 15) / 16);
-    for (int l = 0; l < L; ++l)
-      hipLaunchKernelGGL(k_sp_count, dim3(cgrid), dim3(256), 0, h->stream, h->X + (size_t)l * T * g.Mp,
-                         rp + (size_t)l * (T + 1), nnz_dev + l, g);
-    CK(hipGetLastError());
-    CK(hipStreamSynchronize(h->stream));
-    std::vector<unsigned long long> nl(L);
-    CK(hipMemcpy(nl.data(), nnz_dev, (size_t)L * 8, hipMemcpyDeviceToHost));
-    CK(hipFree(nnz_dev));
-    bool fits = true;
-    h->nnz = 0;
-    for (int l = 0; l < L; ++l) { h->nnz += nl[l]; fits = fits && nl[l] < 0xffffffffull; }
-    const double sparse_bytes = 4.0 * (double)h->nnz + 4.0 * (double)rows, dense_bytes = (double)rows * g.Mp;
-    if (need_lists && !fits) { (void)hipFree(rp); return fail(nullptr, VMR_EINVAL, "more than 2^32 reports in one layer"); }
-    h->sparse = fits && (force_sparse || need_lists || !dense_fits || sparse_bytes <= 0.5 * dense_bytes);
-    if (!h->sparse) g.wide = 0;
-    g.gen = (h->sparse && (need_lists || g.wide)) ? 1 : 0;
-    if (h->sparse) {
-      CK(hipMalloc(&h->Qt, rows * 4));
-      CK(hipMemsetAsync(h->Qt, 0, rows * 4, h->stream));
-      auto fill_layer = [&](int l, const unsigned* rpl, unsigned* etmp, unsigned* etmp2) {
-        if (g.mut)
-          hipLaunchKernelGGL(k_sp_fill<true>, dim3(cgrid), dim3(256), 0, h->stream, h->X + (size_t)l * T * g.Mp,
-                             h->Rb + (size_t)l * T * g.W, rpl, etmp, etmp2, h->Qt + (size_t)l * T, g);
-        else
-          hipLaunchKernelGGL(k_sp_fill<false>, dim3(cgrid), dim3(256), 0, h->stream, h->X + (size_t)l * T * g.Mp,
-                             h->Rb + (size_t)l * T * g.W, rpl, etmp, etmp2, h->Qt + (size_t)l * T, g);
-      };
-      {
-        const SlFill ff = fill_layer;
-        rc = sl_place_entries(h, rp, nl, nullptr, nullptr, &ff);
-        if (!rc) rc = sl_finish(h);
-      }
-      if (!rc) rc = mask_lists_from_words(h);
-      if (!rc) { CK(hipFree(h->X)); h->X = nullptr; }   // the lists replace the dense tensor
-    }
-    CK(hipFree(rp));
-    if (rc) return rc;
-  } else if (force_sparse) {
-    return fail(nullptr, VMR_EINVAL, "VMR_FORMAT=sparse needs M <= 8192, counts <= 2047 and (largest count + 1) * M <= 2^20");
-  }
-  return create_tail(h, prop);
-}
-
-extern "C" int vmr_create(vmr_handle* out, int device, int L, int N, int M, int K, int mutuality, const uint8_t* X,
-                          const uint8_t* R, int data_on_device, double eps) {
-  if (!out) return fail(nullptr, VMR_EINVAL, "out is NULL");
-  *out = nullptr;
-  if (L < 1 || N < 1 || M < 1) return fail(nullptr, VMR_EINVAL, "L, N, M must be positive");
-  if (K < 2 || K > KGEN_MAX) return fail(nullptr, VMR_EINVAL, "K must be in [2, 256]");
-  if (!X) return fail(nullptr, VMR_EINVAL, "X is NULL");
-  vmr_ctx* h = nullptr;
-  hipDeviceProp_t prop;
-  int rc = create_ctx(&h, &prop, device, L, N, M, K, mutuality, eps);
-  if (!rc) rc = create_dense(h, prop, X, R, data_on_device);
-  if (rc) { if (h) vmr_destroy(h); return rc; }
-  *out = h;
-  return VMR_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// vmr_create_coo: coordinate lists (what the reference holds: sptensor subs / vals, model.py:136-171; the reader's output,
-// _io.py:132-295) straight to report lists -- no dense [L,N,N,M] tensor anywhere.  A Karnataka village layer is 624
-// reports against a 34 MB dense tensor; a layer of BASELINE config 5 is 5 GB of reports against 64 GB.
-// Reports and mask entries are sorted by (layer, tie, reporter) (one 64-bit radix sort each); sorted order IS the tie-major
-// order k_sp_round consumes, the mirror count and the mask bit of a report are binary searches in the sorted keys, and a
-// sparse mask becomes the mask lists directly.
-// A key is tie << mb | m, with mb = max(13, ceil(log2 Mp)) bits for the reporter (vmr_ctx::coo_mb): 13 up to Mp = 8192, up to
-// 16 at M = 65535 (the mask lists hold 16-bit reporters).
-// ------------------------------------------------------------------------------------------
-#define COO_KEY(tie, m, mb) (((unsigned long long)(tie) << (mb)) | (unsigned long long)(m))
-#define COO_M(key, mb) ((unsigned)((key) & ((1ull << (mb)) - 1ull)))
-
-__global__ void k_coo_keys(const int32_t* __restrict__ sl, const int32_t* __restrict__ si, const int32_t* __restrict__ sj,
-                           const int32_t* __restrict__ sm, long long n, int L, int N, int M, int mb, unsigned long long* __restrict__ keys,
-                           int* bad) {
-  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
-    const int l = sl[e], i = si[e], j = sj[e], m = sm[e];
-    if (l < 0 || l >= L || i < 0 || i >= N || j < 0 || j >= N || m < 0 || m >= M) { atomicOr(bad, 1); keys[e] = ~0ull; continue; }
-    keys[e] = COO_KEY(((unsigned long long)l * N + i) * N + j, m, mb);
-  }
-}
-// index of `key` in the sorted keys, or -1
-__device__ __forceinline__ long long coo_find(const unsigned long long* __restrict__ k, long long n, unsigned long long key) {
-  long long a = 0, b = n;
-  while (a < b) {
-    const long long c = a + ((b - a) >> 1);
-    if (k[c] < key) a = c + 1; else b = c;
-  }
-  return (a < n && k[a] == key) ? a : -1;
-}
-// per-tie counts of the sorted keys (cnt [L][T+1], layer-relative ties); duplicates flagged
-__global__ void k_coo_count(const unsigned long long* __restrict__ k, long long n, size_t T, int mb, unsigned* __restrict__ cnt, int* bad) {
-  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
-    if (e > 0 && k[e] == k[e - 1]) atomicOr(bad, 2);
-    const unsigned long long tie = k[e] >> mb, l = tie / T;
-    atomicAdd(&cnt[l * (T + 1) + (tie - l * T)], 1u);
-  }
-}
-// per tie: coverage, mask row class, statistics of the partial rows
-__global__ void k_coo_class(const unsigned* __restrict__ cx, const unsigned* __restrict__ cr /*null: all ones*/, size_t T, int L, int M,
-                            uint8_t* __restrict__ cov, uint8_t* __restrict__ rcls, unsigned long long* npartial, unsigned* maxrow) {
-  unsigned long long lpart = 0, lempty = 0;
-  unsigned mx = 0;
-  for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < (size_t)L * T; q += (size_t)gridDim.x * blockDim.x) {
-    const size_t l = q / T, t = q - l * T;
-    const unsigned nX = cx[l * (T + 1) + t], nR = cr ? cr[l * (T + 1) + t] : (unsigned)M;
-    cov[q] = (nX > 0 && nR > 0) ? 1 : 0;
-    const unsigned c = nR == 0 ? 0u : (nR == (unsigned)M ? 1u : 2u);
-    rcls[q] = (uint8_t)c;
-    if (c == 2u) { ++lpart; mx = max(mx, nR); }
-    if (c == 0u) ++lempty;
-  }
-  if (lpart) atomicAdd(npartial, lpart);
-  if (lempty) atomicAdd(npartial + 1, lempty);
-  if (mx) atomicMax(maxrow, mx);
-}
-// the reports' entries in tie-major (= sorted) order, the mirror sums Qt, sum and maximum of the counts
-template <bool MUT>
-__global__ void k_coo_entries(const unsigned long long* __restrict__ kx, const unsigned* __restrict__ vx, long long nx,
-                              const unsigned long long* __restrict__ kr, long long nr /* < 0: all ones */, int N, int Mp, int mb,
-                              unsigned* __restrict__ etmp, unsigned* __restrict__ etmp2, unsigned* __restrict__ Qt, unsigned long long* sumx, unsigned* xmax, int* bad) {
-  unsigned long long s = 0;
-  unsigned mx = 0;
-  const unsigned long long T = (unsigned long long)N * N;
-  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < nx; e += (long long)gridDim.x * blockDim.x) {
-    const unsigned long long key = kx[e], tie = key >> mb, l = tie / T, t = tie - l * T, i = t / N, j = t - i * N;
-    const unsigned m = COO_M(key, mb), x = vx[e];
-    if (x == 0u || x > 0x7fffffffu) { atomicOr(bad, 4); continue; }   // (int32 values: zero or negative)
-    s += x; mx = max(mx, x);
-    const unsigned long long tm = l * T + j * N + i;
-    unsigned y = 0;
-    if (MUT) {
-      const long long f = coo_find(kx, nx, COO_KEY(tm, m, mb));
-      y = f >= 0 ? vx[f] : 0u;
-      if (nr < 0 || coo_find(kr, nr, COO_KEY(tm, m, mb)) >= 0) atomicAdd(&Qt[tm], x);   // R[mirror, m] X[this, m]
-    }
-    const unsigned inr = (nr < 0 || coo_find(kr, nr, key) >= 0) ? 1u : 0u;
-    // two words per entry (sweep_sl.h, wide entries); k_coo_pack folds them into one where the packed format holds the tensor
-    const unsigned long long row = (unsigned long long)y * (unsigned)Mp + m;
-    if (row > 0xffffffffull) atomicOr(bad, 8);
-    etmp[e] = (unsigned)row;
-    etmp2[e] = (x << 1) | inr;
-  }
-  if (s) atomicAdd(sumx, s);
-  if (mx) atomicMax(xmax, mx);
-}
-__global__ void k_coo_pack(unsigned* __restrict__ etmp, const unsigned* __restrict__ etmp2, long long n) {
-  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) {
-    const unsigned w = etmp2[e];
-    etmp[e] = etmp[e] | ((w & 1u) << 20) | ((w >> 1) << 21);
-  }
-}
-// first sorted key of every layer (starts[L] = n)
-__global__ void k_coo_layer_starts(const unsigned long long* __restrict__ k, long long n, unsigned long long T, int L, int mb, unsigned long long* starts) {
-  for (int l = threadIdx.x; l <= L; l += blockDim.x) {
-    const unsigned long long k0 = ((unsigned long long)l * T) << mb;
-    long long a = 0, b = n;
-    while (a < b) { const long long c = a + ((b - a) >> 1); if (k[c] < k0) a = c + 1; else b = c; }
-    starts[l] = (unsigned long long)a;
-  }
-}
-// listed counts of the partial rows only
-__global__ void k_coo_listed(const unsigned* __restrict__ cr, const uint8_t* __restrict__ rcls, size_t T, int L, unsigned* __restrict__ rq) {
-  for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < (size_t)L * (T + 1); q += (size_t)gridDim.x * blockDim.x) {
-    const size_t l = q / (T + 1), t = q - l * (T + 1);
-    rq[q] = (t < T && rcls[l * T + t] == 2) ? cr[q] : 0u;
-  }
-}
-// reporters of the partial rows into the mask lists (rq scanned per layer; rbase: layer offsets)
-__global__ void k_coo_rm(const unsigned long long* __restrict__ kr, long long nr, size_t T, int mb, const uint8_t* __restrict__ rcls,
-                         const unsigned* __restrict__ rq, const unsigned long long* __restrict__ rbase, unsigned short* __restrict__ Rm) {
-  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < nr; e += (long long)gridDim.x * blockDim.x) {
-    const unsigned long long tie = kr[e] >> mb, l = tie / T, t = tie - l * T;
-    if (rcls[tie] != 2) continue;
-    long long a = 0, b = e;   // first entry of this tie: lower bound of tie << mb in [0, e]
-    const unsigned long long k0 = tie << mb;
-    while (a < b) { const long long c = a + ((b - a) >> 1); if (kr[c] < k0) a = c + 1; else b = c; }
-    Rm[rbase[l] + rq[l * (T + 1) + t] + (unsigned long long)(e - a)] = (unsigned short)COO_M(kr[e], mb);
-  }
-}
-// a mask whose partial rows are long: bit-packed words as in the dense path
-__global__ void k_coo_rbits(const unsigned long long* __restrict__ kr, long long nr, int W, int mb, unsigned long long* __restrict__ Rb) {
-  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < nr; e += (long long)gridDim.x * blockDim.x) {
-    const unsigned long long tie = kr[e] >> mb;
-    const unsigned m = COO_M(kr[e], mb);
-    atomicOr(&Rb[tie * W + (m >> 6)], 1ull << (m & 63));
-  }
-}
-
-// sorted keys (and values) of a coordinate list on the device; *k_out, *v_out are hipMalloc'ed
-static int coo_sorted(vmr_ctx* h, long long n, const int32_t* sl, const int32_t* si, const int32_t* sj, const int32_t* sm,
-                      const int32_t* sv, int on_device, unsigned long long** k_out, unsigned** v_out, int* bad_dev) {
-  const Geo& g = h->g;
-  *k_out = nullptr;
-  if (v_out) *v_out = nullptr;
-  const size_t nn = (size_t)std::max<long long>(n, 1);
-  const int32_t* src[5] = {sl, si, sj, sm, sv};
-  int32_t* tmp[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  const int ncol = sv ? 5 : 4;
-  if (!on_device) {
-    for (int c = 0; c < ncol; ++c) {
-      CK(hipMalloc(&tmp[c], nn * 4));
-      if (n > 0) CK(hipMemcpyAsync(tmp[c], src[c], (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
-      src[c] = tmp[c];
-    }
-  }
-  unsigned long long *k0 = nullptr, *k1 = nullptr;
-  unsigned* v1 = nullptr;
-  CK(hipMalloc(&k0, nn * 8));
-  CK(hipMalloc(&k1, nn * 8));
-  if (sv) CK(hipMalloc(&v1, nn * 4));
-  const unsigned grid = (unsigned)std::min<long long>(4096, (n + 255) / 256 + 1);
-  const int mb = h->coo_mb;
-  hipLaunchKernelGGL(k_coo_keys, dim3(grid), dim3(256), 0, h->stream, src[0], src[1], src[2], src[3], n, g.L, g.N, g.M, mb, k0, bad_dev);
-  CK(hipGetLastError());
-  int bits = mb;   // (the sort's bit range: mb reporter bits and ceil(log2(L N^2)) tie bits; create_coo checked it is <= 64)
-  { unsigned long long ties = (unsigned long long)g.L * g.N * g.N; while ((1ull << (bits - mb)) < ties && bits < 64) ++bits; }
-  size_t tb = 0;
-  void* td = nullptr;
-  if (n > 0) {
-    if (sv) CK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, k0, k1, reinterpret_cast<const unsigned*>(src[4]), v1, (int)n, 0, bits, h->stream));
-    else CK(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, k0, k1, (int)n, 0, bits, h->stream));
-    CK(hipMalloc(&td, tb ? tb : 8));
-    if (sv) CK(hipcub::DeviceRadixSort::SortPairs(td, tb, k0, k1, reinterpret_cast<const unsigned*>(src[4]), v1, (int)n, 0, bits, h->stream));
-    else CK(hipcub::DeviceRadixSort::SortKeys(td, tb, k0, k1, (int)n, 0, bits, h->stream));
-  }
-  CK(hipStreamSynchronize(h->stream));
-  if (td) CK(hipFree(td));
-  CK(hipFree(k0));
-  for (int c = 0; c < ncol; ++c) if (tmp[c]) CK(hipFree(tmp[c]));
-  *k_out = k1;
-  if (v_out) *v_out = v1;
-  return VMR_OK;
-}
-
-static int create_coo(vmr_ctx* h, const hipDeviceProp_t& prop, long long nx, const int32_t* xl, const int32_t* xi, const int32_t* xj,
-                      const int32_t* xm, const int32_t* xv, long long nr, const int32_t* rl, const int32_t* ri, const int32_t* rj,
-                      const int32_t* rm, int on_device) {
-  Geo& g = h->g;
-  const int L = g.L, N = g.N, M = g.M, K = g.K;
-  const size_t T = (size_t)N * N, rows = (size_t)L * T, n1 = (size_t)L * (T + 1);
-  const int mb = h->coo_mb;
-  if (nx >= 0x7fffffffll || nr >= 0x7fffffffll) return fail(nullptr, VMR_EINVAL, "more than 2^31 coordinates in one call");
-  int* bad_dev = nullptr;
-  CK(hipMalloc(&bad_dev, 4));
-  CK(hipMemsetAsync(bad_dev, 0, 4, h->stream));
-  unsigned long long *kx = nullptr, *kr = nullptr;
-  unsigned* vx = nullptr;
-  int rc = coo_sorted(h, nx, xl, xi, xj, xm, xv, on_device, &kx, &vx, bad_dev);
-  if (!rc && nr >= 0) rc = coo_sorted(h, nr, rl, ri, rj, rm, nullptr, on_device, &kr, nullptr, bad_dev);
-  unsigned *cx = nullptr, *cr = nullptr, *etmp = nullptr, *etmp2 = nullptr, *maxrow_dev = nullptr;
-  auto cleanup = [&]() { void* p[] = {bad_dev, kx, kr, vx, cx, cr, etmp, etmp2, maxrow_dev}; for (void* q : p) if (q) (void)hipFree(q); };
-  if (rc) { cleanup(); return rc; }
-  {   // subscripts outside the tensor must not reach the kernels below (their keys index the per-tie arrays)
-    int bad0 = 0;
-    hipError_t e0 = hipMemcpy(&bad0, bad_dev, 4, hipMemcpyDeviceToHost);   // (coo_sorted synchronised the stream)
-    if (e0 != hipSuccess) { g_create_err = hipGetErrorString(e0); cleanup(); return VMR_EHIP; }
-    if (bad0 & 1) { cleanup(); return fail(nullptr, VMR_EINVAL, "a subscript lies outside (L, N, N, M)"); }
-  }
-#define CKC(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { g_create_err = std::string(#call) + ": " + hipGetErrorString(e_); (void)hipGetLastError(); cleanup(); return VMR_EHIP; } } while (0)
-  CKC(hipMalloc(&cx, n1 * 4));
-  CKC(hipMemsetAsync(cx, 0, n1 * 4, h->stream));
-  const unsigned gx = (unsigned)std::min<long long>(8192, (nx + 255) / 256 + 1), gr = (unsigned)std::min<long long>(8192, (std::max<long long>(nr, 0) + 255) / 256 + 1);
-  hipLaunchKernelGGL(k_coo_count, dim3(gx), dim3(256), 0, h->stream, kx, nx, T, mb, cx, bad_dev);
-  if (nr >= 0) {
-    CKC(hipMalloc(&cr, n1 * 4));
-    CKC(hipMemsetAsync(cr, 0, n1 * 4, h->stream));
-    hipLaunchKernelGGL(k_coo_count, dim3(gr), dim3(256), 0, h->stream, kr, nr, T, mb, cr, bad_dev);
-  }
-  CKC(hipMalloc(&maxrow_dev, 4));
-  CKC(hipMemsetAsync(maxrow_dev, 0, 4, h->stream));
-  hipLaunchKernelGGL(k_coo_class, dim3((unsigned)std::min<size_t>(4096, (rows + 255) / 256)), dim3(256), 0, h->stream, cx, cr, T, L, M,
-                     h->cov, h->rcls, h->npartial, maxrow_dev);
-  CKC(hipMalloc(&etmp, ((size_t)nx + 64) * 4));
-  CKC(hipMalloc(&etmp2, ((size_t)nx + 64) * 4));
-  CKC(hipMalloc(&h->Qt, rows * 4));
-  CKC(hipMemsetAsync(h->Qt, 0, rows * 4, h->stream));
-  if (g.mut) hipLaunchKernelGGL(k_coo_entries<true>, dim3(gx), dim3(256), 0, h->stream, kx, vx, nx, kr, nr, N, g.Mp, mb, etmp, etmp2, h->Qt, h->sumx, h->xmax, bad_dev);
-  else hipLaunchKernelGGL(k_coo_entries<false>, dim3(gx), dim3(256), 0, h->stream, kx, vx, nx, kr, nr, N, g.Mp, mb, etmp, etmp2, h->Qt, h->sumx, h->xmax, bad_dev);
-  CKC(hipGetLastError());
-  CKC(hipStreamSynchronize(h->stream));
-  int bad = 0;
-  unsigned maxrow = 0;
-  CKC(hipMemcpy(&bad, bad_dev, 4, hipMemcpyDeviceToHost));
-  CKC(hipMemcpy(&maxrow, maxrow_dev, 4, hipMemcpyDeviceToHost));
-  h->rm_maxrow = maxrow;
-  if (bad) {
-    cleanup();
-    return fail(nullptr, VMR_EINVAL, (bad & 1) ? "a subscript lies outside (L, N, N, M)"
-                                   : (bad & 2) ? "duplicate (l, i, j, m) subscripts"
-                                   : (bad & 4) ? "counts must be positive (and below 2^31)"
-                                               : "(largest count + 1) * M exceeds 2^32 table rows");
-  }
-  unsigned xmv = 0;
-  if ((rc = create_state(h, &xmv))) { cleanup(); return rc; }
-  h->sparse = 1;
-  h->nnz = (unsigned long long)nx;
-  // reports per layer: where each layer starts in the sorted keys
-  std::vector<unsigned long long> nl(L, 0);
-  {
-    unsigned long long* starts = nullptr;
-    CKC(hipMalloc(&starts, (size_t)(L + 1) * 8));
-    hipLaunchKernelGGL(k_coo_layer_starts, dim3(1), dim3(64), 0, h->stream, kx, nx, (unsigned long long)T, L, mb, starts);
-    std::vector<unsigned long long> st(L + 1);
-    hipError_t e1 = hipMemcpyAsync(st.data(), starts, (size_t)(L + 1) * 8, hipMemcpyDeviceToHost, h->stream);
-    if (e1 == hipSuccess) e1 = hipStreamSynchronize(h->stream);
-    (void)hipFree(starts);
-    CKC(e1);
-    for (int l = 0; l < L; ++l) nl[l] = st[l + 1] - st[l];
-  }
-  // packed entries (13-bit reporters, 11-bit counts, 2^20 table rows) where they hold the tensor, two words per entry otherwise;
-  // the general kernels take over beyond KMAX categories or with wide entries (sweep_gen.h)
-  g.wide = (g.Mp <= 8192 && xmv <= SL_XMAX && (size_t)(xmv + 1) * g.Mp <= SL_YM_ROWS) ? 0 : 1;
-  g.gen = (K > KMAX || g.wide) ? 1 : 0;
-  if ((unsigned long long)xmv * (unsigned long long)M > 0xffffffffull) {
-    cleanup();
-    return fail(nullptr, VMR_EINVAL, "largest count * M exceeds 2^32 (the per-tie mirror sums are 32-bit)");
-  }
-  if (!g.wide) {
-    hipLaunchKernelGGL(k_coo_pack, dim3(gx), dim3(256), 0, h->stream, etmp, etmp2, (long long)nx);
-    CKC(hipGetLastError());
-  }
-  rc = sl_place_entries(h, cx, nl, etmp, g.wide ? etmp2 : nullptr, nullptr);
-  if (!rc) rc = sl_finish(h);
-  if (rc) { cleanup(); return rc; }
-  // the mask: all ones needs nothing; partial rows become mask lists when they are short, bit-packed words otherwise.  The LDS
-  // A[Mp][K] of k_mask_lists and of the K <= 8 sweep bounds the lists of narrow handles; a wide one (Mp > 8192: general kernels
-  // only, whose pass walks the lists from global memory) takes them whatever Mp K.
-  if (nr >= 0 && h->n_partial > 0) {
-    const double list_bytes = 2.0 * (double)nr + 4.0 * (double)rows, word_bytes = (double)h->n_partial * g.W * 8.0;
-    const bool lists = !h->opt.no_rlists && maxrow <= 64 && (list_bytes * 4.0 <= word_bytes || g.N <= 1024) &&
-                       (g.Mp > 8192 || (size_t)g.Mp * K * 8 <= 160 * 1024);
-    {
-      size_t fr = 0, tot = 0;
-      CKC(hipMemGetInfo(&fr, &tot));
-      const double need = lists ? list_bytes + 4.0 * (double)n1 : (double)rows * g.W * 8.0;
-      if (need > (double)fr) {
-        char msg[320];
-        snprintf(msg, sizeof msg, "the mask's partial rows would take %.1f GB as %s (%llu partial rows, longest %u reporters, M = %d): more than the "
-                 "device memory left (%.1f GB)", need / 1e9, lists ? "mask lists" : "bit-packed words", (unsigned long long)h->n_partial, maxrow, M, fr / 1e9);
-        cleanup();
-        return fail(nullptr, VMR_EINVAL, msg);
-      }
-    }
-    if (lists) {
-      unsigned* bs = nullptr;
-      CKC(hipMalloc(&h->rq, n1 * 4));
-      CKC(hipMalloc(&bs, ((T + 1) + 2047) / 2048 * 4));
-      hipLaunchKernelGGL(k_coo_listed, dim3((unsigned)std::min<size_t>(4096, (n1 + 255) / 256)), dim3(256), 0, h->stream, cr, h->rcls, T, L, h->rq);
-      std::vector<unsigned long long> rb_(L);
-      h->n_rm = 0;
-      for (int l = 0; l < L; ++l) {
-        if ((rc = scan_u32(h, h->rq + (size_t)l * (T + 1), bs, T + 1))) { (void)hipFree(bs); cleanup(); return rc; }
-        unsigned tot = 0;
-        CKC(hipStreamSynchronize(h->stream));
-        CKC(hipMemcpy(&tot, h->rq + (size_t)l * (T + 1) + T, 4, hipMemcpyDeviceToHost));
-        rb_[l] = h->n_rm; h->n_rm += tot;
-      }
-      CKC(hipFree(bs));
-      CKC(hipMalloc(&h->rbase, (size_t)L * 8));
-      CKC(hipMemcpy(h->rbase, rb_.data(), (size_t)L * 8, hipMemcpyHostToDevice));
-      CKC(hipMalloc(&h->Rm, ((size_t)h->n_rm + 64) * 2));
-      hipLaunchKernelGGL(k_coo_rm, dim3(gr), dim3(256), 0, h->stream, kr, nr, T, mb, h->rcls, h->rq, h->rbase, h->Rm);
-      CKC(hipGetLastError());
-    } else {
-      CKC(hipMalloc(&h->Rb, rows * g.W * 8));
-      CKC(hipMemsetAsync(h->Rb, 0, rows * g.W * 8, h->stream));
-      hipLaunchKernelGGL(k_coo_rbits, dim3(gr), dim3(256), 0, h->stream, kr, nr, g.W, mb, reinterpret_cast<unsigned long long*>(h->Rb));
-      CKC(hipGetLastError());
-    }
-  }
-  CKC(hipStreamSynchronize(h->stream));
-#undef CKC
-  cleanup();
-  return create_tail(h, prop);
-}
-
-extern "C" int vmr_create_coo(vmr_handle* out, int device, int L, int N, int M, int K, int mutuality, int64_t nx, const int32_t* xl,
-                              const int32_t* xi, const int32_t* xj, const int32_t* xm, const int32_t* xv, int64_t nr, const int32_t* rl,
-                              const int32_t* ri, const int32_t* rj, const int32_t* rm, int data_on_device, double eps) {
-  if (!out) return fail(nullptr, VMR_EINVAL, "out is NULL");
-  *out = nullptr;
-  if (nx < 0 || (nx > 0 && (!xl || !xi || !xj || !xm || !xv))) return fail(nullptr, VMR_EINVAL, "X coordinate arrays missing");
-  if (nr > 0 && (!rl || !ri || !rj || !rm)) return fail(nullptr, VMR_EINVAL, "R coordinate arrays missing");
-  // limits of the coordinate route, before anything is allocated
-  if (L < 1 || N < 1 || M < 1) return fail(nullptr, VMR_EINVAL, "L, N, M must be positive");
-  if (M > 65535) return fail(nullptr, VMR_EINVAL, "M exceeds 65535 (M_COO_MAX): the mask lists hold 16-bit reporter indices");
-  int mb = 13;   // reporter bits of a sort key (COO_KEY): 13 up to Mp = 8192, as before wider reporter dimensions were taken
-  while ((1 << mb) < (M + 15) / 16 * 16) ++mb;
-  if ((((unsigned __int128)L * (unsigned)N * (unsigned)N) << mb) >> 64)
-    return fail(nullptr, VMR_EINVAL, "L * N^2 * 2^ceil(log2 M) must stay below 2^64 (the 64-bit sort keys of the coordinates)");
-  vmr_ctx* h = nullptr;
-  hipDeviceProp_t prop;
-  int rc = create_ctx(&h, &prop, device, L, N, M, K, mutuality, eps, true);
-  if (!rc) h->coo_mb = mb;
-  if (!rc) rc = create_coo(h, prop, nx, xl, xi, xj, xm, xv, nr, rl, ri, rj, rm, data_on_device);
-  if (rc) { if (h) vmr_destroy(h); return rc; }
-  *out = h;
-  return VMR_OK;
-}
-
-extern "C" {
-
-void vmr_destroy(vmr_handle h) {
-  if (!h) return;
-  (void)hipSetDevice(h->device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (auto& e : h->evs) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-  for (auto& e : h->graphs) (void)hipGraphExecDestroy(e.ex);
-  void* ptrs[] = {h->drw, h->x0p, h->h0s, h->far_pos, h->far_ent, h->far_base, h->EX, h->gen_s1, h->rm2, h->det_buf, h->fr_slots, h->nu_acc, h->fin_g, h->perm, h->sy, h->cls_p, h->Qt_p, h->nat, h->rho_snap, h->par_snap, h->rq, h->Rm, h->rbase, h->E, h->rs, h->Cg, h->Qt, h->ebase, h->rcls, h->X, h->Rb, h->cov, h->sumx, h->rho, h->logpr, h->lpd, h->lpb, h->par, h->slotA, h->slotR, h->elbo_dev, h->lutg, h->Hg, h->xmax, h->slotF, h->npartial};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
-  if (h->stream2) { (void)hipStreamSynchronize(h->stream2); (void)hipStreamDestroy(h->stream2); }
-  if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-  if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
-}
 
 int vmr_data_stats(vmr_handle h, double* sum_x, uint8_t* coverage) {
   if (!h) return VMR_EINVAL;

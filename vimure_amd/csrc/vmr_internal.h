@@ -77,6 +77,8 @@ __device__ __forceinline__ unsigned long long det_fx(double v, int sh) { return 
 __device__ __forceinline__ double det_back(unsigned long long u, int sh) { return ldexp((double)(long long)u, -sh); }
 
 #define NSLOT 8   // accumulation slots per layer for cross-workgroup sums (global f64 atomics)
+#define FG_G 16   // workgroups per layer of k_fin_gamma: each owns a range of reporters
+#define FR_G 16   // workgroups per layer of k_fin_rho
 
 // The VMR_* environment switches (INTEGRATION.md §3 has the table), read by read_opts -- the only place that reads the
 // environment -- once per handle, in create_ctx: a handle keeps the settings it was created under.  bools: set at all; ints: atoi,
@@ -486,11 +488,32 @@ static int grid_per_layer(vmr_ctx* h, Kern k, size_t smem, int* gl, long long ca
   return VMR_OK;
 }
 
+// a statement instantiated for the handle's K (KK inside it), K = 2..KMAX: the launches of vimure_hip.hip and sweep_tiles.hip
+#ifdef VMR_DEV   // development build: K = 2 only (fast compile, ISA inspection)
+#define DISPATCH_K(K_, ...)                         \
+  switch (K_) {                                     \
+    case 2: { constexpr int KK = 2; __VA_ARGS__; } break; \
+    default: break;                                 \
+  }
+#else
+#define DISPATCH_K(K_, ...)                         \
+  switch (K_) {                                     \
+    case 2: { constexpr int KK = 2; __VA_ARGS__; } break; \
+    case 3: { constexpr int KK = 3; __VA_ARGS__; } break; \
+    case 4: { constexpr int KK = 4; __VA_ARGS__; } break; \
+    case 5: { constexpr int KK = 5; __VA_ARGS__; } break; \
+    case 6: { constexpr int KK = 6; __VA_ARGS__; } break; \
+    case 7: { constexpr int KK = 7; __VA_ARGS__; } break; \
+    case 8: { constexpr int KK = 8; __VA_ARGS__; } break; \
+    default: break;                                 \
+  }
+#endif
+
 // the initial rho prior from MT19937 block states, queued on the handle's stream; draw_prior.hip
 int draw_pr_rho_launch(vmr_ctx* h, int nblk, const int64_t* cuts, const uint32_t* keys, const int32_t* pos, double bias0,
                        int undirected, double* out);
 
-// in-place exclusive scan of n u32 items on the handle's stream (bsum: scratch of ceil(n / 2048) items); vimure_hip.hip
+// in-place exclusive scan of n u32 items on the handle's stream (bsum: scratch of ceil(n / 2048) items); create.hip
 int scan_u32(vmr_ctx* h, unsigned* a, unsigned* bsum, size_t n);
 
 // re-writes rho where the last sweep left it unwritten, before anything reads it (vmr_readout and its kin); vimure_hip.hip
