@@ -536,6 +536,39 @@ int vmr_sample_cores(vmr_handle h, uint64_t seed, int n_samples, int n_trials, i
  * 0..3, k_min out of range, Y or values NULL, a single network whose temporaries do not fit.  Synchronises. */
 int vmr_network_cores(vmr_handle h, const uint8_t* Y, int n, int mode, int k_min, uint16_t* values, uint32_t* summary);
 
+/* The Holland-Leinhardt triad census of n_samples posterior samples of Y, computed where rho lives -- what a user otherwise gets
+ * from `networkx.triadic_census` (`sna::triad.census`, `igraph_triad_census`) on every `sample_inferred_model` draw.  Sample s is
+ * exactly what vmr_sample(h, seed + s, n_trials, ..) writes (seed + s mod 2^64).  Per sample and layer: A_ij = (Y_ij > 0) with the
+ * DIAGONAL CLEARED, and every unordered triple of distinct nodes is counted in the one of the 16 isomorphism classes of its
+ * induced subgraph.  A class is named by its mutual, asymmetric and null dyads and a letter; in the order of the output, which is
+ * networkx's:
+ *    0 003                      4 021U  a -> b <- c           8 030T  a -> b <- c, a -> c      12 120U  a -> b <- c, a <-> c
+ *    1 012   a -> b             5 021C  a -> b -> c           9 030C  a -> b -> c -> a         13 120C  a -> b -> c, a <-> c
+ *    2 102   a <-> b            6 111D  a <-> b <- c         10 201   a <-> b <-> c            14 210   a -> b <-> c, a <-> c
+ *    3 021D  a <- b -> c        7 111U  a <-> b -> c         11 120D  a <- b -> c, a <-> c     15 300   all three mutual
+ * counts: host uint64 [n_samples][L][VMR_CENSUS_NCLASS]; the 16 numbers of a sample and layer sum to C(N, 3).  N < 3 is legal and
+ * gives zeros.  Exact integers: for every connected pair i < j the thirds k are counted by the popcounts of the 15 combinations
+ * of (the state of k seen from i, the state seen from j) other than (none, none), the thirds tied to neither are N - 2 - their
+ * sum, a triad found from each of its c connected dyads is divided by c, and 003 is what is left of C(N, 3).  The work is
+ * proportional to ties x ceil(N / 64); any N the handle has.  Integer adds commute: every output is identical from run to run and
+ * for any chunking.  The samples are packed into the bit rows of vmr_sample_triads.  Reads the CURRENT rho (after vmr_restore:
+ * the snapshot's) once per chunk of samples; any K, any n_trials >= 1, both data formats.  A chunk (L N^2 + 16 L N ceil(N/64) +
+ * 128 L bytes per sample; half of the free device memory at most, 256 samples at most, VMR_NETSTATS_CHUNK at most) is freed before
+ * return; a single sample that does not fit is refused with VMR_EINVAL.
+ * VMR_EINVAL, with a message that names the call and the argument, whatever the state of the handle: n_samples < 1, n_trials < 1,
+ * counts NULL.  Before vmr_set_state: VMR_ESTATE.  Synchronises. */
+#define VMR_CENSUS_NCLASS 16   /* 003 012 102 021D 021U 021C 111D 111U 030T 030C 201 120D 120U 120C 210 300 (networkx's order and naming) */
+int vmr_sample_triad_census(vmr_handle h, uint64_t seed, int n_samples, int n_trials, uint64_t* counts /* [n_samples][L][16] */);
+
+/* The same census, by the same packing and the same kernel, of n networks the caller supplies -- the inferred network, a ground
+ * truth, a designed graph.  Y: HOST uint8 [n][L][N][N]; an entry > 0 is a tie, the diagonal is ignored.  counts: host uint64
+ * [n][L][VMR_CENSUS_NCLASS].  The handle gives N, L, the device and the stream and nothing else: the call works before
+ * vmr_set_state and does not touch rho.  Network q of a call equals what vmr_sample_triad_census returns for a sample with the
+ * same ties.  The networks are uploaded in chunks (L N^2 + 16 L N ceil(N/64) + 128 L bytes per network).  VMR_EINVAL, with a
+ * message that names the call and the argument: n < 1, Y or counts NULL, a single network whose temporaries do not fit.
+ * Synchronises. */
+int vmr_network_triad_census(vmr_handle h, const uint8_t* Y /* host [n][L][N][N] */, int n, uint64_t* counts /* [n][L][16] */);
+
 /* Posterior predictive checks: n_rep replicated datasets drawn from the fitted model over the support of the handle's own R and
  * reduced where they are drawn -- no replicate is ever written -- and the same reduction of the observed data.
  * Replicate r: Y_r is exactly what vmr_sample(h, seed_y + r, n_trials, ..) writes (mod 2^64; the CURRENT rho, after vmr_restore

@@ -82,6 +82,11 @@ class CoresArgumentError(EngineError, ValueError):
     than the peel's working set holds (`_lib.CORE_NMAX`), temporaries that do not fit in the free device memory."""
 
 
+class CensusArgumentError(EngineError, ValueError):
+    """An argument `sample_triad_census` / `network_triad_census` refuse (VMR_EINVAL): n_samples or n_trials below 1, networks of
+    another shape than the handle's, temporaries that do not fit in the free device memory."""
+
+
 SCORE_OUTPUTS = ("hist", "conf", "sums", "auc", "auc_pairs")
 INF_SELECT = {"none": 0, "lost": _lib.INF_LOST, "gained": _lib.INF_GAINED, "both": _lib.INF_LOST | _lib.INF_GAINED}
 # columns of the table of `CaviEngine.reporter_influence`, in the order of vmr_reporter_influence's row pointers
@@ -665,6 +670,29 @@ class CaviEngine:
             return out[0] if one else out
         smd = {name: (sm[0, :, q] if one else sm[..., q]).astype(np.int64) for q, name in enumerate(_CORE_STATS)}
         return (out[0] if one else out), smd
+
+    def sample_triad_census(self, seed, n_samples, n_trials=1):
+        """The triad census of n_samples posterior samples, computed on the device (vmr_sample_triad_census): sample s is
+        `self.sample(seed + s, n_trials)`, A = (Y > 0) with the diagonal cleared, and every unordered triple of nodes is counted
+        in its Holland-Leinhardt class.  Returns int64 [S, L, 16] in the order of `_lib.CENSUS_NAMES` -- 003 012 102 021D 021U
+        021C 111D 111U 030T 030C 201 120D 120U 120C 210 300, `networkx.triadic_census`'s order and naming; the 16 numbers of a
+        sample and layer sum to C(N, 3).  Exact integers, the same from run to run and for any chunking.  A refused argument
+        raises `CensusArgumentError`."""
+        S = int(n_samples)
+        counts = np.zeros((max(S, 0), self.L, _lib.CENSUS_NCLASS), np.uint64)
+        self._check(self.lib.vmr_sample_triad_census(self._h, int(seed) & (2 ** 64 - 1), S, int(n_trials), counts.ctypes.data), CensusArgumentError)
+        return counts.astype(np.int64)
+
+    def network_triad_census(self, Y):
+        """The census of `sample_triad_census` of networks the caller supplies (vmr_network_triad_census), by the same kernel:
+        Y [L, N, N] -> int64 [L, 16], or [n, L, N, N] -> [n, L, 16]; an entry > 0 is a tie, the diagonal is ignored.  The engine
+        gives the shape and the device only: no state is needed and rho is not touched.  A refused argument raises
+        `CensusArgumentError`."""
+        ties, one = self._network_ties(Y, CensusArgumentError)
+        out = np.zeros((ties.shape[0], self.L, _lib.CENSUS_NCLASS), np.uint64)
+        self._check(self.lib.vmr_network_triad_census(self._h, ties.ctypes.data, ties.shape[0], out.ctypes.data), CensusArgumentError)
+        out = out.astype(np.int64)
+        return out[0] if one else out
 
     def _mixing_args(self, groups, C):
         """(codes int32 [N] or None, C) for the mixing calls: C None is the largest code + 1."""

@@ -870,6 +870,27 @@ class VimureModel(TransformerMixin, BaseEstimator):
             counts = eng.sample_cores(seed, n_samples, mode=mode, k_min=k, top_k=top_k, n_trials=n_trials, values=bool(values))
         return CoreStats(self.N, counts, mode=mode, k_min=k, top_k=top_k, inferred=inferred, seed=seed, n_trials=n_trials)
 
+    def posterior_triad_census(self, n_samples=100, seed=None, n_trials=1, X=None, R=None):
+        """Which local structures does the network hold, and how sure is the posterior of them?  The Holland-Leinhardt triad
+        census (`networkx.triadic_census`: the unordered triples of nodes in each of the 16 classes 003 012 102 021D 021U 021C
+        111D 111U 030T 030C 201 120D 120U 120C 210 300) over the posterior of the network, computed on the GPU
+        (vmr_sample_triad_census): n_samples draws of Y from q(Y) -- sample s is `sample_inferred_model(N=n_trials, seed=seed + s,
+        device=True)[0]` -- counted where rho lives on A = (Y > 0) without self-loops; only the 16 integers per sample and layer
+        cross PCIe.  It says what the six aggregates of `posterior_network_stats(triads=True)` cannot: whether closed triads are
+        transitive (030T, 120D, 120U) or cyclic (030C), whether brokered two-paths stay open (021C, 111D, 111U, 201), whether
+        hierarchies (021D, 021U, 120D, 120U) are over-represented given the dyads.
+        Returns a `census.TriadCensus`: counts, mean, sd, `quantiles()`, the census of the point estimate `get_inferred_model()`
+        (`inferred`, by the same kernel), `dyads()`, `expected_under_man()` (the expectation given each sample's own mutual,
+        asymmetric and null dyads), `excess()`, `transitive_share()`, `frame()` and `summary()`.  seed None: the fit's.  Engine as
+        in `calculate_mean_poisson`."""
+        from .census import TriadCensus
+        if seed is None:
+            seed = self.seed
+        with self._read_engine(X, R) as eng:
+            inferred = eng.network_triad_census(self.get_inferred_model())
+            counts = eng.sample_triad_census(seed, n_samples, n_trials=n_trials)
+        return TriadCensus(self.N, counts, inferred=inferred, seed=seed, n_trials=n_trials)
+
     def posterior_predictive_check(self, n_rep=100, seed=None, params="draw", n_trials=1, by_reporter=False, X=None, R=None):
         """Does data drawn from the fitted model look like the data it was fitted to?  n_rep replicated datasets are drawn on the
         GPU over the support of R and reduced there (vmr_ppc_replicates; no replicate is written) to the integers of
