@@ -569,6 +569,62 @@ int vmr_sample_triad_census(vmr_handle h, uint64_t seed, int n_samples, int n_tr
  * Synchronises. */
 int vmr_network_triad_census(vmr_handle h, const uint8_t* Y /* host [n][L][N][N] */, int n, uint64_t* counts /* [n][L][16] */);
 
+/* Shared partners of the ties of n_samples posterior samples of Y, computed where rho lives: the posterior TIE BY TIE -- the
+ * support of Jackson, Rodriguez-Barraquer and Tan (the share of ties whose two ends have a partner in common), the embeddedness
+ * of every tie, the local bridges (ties with no common partner), Krackhardt's Simmelian ties and the edgewise-shared-partner
+ * distribution behind GWESP.  Sample s is exactly what vmr_sample(h, seed + s, n_trials, ..) writes (seed + s mod 2^64).  Per
+ * sample and layer A_ij = (Y_ij > 0) with the DIAGONAL CLEARED, and `mode` names the ties that are counted and their partners:
+ *   VMR_SP_UNION    unordered pairs i < j tied either way    k tied (either way) to i and to j
+ *   VMR_SP_MUTUAL   unordered pairs tied both ways           k tied both ways to both (a Simmelian tie has one)
+ *   VMR_SP_PATH     ordered ties i -> j                      k with i -> k -> j: the tie closes a two-path (transitive embeddedness)
+ * A partner is neither i nor j.  Outputs, host memory:
+ *   hist    uint64 [n_samples][L][n_bins]   the ties with exactly b partners; the LAST bin holds those with n_bins - 1 or more
+ *   totals  uint64 [n_samples][L][VMR_SP_NTOTAL]   ties, supported ties (>= 1 partner), the partners summed over the ties, the
+ *           largest partner count of a tie
+ *   node_ties, node_supported   int32 [n_samples][L][N], each optional (NULL) and independent of the other: the counted ties
+ *           node v is an end of, and those of them with >= 1 partner (in path mode i -> j and j -> i are two ties of both nodes)
+ *   pairs   int32 [n_pairs][3] = (layer, i, j), i != j, or NULL with n_pairs = 0: ties to follow over the samples.  In union and
+ *           mutual mode (i, j) and (j, i) name the same tie; a pair may be listed more than once.  Per listed pair:
+ *           pair_present uint32 [n_pairs] the samples in which it is a counted tie, pair_supported uint32 [n_pairs] those in
+ *           which it also has >= 1 partner, pair_partners uint64 [n_pairs] its partners summed over the samples in which it is a
+ *           tie.  Required when n_pairs > 0, untouched otherwise.
+ * The partners of (i, j) are popcounts of two bit rows, popc(P_i & Q_j) over ceil(N / 64) words: the work is proportional to
+ * ties x ceil(N / 64), integers only, any N the handle has; N < 3 is legal and no tie has a partner.  Every output is an exact
+ * integer, identical from run to run and for any chunking (integer adds and an integer maximum; 64-bit beyond a workgroup).  The
+ * samples are packed into the bit rows of vmr_sample_triads.  Reads the CURRENT rho (after vmr_restore: the snapshot's) once per
+ * chunk of samples; any K, any n_trials >= 1, both data formats.  A chunk (L N^2 + 16 L N ceil(N/64) + 8 L (n_bins + 4) bytes per
+ * sample, + 4 L N per node array; half of the free device memory at most, 256 samples at most, VMR_NETSTATS_CHUNK at most) and
+ * the pairs with their accumulators (28 n_pairs bytes per call) are freed before return; a single sample that does not fit is
+ * refused with VMR_EINVAL.
+ * VMR_EINVAL, with a message that names the call and the argument, whatever the state of the handle: n_samples < 1, n_trials < 1,
+ * mode outside 0..2, n_bins outside [2, VMR_SP_MAX_BINS], hist or totals NULL, n_pairs < 0, pairs or a pair output NULL with
+ * n_pairs > 0, a pair whose layer or node is out of range or with i == j (checked on the host before any launch).  Before
+ * vmr_set_state: VMR_ESTATE.  Synchronises. */
+#define VMR_SP_UNION 0
+#define VMR_SP_MUTUAL 1
+#define VMR_SP_PATH 2
+#define VMR_SP_MAX_BINS 1024
+#define VMR_SP_NTOTAL 4    /* ties, supported ties (>= 1 partner), sum of partners over ties, largest partner count */
+int vmr_sample_shared_partners(vmr_handle h, uint64_t seed, int n_samples, int n_trials, int mode, int n_bins,
+                               uint64_t* hist,            /* [n_samples][L][n_bins] */
+                               uint64_t* totals,          /* [n_samples][L][4] */
+                               int32_t* node_ties,        /* [n_samples][L][N] or NULL */
+                               int32_t* node_supported,   /* [n_samples][L][N] or NULL */
+                               const int32_t* pairs, int n_pairs,   /* [n_pairs][3] = (layer, i, j), or NULL / 0 */
+                               uint32_t* pair_present, uint32_t* pair_supported, uint64_t* pair_partners /* [n_pairs] each */);
+
+/* The same counts, by the same packing and the same kernels, of n networks the caller supplies -- the inferred network, a ground
+ * truth, a designed graph.  Y: HOST uint8 [n][L][N][N]; an entry > 0 is a tie, the diagonal is ignored.  hist [n][L][n_bins],
+ * totals [n][L][4] and the node arrays [n][L][N] as above.  pair_partners: host int32 [n][n_pairs], the partners of every listed
+ * pair in every network, -1 where the pair is not a counted tie; required when n_pairs > 0.  The handle gives N, L, the device
+ * and the stream and nothing else: the call works before vmr_set_state and does not touch rho.  Network q of a call equals what
+ * vmr_sample_shared_partners returns for a sample with the same ties.  The networks are uploaded in chunks (the bytes above + 4
+ * n_pairs per network).  VMR_EINVAL, with a message that names the call and the argument: n < 1, Y NULL, and the cases above but
+ * n_samples and n_trials; a single network whose temporaries do not fit.  Synchronises. */
+int vmr_network_shared_partners(vmr_handle h, const uint8_t* Y /* host [n][L][N][N] */, int n, int mode, int n_bins, uint64_t* hist,
+                                uint64_t* totals, int32_t* node_ties, int32_t* node_supported, const int32_t* pairs, int n_pairs,
+                                int32_t* pair_partners /* [n][n_pairs]: partners, -1 where not a tie */);
+
 /* Posterior predictive checks: n_rep replicated datasets drawn from the fitted model over the support of the handle's own R and
  * reduced where they are drawn -- no replicate is ever written -- and the same reduction of the observed data.
  * Replicate r: Y_r is exactly what vmr_sample(h, seed_y + r, n_trials, ..) writes (mod 2^64; the CURRENT rho, after vmr_restore

@@ -28,6 +28,9 @@ CORE_NMAX = 2048
 CORE_MODES = ("union", "total", "in", "out")   # VMR_CORE_UNION, VMR_CORE_TOTAL, VMR_CORE_IN, VMR_CORE_OUT
 CENSUS_NCLASS = 16
 CENSUS_NAMES = ("003", "012", "102", "021D", "021U", "021C", "111D", "111U", "030T", "030C", "201", "120D", "120U", "120C", "210", "300")
+SP_MODES = ("union", "mutual", "path")     # VMR_SP_UNION, VMR_SP_MUTUAL, VMR_SP_PATH
+SP_MAX_BINS, SP_NTOTAL = 1024, 4
+SP_TOTALS = ("ties", "supported", "partners", "max_partners")
 EDGE_REPORTED, EDGE_INFERRED = 1, 2
 SCORE_RHO1, SCORE_PROB = 0, 1
 SCORE_NCONF, SCORE_NSUM, SCORE_MAX_THR = 5, 4, 4096
@@ -93,6 +96,9 @@ SIGNATURES = {
     "vmr_network_cores": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vmr_sample_triad_census": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p]),
     "vmr_network_triad_census": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "vmr_sample_shared_partners": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int] +
+                                   [C.c_void_p] * 3),
+    "vmr_network_shared_partners": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p]),
     "vmr_ppc_replicates": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
     "vmr_ppc_observed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -87,6 +87,12 @@ class CensusArgumentError(EngineError, ValueError):
     another shape than the handle's, temporaries that do not fit in the free device memory."""
 
 
+class PartnersArgumentError(EngineError, ValueError):
+    """An argument `sample_shared_partners` / `network_shared_partners` refuse (VMR_EINVAL): n_samples or n_trials below 1, an
+    unknown mode, n_bins outside [2, `_lib.SP_MAX_BINS`], a pair whose layer or node is out of range or that names one node twice,
+    networks of another shape than the handle's, temporaries that do not fit in the free device memory."""
+
+
 SCORE_OUTPUTS = ("hist", "conf", "sums", "auc", "auc_pairs")
 INF_SELECT = {"none": 0, "lost": _lib.INF_LOST, "gained": _lib.INF_GAINED, "both": _lib.INF_LOST | _lib.INF_GAINED}
 # columns of the table of `CaviEngine.reporter_influence`, in the order of vmr_reporter_influence's row pointers
@@ -693,6 +699,73 @@ class CaviEngine:
         self._check(self.lib.vmr_network_triad_census(self._h, ties.ctypes.data, ties.shape[0], out.ctypes.data), CensusArgumentError)
         out = out.astype(np.int64)
         return out[0] if one else out
+
+    def _partners_args(self, mode, n_bins, n, nodes, pairs):
+        """(mode code, n_bins, hist, totals, the two node arrays or None, pairs int32 [P, 3] or None) for the shared-partner calls
+        on n samples or networks."""
+        if mode not in _lib.SP_MODES:
+            raise PartnersArgumentError(f"mode must be one of {_lib.SP_MODES}, got {mode!r}")
+        B = int(n_bins)
+        hist = np.zeros((max(n, 0), self.L, max(B, 0)), np.uint64)
+        totals = np.zeros((max(n, 0), self.L, _lib.SP_NTOTAL), np.uint64)
+        nt = np.zeros((max(n, 0), self.L, self.N), np.int32) if nodes else None
+        ns = np.zeros((max(n, 0), self.L, self.N), np.int32) if nodes else None
+        pa = None
+        if pairs is not None:
+            pa = np.ascontiguousarray(pairs, dtype=np.int32)
+            if pa.ndim != 2 or pa.shape[1] != 3:
+                raise PartnersArgumentError(f"pairs has shape {np.shape(pairs)}, expected (n_pairs, 3): rows of (layer, i, j)")
+        return _lib.SP_MODES.index(mode), B, hist, totals, nt, ns, pa
+
+    @staticmethod
+    def _partners_result(hist, totals, nt, ns, one=False):
+        out = {"hist": hist.astype(np.int64), "totals": totals.astype(np.int64)}
+        if nt is not None:
+            out["node_ties"], out["node_supported"] = nt, ns
+        return {k: v[0] for k, v in out.items()} if one else out
+
+    def sample_shared_partners(self, seed, n_samples, n_trials=1, mode="union", n_bins=64, nodes=False, pairs=None):
+        """Shared partners of the ties of n_samples posterior samples, computed on the device (vmr_sample_shared_partners): sample
+        s is `self.sample(seed + s, n_trials)`, A = (Y > 0) with the diagonal cleared.  mode "union": the unordered pairs tied
+        either way, a partner is tied (either way) to both ends; "mutual": the pairs tied both ways, a partner is tied both ways to
+        both (Simmelian ties); "path": the ordered ties i -> j, a partner k has i -> k -> j.  Returns a dict: `hist` int64 [S, L,
+        n_bins] (ties with exactly b partners; the last bin holds b >= n_bins - 1), `totals` int64 [S, L, 4] in the order of
+        `_lib.SP_TOTALS` (ties, supported ties, partners summed over the ties, the largest count); with nodes=True `node_ties`
+        and `node_supported` int32 [S, L, N] (the counted ties a node is an end of; those with a partner); with pairs (rows of
+        (layer, i, j)) `pair_present`, `pair_supported`, `pair_partners` int64 [n_pairs]: the samples in which the pair is a
+        counted tie, those in which it also has a partner, and its partners summed over the former.  Exact integers, the same from
+        run to run and for any chunking.  A refused argument raises `PartnersArgumentError`."""
+        S = int(n_samples)
+        m, B, hist, totals, nt, ns, pa = self._partners_args(mode, n_bins, S, nodes, pairs)
+        P = 0 if pa is None else len(pa)
+        pr, ps, pp = np.zeros(P, np.uint32), np.zeros(P, np.uint32), np.zeros(P, np.uint64)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        self._check(self.lib.vmr_sample_shared_partners(self._h, int(seed) & (2 ** 64 - 1), S, int(n_trials), m, B, hist.ctypes.data,
+                                                        totals.ctypes.data, ptr(nt), ptr(ns), ptr(pa), P, pr.ctypes.data, ps.ctypes.data,
+                                                        pp.ctypes.data), PartnersArgumentError)
+        out = self._partners_result(hist, totals, nt, ns)
+        if pa is not None:
+            out.update(pair_present=pr.astype(np.int64), pair_supported=ps.astype(np.int64), pair_partners=pp.astype(np.int64))
+        return out
+
+    def network_shared_partners(self, Y, mode="union", n_bins=64, nodes=False, pairs=None):
+        """The counts of `sample_shared_partners` of networks the caller supplies (vmr_network_shared_partners), by the same
+        kernels: Y [L, N, N] or [n, L, N, N] (an entry > 0 is a tie, the diagonal is ignored) -> the same dict without or with the
+        leading axis; with pairs `pair_partners` int32 [n, n_pairs]: the partners of every listed pair, -1 where it is not a
+        counted tie.  The engine gives the shape and the device only: no state is needed and rho is not touched.  A refused
+        argument raises `PartnersArgumentError`."""
+        ties, one = self._network_ties(Y, PartnersArgumentError)
+        n = ties.shape[0]
+        m, B, hist, totals, nt, ns, pa = self._partners_args(mode, n_bins, n, nodes, pairs)
+        P = 0 if pa is None else len(pa)
+        pp = np.zeros((n, P), np.int32)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        self._check(self.lib.vmr_network_shared_partners(self._h, ties.ctypes.data, n, m, B, hist.ctypes.data, totals.ctypes.data, ptr(nt), ptr(ns),
+                                                         ptr(pa), P, pp.ctypes.data), PartnersArgumentError)
+        out = self._partners_result(hist, totals, nt, ns, one)
+        if pa is not None:
+            out["pair_partners"] = pp[0] if one else pp
+        return out
 
     def _mixing_args(self, groups, C):
         """(codes int32 [N] or None, C) for the mixing calls: C None is the largest code + 1."""

@@ -891,6 +891,42 @@ class VimureModel(TransformerMixin, BaseEstimator):
             counts = eng.sample_triad_census(seed, n_samples, n_trials=n_trials)
         return TriadCensus(self.N, counts, inferred=inferred, seed=seed, n_trials=n_trials)
 
+    def posterior_shared_partners(self, mode="union", n_samples=100, seed=None, n_trials=1, n_bins=64, nodes=False, ties="inferred", X=None,
+                                  R=None):
+        """Which ties does the posterior say are embedded, and which are bridges?  The shared partners of every tie over the
+        posterior of the network, computed on the GPU (vmr_sample_shared_partners): n_samples draws of Y from q(Y) -- sample s is
+        `sample_inferred_model(N=n_trials, seed=seed + s, device=True)[0]` -- reduced where rho lives on A = (Y > 0) without
+        self-loops; rho does not cross PCIe.  mode "union": the unordered pairs tied either way, a partner is tied (either way) to
+        both ends -- the support of Jackson, Rodriguez-Barraquer and Tan is the share of ties with a partner, a local bridge a tie
+        with none; "mutual": the pairs tied both ways and partners tied both ways to both (Krackhardt's Simmelian ties); "path":
+        the ordered ties i -> j and the k with i -> k -> j, the edgewise shared partners behind ERGM's GWESP.  n_bins: the bins
+        of the histogram of ties by partner count, whose last bin pools the larger counts.  nodes=True: also per node its ties
+        and its supported ties.  ties: the ties to follow one by one -- "inferred": those of `get_inferred_model()` under the
+        mode's tie rule; an array of (layer, i, j) rows; None: none.
+        Returns a `partners.SharedPartners`: hist, totals, `support()`, `mean_partners()`, `local_bridges()`, mean, sd,
+        `quantiles()`, `gwesp(decay)`, `node_support()`, the same counts of the point estimate (`inferred`, by the same kernels),
+        `ties_frame()`, `bridges()`, `frame()` and `summary()`.  seed None: the fit's.  Engine as in `calculate_mean_poisson`."""
+        from .partners import SharedPartners
+        if seed is None:
+            seed = self.seed
+        point = self.get_inferred_model()
+        if isinstance(ties, str):
+            if ties != "inferred":
+                raise ValueError(f'ties must be "inferred", None or an array of (layer, i, j) rows, got {ties!r}')
+            A = np.asarray(point) > 0
+            A &= ~np.eye(self.N, dtype=bool)
+            At = A.transpose(0, 2, 1)
+            T = A if mode == "path" else np.triu(A & At if mode == "mutual" else A | At, 1)
+            pairs = np.argwhere(T).astype(np.int32)
+        else:
+            pairs = None if ties is None else np.asarray(ties, dtype=np.int32).reshape(-1, 3)
+        with self._read_engine(X, R) as eng:
+            inferred = eng.network_shared_partners(point, mode=mode, n_bins=n_bins, nodes=nodes, pairs=pairs)
+            res = eng.sample_shared_partners(seed, n_samples, n_trials=n_trials, mode=mode, n_bins=n_bins, nodes=nodes, pairs=pairs)
+        return SharedPartners(self.N, mode, res["hist"], res["totals"], node_ties=res.get("node_ties"), node_supported=res.get("node_supported"),
+                              pairs=pairs, pair_present=res.get("pair_present"), pair_supported=res.get("pair_supported"),
+                              pair_partners=res.get("pair_partners"), inferred=inferred, seed=seed, n_trials=n_trials)
+
     def posterior_predictive_check(self, n_rep=100, seed=None, params="draw", n_trials=1, by_reporter=False, X=None, R=None):
         """Does data drawn from the fitted model look like the data it was fitted to?  n_rep replicated datasets are drawn on the
         GPU over the support of R and reduced there (vmr_ppc_replicates; no replicate is written) to the integers of
