@@ -625,6 +625,68 @@ int vmr_network_shared_partners(vmr_handle h, const uint8_t* Y /* host [n][L][N]
                                 uint64_t* totals, int32_t* node_ties, int32_t* node_supported, const int32_t* pairs, int n_pairs,
                                 int32_t* pair_partners /* [n][n_pairs]: partners, -1 where not a tie */);
 
+/* Burt's structural holes of n_samples posterior samples of Y, computed where rho lives: the posterior NODE BY NODE as an ego
+ * network -- whose own contacts are disconnected from one another -- what a user otherwise gets from `networkx.effective_size`
+ * and `networkx.constraint` on every `sample_inferred_model` draw.  Sample s is exactly what vmr_sample(h, seed + s, n_trials, ..)
+ * writes (seed + s mod 2^64).  Per sample and layer A = (Y > 0) with the DIAGONAL CLEARED, U = A | A^T, Mu = A & A^T, and `mode`
+ * names the weights z:
+ *   VMR_SH_UNION     z_ij = U_ij: the symmetrised binary network -- networkx on `G.to_undirected()`
+ *   VMR_SH_WEIGHTED  z_ij = A_ij + A_ji = U_ij + Mu_ij in {0, 1, 2}: Burt's mutual weights on the directed network -- networkx on
+ *                    the DiGraph, which reports NaN for a node without out-ties whatever its in-ties; here only isolates are undefined
+ * For node i: the degree d_i = sum_j U_ij, the strength s_i = sum_j z_ij, p_ij = z_ij / s_i, and mx_j = max_x z_jx, which is 2
+ * exactly when j has a mutual tie in weighted mode (s_j > d_j) and 1 otherwise.  The measures:
+ *   redundancy numerator  R_i = sum_{j in U_i} f_j sum_q z_iq z_jq, f_j = 2 / mx_j in {1, 2}: an exact integer, <= 2 s_i (d_i - 1)
+ *   effective size        ES_i = d_i - R_i / (2 s_i), evaluated as (2 s_i d_i - R_i) / (2 s_i): the numerator is an exact integer,
+ *                         so ES is the correctly rounded value of the rational and a host reproduces it from (d, s, R) with ==.
+ *                         Union mode: Borgatti's n - 2 t / n; weighted mode: Burt's sum_j (1 - sum_q p_iq m_jq), m_jq = z_jq / mx_j
+ *   constraint            c_i = sum_{j in U_i} ((z_ij + sum_{q in U_i & U_j} z_iq z_qj / s_q) / s_i)^2, every operation rounded as
+ *                         written (no contraction); the sums in an order that depends on N only
+ *   efficiency            ES_i / d_i is left to the caller
+ * A node with d_i = 0 is UNDEFINED: both measures are stored as 0.0 and the caller masks them by the degree.  Ranks are taken
+ * among the defined nodes: by effective size rank_v = #{defined u : ES_u > ES_v}, by constraint rank_v = #{defined u : c_u < c_v}
+ * (0: the first broker; equal values share the smaller rank); an undefined node gets rank = #defined.  Outputs, host memory; index
+ * 0 of the leading [2] is the effective size, 1 the constraint:
+ *   node_sum, node_sumsq   sum_s value and sum_s value^2 (the square rounded before it is added), ascending s   double [2][L][N]
+ *   node_rank_sum          sum_s rank                                                                          uint64 [2][L][N]
+ *   node_top               #{s : rank < top_k}                                                                 uint32 [2][L][N]
+ *   node_defined           #{s : d > 0}: the samples in which the node is not isolated                         uint32 [L][N]
+ *   summary                (#defined, sum_v ES_v, sum_v c_v) over the defined nodes                             double [n_samples][L][3]
+ *   degree, strength       d and s                                                                             int32 [n_samples][L][N]
+ *   redundancy             R                                                                                   uint64 [n_samples][L][N]
+ *   effective_size, constraint   the two measures of every sample                                              double [n_samples][L][N]
+ * node_sum may not be NULL, every other output may be, each on its own.
+ * The samples are packed into the bit rows of vmr_sample_triads.  One wave per (node, layer, sample) lists the node's neighbours
+ * and walks their rows: the integers are popcounts, the FP64 sum of a pair walks the common neighbours in ascending order; no
+ * atomics, a node is owned by one wave.  The work is proportional to ties x ceil(N / 64) plus the common neighbours, the ranks are
+ * N^2 comparisons out of LDS; any N the handle has.  Every output is bit-identical from run to run and for any chunking.  Reads
+ * the CURRENT rho (after vmr_restore: the snapshot's) once per chunk of samples; any K, any n_trials >= 1, both data formats.  A
+ * chunk (L N^2 + 16 L N ceil(N/64) + 40 L N + 24 L bytes per sample, whichever outputs are asked for, beside 60 L N bytes of
+ * per-node accumulators per call; half of the free device memory at most, 256 samples at most, VMR_NETSTATS_CHUNK at most) is
+ * freed before return; a single sample that does not fit is refused with VMR_EINVAL.
+ * VMR_EINVAL, with a message that names the call and the argument, whatever the state of the handle: n_samples < 1, n_trials < 1,
+ * mode outside 0..1, top_k outside [1, N], node_sum NULL.  Before vmr_set_state: VMR_ESTATE.  Synchronises. */
+#define VMR_SH_UNION 0
+#define VMR_SH_WEIGHTED 1
+#define VMR_SH_NSUMMARY 3   /* defined nodes, sum of their effective sizes, sum of their constraints */
+int vmr_sample_structural_holes(vmr_handle h, uint64_t seed, int n_samples, int n_trials, int mode, int top_k,
+                                double* node_sum /* [2][L][N]: effective size, constraint; required */, double* node_sumsq,
+                                uint64_t* node_rank_sum, uint32_t* node_top /* [2][L][N] each, or NULL */,
+                                uint32_t* node_defined /* [L][N] */, double* summary /* [n_samples][L][3] */, int32_t* degree,
+                                int32_t* strength, uint64_t* redundancy, double* effective_size,
+                                double* constraint /* [n_samples][L][N] each, or NULL */);
+
+/* The same measures, by the same packing and the same kernels, of n networks the caller supplies -- the inferred network, a
+ * ground truth, a designed graph.  Y: HOST uint8 [n][L][N][N]; an entry > 0 is a tie, the diagonal is ignored.  effective_size,
+ * constraint: host double [n][L][N], required; degree, strength int32 [n][L][N], redundancy uint64 [n][L][N], summary double
+ * [n][L][3] as above, or NULL.  The handle gives N, L, the device and the stream and nothing else: the call works before
+ * vmr_set_state and does not touch rho.  Network q of a call equals, bit for bit, what vmr_sample_structural_holes returns for a
+ * sample with the same ties.  The networks are uploaded in chunks (L N^2 + 16 L N ceil(N/64) + 24 L N bytes per network, + 8 L N
+ * with redundancy, + 24 L with summary).  VMR_EINVAL, with a message that names the call and the argument: n < 1, mode outside
+ * 0..1, Y, effective_size or constraint NULL, a single network whose temporaries do not fit.  Synchronises. */
+int vmr_network_structural_holes(vmr_handle h, const uint8_t* Y /* host [n][L][N][N] */, int n, int mode, double* effective_size,
+                                 double* constraint /* [n][L][N], required */, int32_t* degree, int32_t* strength,
+                                 uint64_t* redundancy, double* summary /* or NULL */);
+
 /* Posterior predictive checks: n_rep replicated datasets drawn from the fitted model over the support of the handle's own R and
  * reduced where they are drawn -- no replicate is ever written -- and the same reduction of the observed data.
  * Replicate r: Y_r is exactly what vmr_sample(h, seed_y + r, n_trials, ..) writes (mod 2^64; the CURRENT rho, after vmr_restore

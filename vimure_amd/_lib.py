@@ -31,6 +31,8 @@ CENSUS_NAMES = ("003", "012", "102", "021D", "021U", "021C", "111D", "111U", "03
 SP_MODES = ("union", "mutual", "path")     # VMR_SP_UNION, VMR_SP_MUTUAL, VMR_SP_PATH
 SP_MAX_BINS, SP_NTOTAL = 1024, 4
 SP_TOTALS = ("ties", "supported", "partners", "max_partners")
+SH_MODES = ("union", "weighted")           # VMR_SH_UNION, VMR_SH_WEIGHTED
+SH_SUMMARY = ("n_defined", "effective_size_sum", "constraint_sum")   # the columns of the structural-holes calls' summary
 EDGE_REPORTED, EDGE_INFERRED = 1, 2
 SCORE_RHO1, SCORE_PROB = 0, 1
 SCORE_NCONF, SCORE_NSUM, SCORE_MAX_THR = 5, 4, 4096
@@ -99,6 +101,8 @@ SIGNATURES = {
     "vmr_sample_shared_partners": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int] +
                                    [C.c_void_p] * 3),
     "vmr_network_shared_partners": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p]),
+    "vmr_sample_structural_holes": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 11),
+    "vmr_network_structural_holes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6),
     "vmr_ppc_replicates": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
     "vmr_ppc_observed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

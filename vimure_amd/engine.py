@@ -93,6 +93,12 @@ class PartnersArgumentError(EngineError, ValueError):
     networks of another shape than the handle's, temporaries that do not fit in the free device memory."""
 
 
+class StructuralHolesArgumentError(EngineError, ValueError):
+    """An argument `sample_structural_holes` / `network_structural_holes` refuse (VMR_EINVAL): n_samples or n_trials below 1, a
+    mode other than union or weighted, top_k outside [1, N], networks of another shape than the handle's, temporaries that do not
+    fit in the free device memory."""
+
+
 SCORE_OUTPUTS = ("hist", "conf", "sums", "auc", "auc_pairs")
 INF_SELECT = {"none": 0, "lost": _lib.INF_LOST, "gained": _lib.INF_GAINED, "both": _lib.INF_LOST | _lib.INF_GAINED}
 # columns of the table of `CaviEngine.reporter_influence`, in the order of vmr_reporter_influence's row pointers
@@ -766,6 +772,64 @@ class CaviEngine:
         if pa is not None:
             out["pair_partners"] = pp[0] if one else pp
         return out
+
+    @staticmethod
+    def _holes_values(deg, st, red, es, con, sm, one=False):
+        """The per-network dict of the structural-holes calls: the integers as they are (redundancy as int64), the two measures
+        with NaN where the node is isolated (degree 0), the summary's columns under `_lib.SH_SUMMARY` when it was asked for."""
+        undefined = deg == 0
+        out = {"degree": deg, "strength": st, "redundancy": red.astype(np.int64), "effective_size": np.where(undefined, np.nan, es),
+               "constraint": np.where(undefined, np.nan, con)}
+        if sm is not None:
+            out.update({name: np.ascontiguousarray(sm[..., q]) for q, name in enumerate(_lib.SH_SUMMARY)})
+        return {k: v[0] for k, v in out.items()} if one else out
+
+    def sample_structural_holes(self, seed, n_samples, n_trials=1, mode="union", top_k=10, values=False):
+        """Burt's structural holes of n_samples posterior samples, computed on the device (vmr_sample_structural_holes): sample s
+        is `self.sample(seed + s, n_trials)`, A = (Y > 0) with the diagonal cleared, U = A | A.T.  mode "union": the weights z = U,
+        `networkx.effective_size` / `constraint` of the undirected graph; "weighted": z = A + A.T in {0, 1, 2}, networkx on the
+        DiGraph -- but defined for every node with a tie, an in-tie included.  With d the degree in U and s the row sum of z: the
+        redundancy numerator R (an exact integer), the effective size ES = d - R / (2 s), evaluated as (2 s d - R) / (2 s), and
+        the constraint c = sum_j ((z_ij + sum_q z_iq z_qj / s_q) / s_i)^2; include/vimure_hip.h has the contract.  An isolated
+        node is undefined.  rank[v] = #{defined u : ES_u > ES_v} by effective size and #{defined u : c_u < c_v} by constraint (0:
+        the first broker), #defined for an undefined node.  Returns a dict: `node_sum`, `node_sumsq` float64 [2, L, N] (index 0 the
+        effective size, 1 the constraint; an undefined sample adds 0), `node_rank_sum`, `node_top` (#{s : rank < top_k}) int64
+        [2, L, N], `node_defined` int64 [L, N] (the samples in which the node has a tie) and, float64 [S, L] under the names of
+        `_lib.SH_SUMMARY`, `n_defined`, `effective_size_sum`, `constraint_sum`; with values=True also `degree`, `strength` int32,
+        `redundancy` int64 and `effective_size`, `constraint` float64 [S, L, N], NaN where the node is isolated.  Every number is
+        the same from run to run and for any chunking.  Any N.  A refused argument raises `StructuralHolesArgumentError`."""
+        md = self._name_code(mode, _lib.SH_MODES, "mode", StructuralHolesArgumentError)
+        S, LN = max(int(n_samples), 0), (self.L, self.N)
+        acc = {"node_sum": np.zeros((2,) + LN, np.float64), "node_sumsq": np.zeros((2,) + LN, np.float64),
+               "node_rank_sum": np.zeros((2,) + LN, np.uint64), "node_top": np.zeros((2,) + LN, np.uint32), "node_defined": np.zeros(LN, np.uint32)}
+        sm = np.zeros((S, self.L, len(_lib.SH_SUMMARY)), np.float64)
+        per = [np.zeros((S,) + LN, t) for t in (np.int32, np.int32, np.uint64, np.float64, np.float64)] if values else [None] * 5
+        self._check(self.lib.vmr_sample_structural_holes(self._h, int(seed) & (2 ** 64 - 1), int(n_samples), int(n_trials), md, int(top_k),
+                                                         *[a.ctypes.data for a in acc.values()], sm.ctypes.data,
+                                                         *[None if a is None else a.ctypes.data for a in per]), StructuralHolesArgumentError)
+        out = {k: (a if a.dtype == np.float64 else a.astype(np.int64)) for k, a in acc.items()}
+        out.update({name: np.ascontiguousarray(sm[..., q]) for q, name in enumerate(_lib.SH_SUMMARY)})
+        if values:
+            out.update(self._holes_values(*per, None))
+        return out
+
+    def network_structural_holes(self, Y, mode="union", summary=False):
+        """The measures of `sample_structural_holes` of networks the caller supplies (vmr_network_structural_holes), by the same
+        kernels: Y [L, N, N] or [n, L, N, N] (an entry > 0 is a tie, the diagonal is ignored) -> a dict of `degree`, `strength`
+        int32, `redundancy` int64 and `effective_size`, `constraint` float64 (NaN where the node is isolated), [L, N] or [n, L, N];
+        with summary=True also `n_defined`, `effective_size_sum`, `constraint_sum` float64 [L] or [n, L].  The engine gives the
+        shape and the device only: no state is needed and rho is not touched.  A refused argument raises
+        `StructuralHolesArgumentError`."""
+        md = self._name_code(mode, _lib.SH_MODES, "mode", StructuralHolesArgumentError)
+        ties, one = self._network_ties(Y, StructuralHolesArgumentError)
+        n, LN = ties.shape[0], (self.L, self.N)
+        es, con = np.zeros((n,) + LN, np.float64), np.zeros((n,) + LN, np.float64)
+        deg, st, red = np.zeros((n,) + LN, np.int32), np.zeros((n,) + LN, np.int32), np.zeros((n,) + LN, np.uint64)
+        sm = np.zeros((n, self.L, len(_lib.SH_SUMMARY)), np.float64) if summary else None
+        self._check(self.lib.vmr_network_structural_holes(self._h, ties.ctypes.data, n, md, es.ctypes.data, con.ctypes.data, deg.ctypes.data,
+                                                          st.ctypes.data, red.ctypes.data, sm.ctypes.data if summary else None),
+                    StructuralHolesArgumentError)
+        return self._holes_values(deg, st, red, es, con, sm, one)
 
     def _mixing_args(self, groups, C):
         """(codes int32 [N] or None, C) for the mixing calls: C None is the largest code + 1."""

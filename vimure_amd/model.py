@@ -927,6 +927,30 @@ class VimureModel(TransformerMixin, BaseEstimator):
                               pairs=pairs, pair_present=res.get("pair_present"), pair_supported=res.get("pair_supported"),
                               pair_partners=res.get("pair_partners"), inferred=inferred, seed=seed, n_trials=n_trials)
 
+    def posterior_structural_holes(self, mode="union", n_samples=100, seed=None, n_trials=1, top_k=10, values=False, X=None, R=None):
+        """Whose contacts are disconnected from one another -- who brokers between groups that do not talk -- and how sure is the
+        posterior of it?  Burt's structural holes over the posterior of the network, computed on the GPU
+        (vmr_sample_structural_holes): n_samples draws of Y from q(Y) -- sample s is `sample_inferred_model(N=n_trials, seed=seed
+        + s, device=True)[0]` -- and per draw and layer, on A = (Y > 0) without self-loops, every node's effective size (its
+        non-redundant contacts) and constraint (how far its ties are concentrated in one interconnected group).  mode "union": the
+        symmetrised binary network, `networkx.effective_size` / `networkx.constraint` of the undirected graph; "weighted": Burt's
+        weights A + A.T on the directed network, networkx on the DiGraph -- but defined for every node with a tie.  A node
+        without a tie is undefined in that draw.  Reduced where rho lives to every node's sum and sum of squares of both measures,
+        the sums of its ranks among the defined nodes, how often it is among the top_k (the largest effective sizes, the smallest
+        constraints) and in how many draws it is defined; rho does not cross PCIe (values=True: also every draw's degree,
+        strength, redundancy and the two measures).  Local and cheap: any N, unlike `posterior_betweenness`.
+        Returns a `holes.StructuralHoles`: the views `.effective_size` and `.constraint` (mean and sd over the draws in which the
+        node is defined, expected_rank, top_prob, `top()`, `frame()`), `defined_prob`, `efficiency()`, `brokers()`, the measures
+        of the point estimate `get_inferred_model()` (`inferred`, by the same kernels), `frame()` and `summary()`.  seed None: the
+        fit's.  Engine as in `calculate_mean_poisson`."""
+        from .holes import StructuralHoles
+        if seed is None:
+            seed = self.seed
+        with self._read_engine(X, R) as eng:
+            inferred = eng.network_structural_holes(self.get_inferred_model(), mode=mode)
+            counts = eng.sample_structural_holes(seed, n_samples, n_trials=n_trials, mode=mode, top_k=top_k, values=bool(values))
+        return StructuralHoles(self.N, counts, mode=mode, top_k=top_k, inferred=inferred, seed=seed, n_trials=n_trials)
+
     def posterior_predictive_check(self, n_rep=100, seed=None, params="draw", n_trials=1, by_reporter=False, X=None, R=None):
         """Does data drawn from the fitted model look like the data it was fitted to?  n_rep replicated datasets are drawn on the
         GPU over the support of R and reduced there (vmr_ppc_replicates; no replicate is written) to the integers of
