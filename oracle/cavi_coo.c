@@ -151,6 +151,11 @@ static inline double w1(double z1, double z2) { /* model.py:685-693 */
   if (den == 0.0) den = 1.0;
   return z1 / den;
 }
+static inline double w2(double z1, double z2) { /* model.py:694-696: the same denominator */
+  double den = z1 + z2;
+  if (den == 0.0) den = 1.0;
+  return z2 / den;
+}
 
 /* sum over the mask entries of tie t of v[m] (all-ones mask: the precomputed total) */
 static inline double mask_sum(const coo_state* s, int64_t t, const double* v, double vfull) {
@@ -266,7 +271,7 @@ static void rho_nu(coo_state* s, int do_rho, int do_nu) {
             const int m = s->xm[q];
             for (int k = 0; k < K; ++k) {
               double z1 = c.Gth[m] * c.Gla[k], z2 = gnu * (double)s->xy[q];
-              nu_acc += (double)s->xv[q] * (z2 / (z1 + z2)) * rho[k];
+              nu_acc += (double)s->xv[q] * w2(z1, z2) * rho[k];
             }
           }
     }

@@ -89,6 +89,11 @@ static inline double w1(double z1, double z2) {
   if (den == 0.0) den = 1.0;
   return z1 / den;
 }
+static inline double w2(double z1, double z2) { /* model.py:694-696: the same denominator */
+  double den = z1 + z2;
+  if (den == 0.0) den = 1.0;
+  return z2 / den;
+}
 
 /* model.py:698-727 + :832-859 */
 void ref_update_gamma(ref_state* s) {
@@ -210,7 +215,7 @@ static void rho_nu(ref_state* s, int do_rho, int do_nu) {
             if (x[m] && y[m])
               for (int k = 0; k < K; ++k) {
                 double z1 = Gth[m] * Gla[k], z2 = gnu * (double)y[m];
-                nu_acc += (double)x[m] * (z2 / (z1 + z2)) * rho[k];
+                nu_acc += (double)x[m] * w2(z1, z2) * rho[k];
               }
       }
     free(Gth);

@@ -13,7 +13,8 @@ choice of `create_tail` (`best`, `waves`; vimure_amd/csrc/create.hip) from their
 can say on the host which levels each variant keeps in LDS.
 
 tests/test_plain_sweeps_host.py holds every case to its class, the two oracles to each other and shows three forgetful models
-caught; tests/test_hip_plain_sweeps.py runs cases x schedules on the device."""
+caught; tests/test_hip_plain_sweeps.py runs cases x schedules on the device (`make_engine`: the handle, asserted to be of the
+case's family); tests/geo_zero_util.py reuses the cases, the model and the handle where a geometric expectation is 0."""
 import numpy as np
 
 from tests import call_sequence_util as cs
@@ -431,6 +432,9 @@ class PlainModel(cs.SeqModel):
             Xd[np.transpose(X, (0, 2, 1, 3)) >= drop_from] = 0
             self.Xd = Xd
 
+    def _start_state(self, state_seed):
+        return case_state(self.case, state_seed)
+
     def _on(self, Xalt, whichs, keys):
         """Updates `whichs` computed over another tensor from the present state; only `keys` come back."""
         s = self.b.get()
@@ -468,7 +472,7 @@ class PlainModel(cs.SeqModel):
         name = op["op"]
         if name == "set_state":
             self.last = name
-            self.state = case_state(self.case, op["state_seed"])
+            self.state = self._start_state(op["state_seed"])
             self.b = self.backend(self.X, self.R, self.K, self.mut, self.pri, self.state)
             self.g_stale = self._g()
             self.restored, self.hidden_rho, self.rho_before, self.prte, self.old_rho = False, None, None, False, None
@@ -502,6 +506,33 @@ def run_model(case, schedule, backend="coo", forget=None, drop_from=None):
         ret = model.apply(op)
         out.append((ret, model.observe() if op["compare"] else None))
     return out
+
+
+def make_engine(case, monkeypatch, extra=None, data=None, priors=cs.PRI):
+    """The case's handle under its switches (and `extra`), asserted to be of the case's family; data: (X, R) other than the
+    case's own (tests/geo_zero_util.py takes reports out), priors: what `set_priors` gets."""
+    from vimure_amd import CaviEngine
+    spec = CASES[case]
+    for k in cs.SWITCHES:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in dict(spec["env"], **(extra or {})).items():
+        monkeypatch.setenv(k, v)
+    X, R, K, mut, entry, _ = built(case)
+    if data is not None:
+        X, R = data
+    if entry == "coo":
+        subs, vals = coo_of(X)
+        eng = CaviEngine.from_coo(subs, vals, X.shape, R=None if R is None else np.nonzero(R), K=K, mutuality=mut)
+    else:
+        eng = CaviEngine(X, R, K=K, mutuality=mut)
+    fmt, mask, (passes, levels, far) = eng.data_format()[0], eng.mask_format()[0], eng.sweep_shape()
+    assert fmt == spec["fmt"], (case, fmt)
+    assert spec["mask"] is None or mask == spec["mask"], (case, mask)
+    assert spec["passes"] is None or passes == spec["passes"], (case, passes, levels, far)
+    assert spec.get("levels") is None or levels == spec["levels"], (case, passes, levels, far)
+    assert (far > 0) == bool(spec.get("far")), (case, passes, levels, far)
+    eng.set_priors(*priors)
+    return eng
 
 
 def worst_ratio(a, b):

@@ -25,27 +25,7 @@ def _oracle(case, schedule):
     return _ORACLE[(case, schedule)]
 
 
-def _engine(case, monkeypatch, extra=None):
-    from vimure_amd import CaviEngine
-    spec = u.CASES[case]
-    for k in cs.SWITCHES:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in dict(spec["env"], **(extra or {})).items():
-        monkeypatch.setenv(k, v)
-    X, R, K, mut, entry, _ = u.built(case)
-    if entry == "coo":
-        subs, vals = u.coo_of(X)
-        eng = CaviEngine.from_coo(subs, vals, X.shape, R=None if R is None else np.nonzero(R), K=K, mutuality=mut)
-    else:
-        eng = CaviEngine(X, R, K=K, mutuality=mut)
-    fmt, mask, (passes, levels, far) = eng.data_format()[0], eng.mask_format()[0], eng.sweep_shape()
-    assert fmt == spec["fmt"], (case, fmt)
-    assert spec["mask"] is None or mask == spec["mask"], (case, mask)
-    assert spec["passes"] is None or passes == spec["passes"], (case, passes, levels, far)
-    assert spec.get("levels") is None or levels == spec["levels"], (case, passes, levels, far)
-    assert (far > 0) == bool(spec.get("far")), (case, passes, levels, far)
-    eng.set_priors(*cs.PRI)
-    return eng
+_engine = u.make_engine      # (the handle and the assertions on its family: shared with tests/test_hip_geo_zero.py)
 
 
 def _run(eng, case, schedule):

@@ -19,8 +19,7 @@ int create_tail(vmr_ctx* h, const hipDeviceProp_t& prop);
 // the statistics of the far reports (k_far_hist) after a statistics pass; count: the count-mode pass of create_tail;
 // nu: -1 = no nu sum in this sweep; 0 = the raw sum to elbo_dev[1]; 1 = nu committed too (as launch_hist's)
 int launch_far(vmr_ctx* h, int count, int nu);
-// the count-mode result in H becomes the constants C[l][y][m] (k_take_counts, H left zeroed) and, for handles with h0s, their
-// level-0 totals (k_level0_total)
+// the count-mode result in H becomes the constants C[l][y][m] (k_take_counts, H left zeroed)
 int take_counts(vmr_ctx* h);
 
 #endif

@@ -769,7 +769,7 @@ int create_tail(vmr_ctx* h, const hipDeviceProp_t& prop) {
         (void)hipFree(ss);
         CK(es);
       }
-      const size_t n0 = (size_t)L * NSLOT * K + L;
+      const size_t n0 = (size_t)L * NSLOT * K;
       CK(hipMalloc(&h->h0s, n0 * 8));
       CK(hipMemsetAsync(h->h0s, 0, n0 * 8, h->stream));
     }

@@ -128,8 +128,9 @@ struct MaskStream {
 
 // Weights of the cache refresh (model.py:685-693) without a divide per report:
 //   w1 = z1/(z1 + z2) = 1/(1 + c y),  c[m][k] = G_nu / (G_theta[m] G_lambda[k])  (LDS table, built per launch)
-//   w2 = z2/(z1 + z2) = c y w1.
-// y = 0 gives exactly 1; a z1 that underflows to 0 gives c = inf and w1 = 0 (the reference's den==0 -> 1 rule).
+// y = 0 gives exactly 1; a z1 that underflows to 0 gives c = inf and w1 = 0 at EVERY y: at y = 0 by the reference's den==0 -> 1
+// rule, beyond it as z1/z2 = 0 (G_nu = 0 as well: the rule again) -- selected before the reciprocal, whose Newton step makes
+// 1/inf a NaN.
 template <int K>
 __device__ __forceinline__ void build_ct(double* ct, const double* Gth, const double (&Gla)[K], double gnu, int Mp) {
   for (int m = threadIdx.x; m < Mp; m += TPB) {
@@ -141,14 +142,13 @@ __device__ __forceinline__ void build_ct(double* ct, const double* Gth, const do
   }
 }
 template <int K>
-__device__ __forceinline__ void weights(double (&w)[K], double (&cy)[K], const double* ct, int m, unsigned y) {
+__device__ __forceinline__ void weights(double (&w)[K], const double* ct, int m, unsigned y) {
   const double dy = (double)y;
   const double* p = ct + (size_t)m * K;
   if (K == 2) {   // one reciprocal for both categories: 1/a0 = a1/(a0 a1)
     const double c0 = p[0], c1 = p[1];
     if (c0 < (double)INFINITY && c1 < (double)INFINITY) {
-      cy[0] = c0 * dy; cy[1] = c1 * dy;
-      const double a0 = 1.0 + cy[0], a1 = 1.0 + cy[1];
+      const double a0 = 1.0 + c0 * dy, a1 = 1.0 + c1 * dy;
       const double r = fast_rcp(a0 * a1);
       w[0] = a1 * r; w[1] = a0 * r;   // y = 0: a0 = a1 = 1 and r = 1 exactly
       return;
@@ -157,31 +157,8 @@ __device__ __forceinline__ void weights(double (&w)[K], double (&cy)[K], const d
 #pragma unroll
   for (int k = 0; k < K; ++k) {
     const double c = p[k];
-    cy[k] = c * dy;
-    const double r = fast_rcp(1.0 + cy[k]);
-    w[k] = (y == 0) ? ((c < (double)INFINITY) ? 1.0 : 0.0) : r;
-  }
-}
-
-// the same weights from cb = G_nu / G_theta_m and 1 / G_lambda_k (report lists: one table entry per reporter)
-template <int K>
-__device__ __forceinline__ void weights_cb(double (&w)[K], double cb, const double (&iGla)[K], unsigned y) {
-  const double dy = (double)y;
-  double c[K];
-#pragma unroll
-  for (int k = 0; k < K; ++k) c[k] = cb * iGla[k];
-  if (K == 2) {   // one reciprocal for both categories: 1/a0 = a1/(a0 a1)
-    if (c[0] < (double)INFINITY && c[1] < (double)INFINITY) {
-      const double a0 = 1.0 + c[0] * dy, a1 = 1.0 + c[1] * dy;
-      const double r = fast_rcp(a0 * a1);
-      w[0] = a1 * r; w[1] = a0 * r;   // y = 0: a0 = a1 = 1 and r = 1 exactly
-      return;
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    const double r = fast_rcp(1.0 + c[k] * dy);
-    w[k] = (y == 0) ? ((c[k] < (double)INFINITY) ? 1.0 : 0.0) : r;
+    const double r = fast_rcp(1.0 + c * dy);   // y = 0: 1 exactly; c = inf: a NaN (inf 0, or the Newton step), not taken
+    w[k] = (c < (double)INFINITY) ? r : 0.0;
   }
 }
 
@@ -591,8 +568,8 @@ __global__ __launch_bounds__(TPB, ELBO ? 2 : VMR_LB_RHO) void k_rho(RhoArgs a, G
         [&](int te, int m, unsigned x, SumU<K>& acc) {
           const double dx = (double)x, lt = lth[m];
           if (MUT) {
-            double w[K], cy[K];
-            weights<K>(w, cy, ct, m, (unsigned)xt[cur.mirror(te) * g.stride + m]);
+            double w[K];
+            weights<K>(w, ct, m, (unsigned)xt[cur.mirror(te) * g.stride + m]);
 #pragma unroll
             for (int k = 0; k < K; ++k) acc.U[k] += (lt + lla[k]) * (dx * w[k]);
           } else {

@@ -680,14 +680,12 @@ __device__ __forceinline__ void fin_rho_body(double* par, double* Hg, const doub
       if (fold) {   // (specialised kernels only: K <= KMAX)
         double hk[KMAX];
         h_fold_item(Hl, hcs, (size_t)it, g.K, Cg ? Cg + (size_t)l * items : nullptr, hk);
-        for (int k = 0; k < g.K; ++k) {
-          const double z1 = gth * par[o.G_la + l * g.K + k];
-          if (g.mut && y > 0) a0 += (z2 / (z1 + z2)) * hk[k];
-        }
+        for (int k = 0; k < g.K; ++k)
+          if (g.mut && y > 0) a0 += w2_of(gth * par[o.G_la + l * g.K + k], z2) * hk[k];
       } else if (g.mut && y > 0) {
         for (int k = 0; k < g.K; ++k) {   // (general kernels, deterministic mode: the cells hold integers, sweep_gen.hip)
           const double hv = g.det ? det_back(reinterpret_cast<const unsigned long long*>(Hl)[(size_t)it * g.K + k], g.det_sh) : Hl[(size_t)it * g.K + k];
-          if (hv != 0.0) a0 += (z2 / (gth * par[o.G_la + l * g.K + k] + z2)) * hv;
+          if (hv != 0.0) a0 += w2_of(gth * par[o.G_la + l * g.K + k], z2) * hv;
         }
       }
     }
@@ -921,13 +919,10 @@ __global__ __launch_bounds__(1024) void k_far_hist(const unsigned* __restrict__ 
       if (nu_acc) {
         const unsigned y = ym / (unsigned)Mp, m = ym - y * (unsigned)Mp;
         const double z2 = gnu * (double)y, gt = gth[m];
-        const double d0 = gt * Gla[0] + z2, w0 = d0 == 0.0 ? 0.0 : z2 / d0;
+        const double w0 = w2_of(gt * Gla[0], z2);
         share -= w0 * dx * dfc;
 #pragma unroll
-        for (int k = 1; k < K; ++k) {
-          const double dk = gt * Gla[k] + z2;
-          share += ((dk == 0.0 ? 0.0 : z2 / dk) - w0) * dx * r[u][k];
-        }
+        for (int k = 1; k < K; ++k) share += (w2_of(gt * Gla[k], z2) - w0) * dx * r[u][k];
       }
     }
   }
@@ -962,34 +957,41 @@ __global__ __launch_bounds__(1024) void k_far_hist(const unsigned* __restrict__ 
   }
 }
 // SlArgs::h0s: the level-0 statistics of the rounds that took them as per-tie products, put into copy 0 of H with the marginals the
-// finalize kernels read -- sum_m H[0][m][k] = S_k (the pass' sums), sum_k H[0][m][k] = C[0][m] - deficits (rebuilt from the constant
-// as for every level, h_fold_item): H[0][m][k] += C[0][m] S_k / sum_m C[0][m] for k >= 1.  One workgroup per layer; consumes h0s.
+// finalize kernels read -- sum_m H[0][m][k] = S_k (the pass' sums), sum_k H[0][m][k] = R_m = C[0][m] - deficits (rebuilt from the
+// constant as for every level, h_fold_item; the deficits: slot 0 of the copies the pass added into): H[0][m][k] += R_m S_k / sum_m R_m
+// for k >= 1.  In proportion to R_m, not to the constant: a reporter whose reports all sit on all-zero rows (R_m = 0) gets exactly
+// the zeros it has, so that the finalize may find its new G_theta to be 0 and drop its row (w1_of) without the other rows' column
+// sums being off by what the spread had put there.  One workgroup per layer; consumes h0s.
 __global__ __launch_bounds__(256) void k_level0_spread(double* Hg, const double* __restrict__ Cg, double* h0s, Geo g) {
   __shared__ double Sk[KMAX];
+  __shared__ double red[16];
+  __shared__ double tot;
   const int l = blockIdx.x, K = g.K, Mp = g.Mp;
+  const size_t hcs = (size_t)g.Y * Mp * K;
+  double* H0 = Hg + (size_t)l * NH * hcs;
+  const double* C0 = Cg + (size_t)l * g.Y * Mp;
+  auto marginal = [&](int m) {
+    double d = 0.0;
+#pragma unroll
+    for (int c = 0; c < NH; ++c) d += H0[(size_t)c * hcs + (size_t)m * K];
+    return C0[m] - d;
+  };
+  double s = 0.0;
+  for (int m = threadIdx.x; m < g.M; m += 256) s += marginal(m);
+  s = block_sum_n(s, red);
+  if (threadIdx.x == 0) tot = s;
+  __syncthreads();
   if ((int)threadIdx.x < K) {
-    double s = 0.0;
-    for (int sl = 0; sl < NSLOT; ++sl) { s += h0s[((size_t)l * NSLOT + sl) * K + threadIdx.x]; h0s[((size_t)l * NSLOT + sl) * K + threadIdx.x] = 0.0; }
-    const double tot = h0s[(size_t)g.L * NSLOT * K + l];
-    Sk[threadIdx.x] = tot > 0.0 ? s / tot : 0.0;
+    double sk = 0.0;
+    for (int sl = 0; sl < NSLOT; ++sl) { sk += h0s[((size_t)l * NSLOT + sl) * K + threadIdx.x]; h0s[((size_t)l * NSLOT + sl) * K + threadIdx.x] = 0.0; }
+    Sk[threadIdx.x] = tot > 0.0 ? sk / tot : 0.0;
   }
   __syncthreads();
-  double* H0 = Hg + (size_t)l * NH * g.Y * Mp * K;
-  const double* C0 = Cg + (size_t)l * g.Y * Mp;
-  for (int q = threadIdx.x; q < g.M * (K - 1); q += 256) {
+  for (int q = threadIdx.x; q < g.M * (K - 1); q += 256) {   // (writes slots k >= 1 of copy 0 only: the marginals read slot 0)
     const int m = q / (K - 1), k = 1 + (q - m * (K - 1));
-    const double c = C0[m];
+    const double c = marginal(m);
     if (c != 0.0 && Sk[k] != 0.0) H0[(size_t)m * K + k] += c * Sk[k];
   }
-}
-// sum_m C[l][0][m] into h0s' tail (vmr_create, once)
-__global__ __launch_bounds__(256) void k_level0_total(const double* __restrict__ Cg, double* h0s, Geo g) {
-  __shared__ double red[16];
-  const int l = blockIdx.x;
-  double s = 0.0;
-  for (int m = threadIdx.x; m < g.M; m += 256) s += Cg[(size_t)l * g.Y * g.Mp + m];
-  s = block_sum_n(s, red);
-  if (threadIdx.x == 0) h0s[(size_t)g.L * NSLOT * g.K + l] = s;
 }
 // the count-mode launch of vmr_create is done: its result becomes the constants (create.h)
 int take_counts(vmr_ctx* h) {
@@ -997,10 +999,6 @@ int take_counts(vmr_ctx* h) {
   const size_t nit = (size_t)g.L * g.Y * g.Mp;
   hipLaunchKernelGGL(k_take_counts, dim3((unsigned)std::min<size_t>(1024, (nit + TPB - 1) / TPB)), dim3(TPB), 0, h->stream, h->Hg, h->Cg, g);
   CK(hipGetLastError());
-  if (h->h0s) {
-    hipLaunchKernelGGL(k_level0_total, dim3(g.L), dim3(256), 0, h->stream, h->Cg, h->h0s, g);
-    CK(hipGetLastError());
-  }
   return VMR_OK;
 }
 

@@ -138,7 +138,7 @@ struct vmr_ctx {
   unsigned long long* far_base = nullptr;   // [L + 1] device copy of far_off
   std::vector<unsigned long long> far_off;
   double* h0s = nullptr;       // level-0 rounds without LDS adds (SlArgs::h0s): [L][NSLOT][K] sums over ties of rho_k times the tie's counts in
-                               // such rounds, then [L] sum_m C[l][0][m]
+                               // such rounds
   unsigned long long stat_slots = 0;   // ... the entry slots its statistics pass still reads (the rounds before a step's first all-level-0 one)
   unsigned* x0p = nullptr;     // ... and [L][NS * 64], by position: a tie's summed counts at mirror count 0 (SlArgs::x0p)
   bool elbo_split = false;     // Geo::farl: the fused rho + ELBO variant does not keep g.hc levels in LDS (its logarithm table): an ELBO sweep is
@@ -292,6 +292,12 @@ __device__ __forceinline__ double w1_of(double z1, double z2) {
   double den = z1 + z2;
   den = (den == 0.0) ? 1.0 : den;
   return z1 / den;
+}
+// ... and of the nu part (model.py:694-696): z2 / (z1 + z2) over the same denominator
+__device__ __forceinline__ double w2_of(double z1, double z2) {
+  double den = z1 + z2;
+  den = (den == 0.0) ? 1.0 : den;
+  return z2 / den;
 }
 
 
