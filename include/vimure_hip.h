@@ -536,6 +536,86 @@ int vmr_sample_cores(vmr_handle h, uint64_t seed, int n_samples, int n_trials, i
  * 0..3, k_min out of range, Y or values NULL, a single network whose temporaries do not fit.  Synchronises. */
 int vmr_network_cores(vmr_handle h, const uint8_t* Y, int n, int mode, int k_min, uint16_t* values, uint32_t* summary);
 
+/* Cascades on n_samples posterior samples of Y, computed where rho lives: the independent-cascade model -- if information enters
+ * at a node (or a set of nodes) and every tie passes it on with probability q_l, how many nodes has it reached after T periods?
+ * Sample s is exactly what vmr_sample(h, seed + s, n_trials, ..) writes (seed + s mod 2^64).  Per sample and layer l:
+ * A = (Y > 0) with the DIAGONAL CLEARED and U = A | A^T.
+ * The model, one definition for the four calls.  Cascade k in [0, n_cascades) of network s keeps every tie independently with
+ * probability q_l (the live-edge form of the independent-cascade model): tie (l, i, j) is LIVE iff u < q_l, where u is the
+ * sampler's 53-bit uniform ((w0 >> 5) 2^26 + (w1 >> 6)) 2^-53 from words 0 and 1 of ONE Philox4x32-10 call with
+ *   key     = (cascade_seed + s) mod 2^64, low word first; s is the GLOBAL sample index of the call (never chunk-local), or the
+ *             network index for the calls that take the caller's networks;
+ *   counter = (t low, t high, k, 1), t the tie's index in [L,N,N] order, t = (l N + i) N + j.  Word 3 = 1 keeps the stream apart
+ *             from the sampler's (.., 0) even when cascade_seed == seed.
+ * The spread follows A_uv (u informs v) for VMR_CASC_OUT, A_vu for VMR_CASC_IN and U for VMR_CASC_UNION; under UNION the pair
+ * {i, j} is ONE variable, drawn at the tie index of (l, min(i, j), max(i, j)), so the live graph is symmetric.  The draw belongs
+ * to the tie, not to the direction it is walked in: OUT and IN see the same live ties.
+ * active_0 = the seed set; active_t = active_{t-1} + {v : a live tie leads from a node of active_{t-1} to v}.  The OUTREACH after
+ * T periods is |active_T| - |active_0|.  q_l = 1 makes every tie live (u < 1 always), q_l = 0 none.  Nothing is floating-point
+ * except the one comparison u < q_l, whose operands are exact on both sides: every output is an exact integer (node_sum and
+ * node_sumsq are sums of quotients of two integers).
+ * q: host double [L], each finite and in [0, 1]; T in [1, VMR_CASC_TMAX]; n_cascades in [1, VMR_CASC_KMAX] (a uint32 total cannot
+ * wrap: 65536 * 2047 < 2^32); direction in 0..2; N <= VMR_CASC_NMAX = 2048, the 24 N bytes of LDS of the connectivity closure
+ * (seen, frontier, next frontier: 48 KiB).
+ *
+ * vmr_sample_outreach: every node as a single seed.  Host outputs:
+ *   values                 sum_k outreach of {v} in cascade k                                         uint32 [n_samples][L][N]
+ *   summary                (sum_v values mod 2^32 -- exact while n_cascades N (N - 1) < 2^32 --, max_v values)   uint32 [n_samples][L][2]
+ *   node_sum, node_sumsq   sum_s c and sum_s c^2 (the square rounded, then added), in ascending s, c = values / n_cascades: one
+ *                          FP64 division of two integers                                             double [L][N]
+ *   node_rank_sum          sum_s rank, rank[v] = #{u : c[u] > c[v]}: 0 is the best entry point, tied nodes share the smaller
+ *                          rank (c is monotone in values and distinct values give distinct c: the integers are compared)   uint64 [L][N]
+ *   node_top               #{s : rank < top_k}, top_k in [1, N]                                       uint32 [L][N]
+ * node_sum may not be NULL, every other output may be.
+ * vmr_sample_seed_outreach: n_sets in [1, VMR_CASC_SETS] seed sets at once.  seed_words: HOST uint64 [N], shared by the layers:
+ * bit b of word v is set iff node v is in set b; a bit at or above n_sets is refused.  A set may be empty or hold every node.
+ *   values      sum_k outreach of set b                                                  uint32 [n_samples][L][n_sets], not NULL
+ *   curve       bin t - 1: the nodes newly reached at period t, summed over samples and cascades; the last bin collects every
+ *               period >= VMR_CASC_NPER, so a set's bins sum to its total outreach whatever T is   uint64 [L][n_sets][VMR_CASC_NPER] or NULL
+ *   node_hits   #{(s, k) : v in active_T}, seeds included (n_samples n_cascades < 2^32 is the caller's)   uint32 [L][n_sets][N] or NULL
+ * The kernels.  The samples are packed into the bit rows of vmr_sample_triads.  Per cascade, one pass over the chunk's bit rows
+ * (a thread per word, one Philox call per set bit) writes the LIVE rows of the one row set the closure walks; then a breadth-first
+ * search over 64-bit words in LDS, at most T levels.  Every node as a seed: one workgroup per (block of 64 sources, layer, sample)
+ * walks the live rows of the direction OPPOSITE to the spread, so that popc(seen[v]) - [v in the block] is v's own outreach
+ * towards the block's nodes; one integer add per node at its end.  Seed sets: one workgroup per (layer, sample) starts from
+ * seed_words and walks along the spread; a period's new bits are counted per set with integer LDS atomics.  Only integers are
+ * added, the samples are folded in ascending s: every output is identical from run to run and for any chunking.  Reads the
+ * CURRENT rho once per chunk of samples; any K, any n_trials >= 1, both data formats.  A chunk (vmr_sample_outreach: L N^2 +
+ * 24 L N ceil(N/64) + 16 L N + 8 L bytes per sample beside 28 L N + 8 L bytes per call; vmr_sample_seed_outreach: L N^2 +
+ * 24 L N ceil(N/64) + 4 L n_sets bytes per sample beside 8 N + 8 L + 512 L n_sets + 4 L n_sets N per call; half of the free
+ * device memory at most, 256 samples at most, VMR_NETSTATS_CHUNK at most) is freed before return; a single sample that does not
+ * fit is refused with VMR_EINVAL.
+ * VMR_EINVAL, with a message that names the call and the argument, whatever the state of the handle: n_samples < 1, n_trials < 1,
+ * N above the bound, direction, T, n_cascades, n_sets or top_k out of range, q NULL or an entry non-finite or outside [0, 1], a
+ * seed bit at or above n_sets, seed_words NULL, a required output NULL.  Before vmr_set_state: VMR_ESTATE.  Synchronises. */
+#define VMR_CASC_OUT 0
+#define VMR_CASC_IN 1
+#define VMR_CASC_UNION 2
+#define VMR_CASC_NMAX 2048    /* nodes at most */
+#define VMR_CASC_TMAX 65535   /* periods at most */
+#define VMR_CASC_KMAX 65536   /* cascades per network at most */
+#define VMR_CASC_SETS 64      /* seed sets per call at most */
+#define VMR_CASC_NPER 64      /* period bins of the curve */
+int vmr_sample_outreach(vmr_handle h, uint64_t seed, int n_samples, int n_trials, uint64_t cascade_seed, int n_cascades, const double* q, int T,
+                        int direction, int top_k, double* node_sum, double* node_sumsq, uint64_t* node_rank_sum, uint32_t* node_top,
+                        uint32_t* summary, uint32_t* values);
+int vmr_sample_seed_outreach(vmr_handle h, uint64_t seed, int n_samples, int n_trials, uint64_t cascade_seed, int n_cascades, const double* q,
+                             int T, int direction, const uint64_t* seed_words, int n_sets, uint32_t* values, uint64_t* curve,
+                             uint32_t* node_hits);
+
+/* The same numbers, by the same packing and the same kernels, of n networks the caller supplies -- the inferred network, a ground
+ * truth, a designed graph.  Y: HOST uint8 [n][L][N][N]; an entry > 0 is a tie, the diagonal is ignored.  Network q of a call
+ * equals a sample with the same ties and s = q: its key is (cascade_seed + q) mod 2^64.  values, summary, curve and node_hits as
+ * above with n in place of n_samples; values may not be NULL, the others may.  The handle gives N, L, the device and the stream
+ * and nothing else: the calls work before vmr_set_state and do not touch rho.  The networks are uploaded in chunks (the bytes
+ * above per network, without the 12 L N of c and the ranks).  VMR_EINVAL, with a message that names the call and the argument:
+ * n < 1, N above VMR_CASC_NMAX, direction, T, n_cascades or n_sets out of range, q as above, a seed bit at or above n_sets, Y,
+ * seed_words or values NULL, a single network whose temporaries do not fit.  Synchronise. */
+int vmr_network_outreach(vmr_handle h, const uint8_t* Y, int n, uint64_t cascade_seed, int n_cascades, const double* q, int T, int direction,
+                         uint32_t* values, uint32_t* summary);
+int vmr_network_seed_outreach(vmr_handle h, const uint8_t* Y, int n, uint64_t cascade_seed, int n_cascades, const double* q, int T, int direction,
+                              const uint64_t* seed_words, int n_sets, uint32_t* values, uint64_t* curve, uint32_t* node_hits);
+
 /* The Holland-Leinhardt triad census of n_samples posterior samples of Y, computed where rho lives -- what a user otherwise gets
  * from `networkx.triadic_census` (`sna::triad.census`, `igraph_triad_census`) on every `sample_inferred_model` draw.  Sample s is
  * exactly what vmr_sample(h, seed + s, n_trials, ..) writes (seed + s mod 2^64).  Per sample and layer: A_ij = (Y_ij > 0) with the

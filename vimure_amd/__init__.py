@@ -7,14 +7,20 @@ behind the C-ABI of include/vimure_hip.h.  There is no CPU fallback.
 from . import _lib  # noqa: F401
 from .engine import CaviEngine, EngineError  # noqa: F401
 
-__all__ = ["CaviEngine", "EngineError", "VimureModel"]
+__all__ = ["CaviEngine", "EngineError", "VimureModel", "CascadeStats", "SeedOutreach", "CascadeArgumentError"]
 
 
 def __getattr__(name):
     if name == "VimureModel":
         from .model import VimureModel
         return VimureModel
-    if name in ("model", "synthetic", "tensor"):
+    if name in ("CascadeStats", "SeedOutreach"):
+        from . import cascades
+        return getattr(cascades, name)
+    if name == "CascadeArgumentError":
+        from .engine import CascadeArgumentError
+        return CascadeArgumentError
+    if name in ("model", "cascades", "synthetic", "tensor"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

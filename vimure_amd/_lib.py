@@ -26,6 +26,8 @@ BTW_NMAX = 2048
 BTW_DIRECTIONS = ("directed", "union")     # VMR_BTW_DIRECTED, VMR_BTW_UNION
 CORE_NMAX = 2048
 CORE_MODES = ("union", "total", "in", "out")   # VMR_CORE_UNION, VMR_CORE_TOTAL, VMR_CORE_IN, VMR_CORE_OUT
+CASC_NMAX, CASC_TMAX, CASC_KMAX, CASC_SETS, CASC_NPER = 2048, 65535, 65536, 64, 64
+CASC_DIRECTIONS = ("out", "in", "union")   # VMR_CASC_OUT, VMR_CASC_IN, VMR_CASC_UNION
 CENSUS_NCLASS = 16
 CENSUS_NAMES = ("003", "012", "102", "021D", "021U", "021C", "111D", "111U", "030T", "030C", "201", "120D", "120U", "120C", "210", "300")
 SP_MODES = ("union", "mutual", "path")     # VMR_SP_UNION, VMR_SP_MUTUAL, VMR_SP_PATH
@@ -96,6 +98,13 @@ SIGNATURES = {
     "vmr_network_betweenness": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "vmr_sample_cores": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 8),
     "vmr_network_cores": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vmr_sample_outreach": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int] +
+                            [C.c_void_p] * 6),
+    "vmr_sample_seed_outreach": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                           C.c_int] + [C.c_void_p] * 3),
+    "vmr_network_outreach": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vmr_network_seed_outreach": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int] +
+                                  [C.c_void_p] * 3),
     "vmr_sample_triad_census": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p]),
     "vmr_network_triad_census": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "vmr_sample_shared_partners": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int] +

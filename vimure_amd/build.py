@@ -40,6 +40,7 @@ def units(dev=False):
          ("centrality", os.path.join(CSRC, "centrality.hip"), extra),  # diffusion centrality of posterior samples and of the mean network
          ("betweenness", os.path.join(CSRC, "betweenness.hip"), extra),  # betweenness centrality of posterior samples and of given networks
          ("cores", os.path.join(CSRC, "cores.hip"), extra),            # k-core decomposition of posterior samples and of given networks
+         ("cascades", os.path.join(CSRC, "cascades.hip"), extra),      # independent cascades on posterior samples and on given networks
          ("census", os.path.join(CSRC, "census.hip"), extra),          # the 16-class triad census of posterior samples and of given networks
          ("partners", os.path.join(CSRC, "partners.hip"), extra),      # shared partners of the ties of posterior samples and of given networks
          ("holes", os.path.join(CSRC, "holes.hip"), extra),            # structural holes of posterior samples and of given networks

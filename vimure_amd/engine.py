@@ -82,6 +82,14 @@ class CoresArgumentError(EngineError, ValueError):
     than the peel's working set holds (`_lib.CORE_NMAX`), temporaries that do not fit in the free device memory."""
 
 
+class CascadeArgumentError(EngineError, ValueError):
+    """An argument `sample_outreach` / `sample_seed_outreach` / `network_outreach` / `network_seed_outreach` refuse (VMR_EINVAL): a
+    direction other than out, in or union, T outside [1, `_lib.CASC_TMAX`], n_cascades outside [1, `_lib.CASC_KMAX`], top_k
+    outside [1, N], a q that is not finite or outside [0, 1], seed sets that are more than `_lib.CASC_SETS`, that name a node out
+    of range or that do not match n_sets, n_samples or n_trials below 1, networks of another shape than the handle's, more nodes
+    than the closure's working set holds (`_lib.CASC_NMAX`), temporaries that do not fit in the free device memory."""
+
+
 class CensusArgumentError(EngineError, ValueError):
     """An argument `sample_triad_census` / `network_triad_census` refuse (VMR_EINVAL): n_samples or n_trials below 1, networks of
     another shape than the handle's, temporaries that do not fit in the free device memory."""
@@ -682,6 +690,121 @@ class CaviEngine:
             return out[0] if one else out
         smd = {name: (sm[0, :, q] if one else sm[..., q]).astype(np.int64) for q, name in enumerate(_CORE_STATS)}
         return (out[0] if one else out), smd
+
+    def _cascade_args(self, q, direction):
+        """(q float64 [L], the direction's code) for the cascade calls; what is not a number or a name is refused here."""
+        try:
+            qa = np.ascontiguousarray(np.broadcast_to(np.asarray(q, dtype=np.float64), (self.L,)))
+        except (TypeError, ValueError):
+            raise CascadeArgumentError(f"q must be a scalar or {self.L} numbers, one per layer") from None
+        return qa, self._name_code(direction, _lib.CASC_DIRECTIONS, "direction", CascadeArgumentError)
+
+    def seed_words(self, seed_sets):
+        """(words uint64 [N], n_sets) of seed sets for the `*_seed_outreach` calls: bit b of word v is set iff node v is in set b.
+        seed_sets: a sequence of node-index sequences (a set may be empty, a node may be in several sets), or the words
+        themselves as a uint64 [N] array (then n_sets is 64 unless the call names it)."""
+        if isinstance(seed_sets, np.ndarray) and seed_sets.dtype == np.uint64:
+            if seed_sets.shape != (self.N,):
+                raise CascadeArgumentError(f"seed words of shape {seed_sets.shape}, expected ({self.N},)")
+            return np.ascontiguousarray(seed_sets), _lib.CASC_SETS
+        sets = list(seed_sets)
+        if not 1 <= len(sets) <= _lib.CASC_SETS:
+            raise CascadeArgumentError(f"between 1 and {_lib.CASC_SETS} seed sets expected, got {len(sets)}")
+        words = np.zeros(self.N, np.uint64)
+        for b, nodes in enumerate(sets):
+            idx = np.asarray(list(nodes), dtype=np.int64).reshape(-1)
+            if idx.size and (idx.min() < 0 or idx.max() >= self.N):
+                raise CascadeArgumentError(f"seed set {b} names a node outside [0, {self.N})")
+            words[idx] |= np.uint64(1) << np.uint64(b)
+        return words, len(sets)
+
+    def _seed_outputs(self, n, n_sets, curve, node_hits):
+        """The arrays of a `*_seed_outreach` call for n samples or networks: (values, curve or None, node_hits or None)."""
+        vals = np.zeros((max(int(n), 0), self.L, n_sets), np.uint32)
+        cv = np.zeros((self.L, n_sets, _lib.CASC_NPER), np.uint64) if curve else None
+        nh = np.zeros((self.L, n_sets, self.N), np.uint32) if node_hits else None
+        return vals, cv, nh
+
+    @staticmethod
+    def _seed_result(vals, cv, nh):
+        out = {"values": vals}
+        if cv is not None:
+            out["curve"] = cv.astype(np.int64)
+        if nh is not None:
+            out["node_hits"] = nh.astype(np.int64)
+        return out
+
+    def sample_outreach(self, seed, n_samples, q, T=3, direction="out", n_cascades=16, cascade_seed=0, top_k=10, n_trials=1, values=False):
+        """The outreach of every node as a single seed under the independent-cascade model, over n_samples posterior samples and
+        n_cascades cascades each, computed on the device (vmr_sample_outreach): sample s is `self.sample(seed + s, n_trials)`,
+        A = (Y > 0) with the diagonal cleared; cascade k of sample s keeps tie (l, i, j) iff u < q_l, u the sampler's uniform from
+        Philox4x32-10 with key cascade_seed + s and counter (tie index, k, 1); the spread follows A ("out"), A.T ("in") or
+        A | A.T ("union", one draw per pair); the outreach of v is the number of other nodes reached within T periods.  q: a
+        scalar or [L], each in [0, 1]; T in [1, `_lib.CASC_TMAX`]; n_cascades in [1, `_lib.CASC_KMAX`].  The node score is c =
+        sum_k outreach / n_cascades, rank[v] = #{u : c[u] > c[v]} (0: the best entry point; ties share the smaller rank).  Returns
+        a dict: `node_sum`, `node_sumsq` float64 [L, N] (sum_s c, sum_s c^2), `node_rank_sum`, `node_top` (#{s : rank < top_k})
+        int64 [L, N], `total`, `max` int64 [S, L] (sum_v and max_v of the summed outreach; the sum is taken mod 2^32); with
+        values=True also `values` uint32 [S, L, N], the outreach summed over the cascades.  Every number is an exact integer or a
+        quotient of two, the same from run to run and for any chunking.  N is at most `_lib.CASC_NMAX`.  A refused argument
+        raises `CascadeArgumentError`."""
+        qa, d = self._cascade_args(q, direction)
+        ptrs, result = self._node_outputs(n_samples, ("total", "max"), np.uint32, np.uint32 if values else None)
+        self._check(self.lib.vmr_sample_outreach(self._h, int(seed) & (2 ** 64 - 1), int(n_samples), int(n_trials), int(cascade_seed) & (2 ** 64 - 1),
+                                                 int(n_cascades), qa.ctypes.data, int(T), d, int(top_k), *ptrs), CascadeArgumentError)
+        return result()
+
+    def sample_seed_outreach(self, seed, n_samples, seed_sets, q, T=3, direction="out", n_cascades=16, cascade_seed=0, n_trials=1, curve=True,
+                             node_hits=False, n_sets=None):
+        """The outreach of up to `_lib.CASC_SETS` seed sets under the model of `sample_outreach`, computed on the device
+        (vmr_sample_seed_outreach).  seed_sets: what `seed_words` takes (n_sets: for words given as an array).  Returns a dict:
+        `values` uint32 [S, L, n_sets], the nodes outside the set that are reached within T periods, summed over the cascades;
+        with curve=True `curve` int64 [L, n_sets, `_lib.CASC_NPER`], bin t - 1 the nodes newly reached at period t summed over
+        samples and cascades (the last bin: every period >= 64); with node_hits=True `node_hits` int64 [L, n_sets, N], the
+        (sample, cascade) pairs in which the node is informed after T periods, seeds included.  A refused argument raises
+        `CascadeArgumentError`."""
+        qa, d = self._cascade_args(q, direction)
+        words, ns = self.seed_words(seed_sets)
+        ns = ns if n_sets is None else int(n_sets)
+        vals, cv, nh = self._seed_outputs(n_samples, max(ns, 1), curve, node_hits)
+        self._check(self.lib.vmr_sample_seed_outreach(self._h, int(seed) & (2 ** 64 - 1), int(n_samples), int(n_trials),
+                                                      int(cascade_seed) & (2 ** 64 - 1), int(n_cascades), qa.ctypes.data, int(T), d,
+                                                      words.ctypes.data, ns, vals.ctypes.data, None if cv is None else cv.ctypes.data,
+                                                      None if nh is None else nh.ctypes.data), CascadeArgumentError)
+        return self._seed_result(vals, cv, nh)
+
+    def network_outreach(self, Y, q, T=3, direction="out", n_cascades=16, cascade_seed=0, summary=False):
+        """The summed outreach of `sample_outreach` of networks the caller supplies (vmr_network_outreach), by the same kernels:
+        Y [L, N, N] -> uint32 [L, N], or [n, L, N, N] -> [n, L, N]; an entry > 0 is a tie, the diagonal is ignored; network i
+        draws its cascades with the key cascade_seed + i.  summary=True: returns (values, dict of `total`, `max`, int64 [L] or
+        [n, L]).  The engine gives the shape and the device only: no state is needed and rho is not touched.  A refused
+        argument raises `CascadeArgumentError`."""
+        qa, d = self._cascade_args(q, direction)
+        ties, one = self._network_ties(Y, CascadeArgumentError)
+        out = np.zeros((ties.shape[0], self.L, self.N), np.uint32)
+        sm = np.zeros((ties.shape[0], self.L, 2), np.uint32) if summary else None
+        self._check(self.lib.vmr_network_outreach(self._h, ties.ctypes.data, ties.shape[0], int(cascade_seed) & (2 ** 64 - 1), int(n_cascades),
+                                                  qa.ctypes.data, int(T), d, out.ctypes.data, sm.ctypes.data if summary else None),
+                    CascadeArgumentError)
+        if not summary:
+            return out[0] if one else out
+        smd = {name: (sm[0, :, k] if one else sm[..., k]).astype(np.int64) for k, name in enumerate(("total", "max"))}
+        return (out[0] if one else out), smd
+
+    def network_seed_outreach(self, Y, seed_sets, q, T=3, direction="out", n_cascades=16, cascade_seed=0, curve=True, node_hits=False,
+                              n_sets=None):
+        """`sample_seed_outreach` of networks the caller supplies (vmr_network_seed_outreach): Y [L, N, N] or [n, L, N, N]; the
+        dict's `values` is uint32 [L, n_sets] or [n, L, n_sets], `curve` and `node_hits` sum over the networks.  No state is
+        needed.  A refused argument raises `CascadeArgumentError`."""
+        qa, d = self._cascade_args(q, direction)
+        ties, one = self._network_ties(Y, CascadeArgumentError)
+        words, ns = self.seed_words(seed_sets)
+        ns = ns if n_sets is None else int(n_sets)
+        vals, cv, nh = self._seed_outputs(ties.shape[0], max(ns, 1), curve, node_hits)
+        self._check(self.lib.vmr_network_seed_outreach(self._h, ties.ctypes.data, ties.shape[0], int(cascade_seed) & (2 ** 64 - 1), int(n_cascades),
+                                                       qa.ctypes.data, int(T), d, words.ctypes.data, ns, vals.ctypes.data,
+                                                       None if cv is None else cv.ctypes.data, None if nh is None else nh.ctypes.data),
+                    CascadeArgumentError)
+        return self._seed_result(vals[0] if one else vals, cv, nh)
 
     def sample_triad_census(self, seed, n_samples, n_trials=1):
         """The triad census of n_samples posterior samples, computed on the device (vmr_sample_triad_census): sample s is

@@ -870,6 +870,52 @@ class VimureModel(TransformerMixin, BaseEstimator):
             counts = eng.sample_cores(seed, n_samples, mode=mode, k_min=k, top_k=top_k, n_trials=n_trials, values=bool(values))
         return CoreStats(self.N, counts, mode=mode, k_min=k, top_k=top_k, inferred=inferred, seed=seed, n_trials=n_trials)
 
+    def posterior_cascades(self, q=None, T=3, direction="out", seeds=None, n_cascades=16, n_samples=100, seed=None, cascade_seed=None,
+                           n_trials=1, top_k=10, values=False, X=None, R=None):
+        """If information enters the network at these nodes and every tie passes it on with probability q, how many nodes has it
+        reached after T periods, who is the best single entry point -- and how sure is the posterior of either?  The
+        independent-cascade model over the posterior of the network, computed on the GPU (vmr_sample_outreach,
+        vmr_sample_seed_outreach): n_samples draws of Y from q(Y) -- sample s is `sample_inferred_model(N=n_trials, seed=seed + s,
+        device=True)[0]` -- and on each n_cascades cascades: a cascade keeps every tie of A = (Y > 0) without self-loops with
+        probability q_l (a counter-based draw keyed by cascade_seed + s, the cascade and the tie), the information spreads along
+        the kept ties of A (direction "out"), A.T ("in") or A | A.T ("union", one draw per pair) for T periods, and the outreach
+        is the number of nodes informed beyond the seeds.  Unlike `posterior_centrality` a node reached twice counts once;
+        `posterior_connectivity` is the case q = 1 without a bound on T.  Exact integers: only they cross PCIe.
+        seeds None: every node as a single seed; returns a `cascades.CascadeStats` -- mean, sd, expected_rank, top_prob, the
+        outreach of the point estimate `get_inferred_model()` (`inferred`, by the same kernels), `top()`, `frame()` and
+        `summary()` (values=True: also every draw's outreach summed over its cascades).  seeds {label: nodes}, up to 64 sets, the
+        nodes by name (the `nodeNames` of a model fitted from an edge list) or by index: returns a `cascades.SeedOutreach` --
+        per set the mean and sd over the samples, `quantiles()`, `curve()` (the cumulative share reached by period),
+        `reach_prob()` (how often each node is informed), `frame()` and `summary()`.
+        q: a scalar or one value per layer in [0, 1]; q None takes `posterior_centrality`'s scale, per layer min(1, N / expected
+        edges), the reciprocal of the expected mean degree.  cascade_seed None: the sampling seed.  At most 2048 nodes.  seed
+        None: the fit's.  Engine as in `calculate_mean_poisson`."""
+        from .cascades import CascadeStats, SeedOutreach, resolve_seed_sets
+        from .centrality import default_q
+        if seed is None:
+            seed = self.seed
+        if cascade_seed is None:
+            cascade_seed = seed
+        labels = sets = None
+        if seeds is not None:
+            names = getattr(self, "nodeNames", None)
+            if names is not None:
+                names = names.sort_values("id")["name"].tolist()
+            labels, sets = resolve_seed_sets(seeds, self.N, names)
+        with self._read_engine(X, R) as eng:
+            if q is None:
+                q = default_q(self.N, eng.expected_stats()["edges"])
+            qa = np.broadcast_to(np.asarray(q, dtype=np.float64), (self.L,)).copy()
+            kw = dict(T=T, direction=direction, n_cascades=n_cascades, cascade_seed=cascade_seed)
+            if sets is not None:
+                res = eng.sample_seed_outreach(seed, n_samples, sets, qa, n_trials=n_trials, curve=True, node_hits=True, **kw)
+                return SeedOutreach(self.N, res, labels, sets, qa, T, direction=direction, n_cascades=n_cascades, seed=seed,
+                                    cascade_seed=cascade_seed, n_trials=n_trials)
+            counts = eng.sample_outreach(seed, n_samples, qa, top_k=top_k, n_trials=n_trials, values=bool(values), **kw)
+            inferred = eng.network_outreach(self.get_inferred_model(), qa, **kw)
+        return CascadeStats(self.N, counts, qa, T, direction=direction, n_cascades=n_cascades, top_k=top_k, inferred=inferred, seed=seed,
+                            cascade_seed=cascade_seed, n_trials=n_trials)
+
     def posterior_triad_census(self, n_samples=100, seed=None, n_trials=1, X=None, R=None):
         """Which local structures does the network hold, and how sure is the posterior of them?  The Holland-Leinhardt triad
         census (`networkx.triadic_census`: the unordered triples of nodes in each of the 16 classes 003 012 102 021D 021U 021C
