@@ -767,6 +767,68 @@ int vmr_network_structural_holes(vmr_handle h, const uint8_t* Y /* host [n][L][N
                                  double* constraint /* [n][L][N], required */, int32_t* degree, int32_t* strength,
                                  uint64_t* redundancy, double* summary /* or NULL */);
 
+/* Who holds the network together: the cut points, the bridges and Borgatti's key-player fragmentation of n_samples posterior
+ * samples of Y, computed where rho lives -- what a user otherwise gets from `networkx.articulation_points`, `networkx.bridges` and
+ * one component search per removed node on every `sample_inferred_model` draw.  Sample s is exactly what vmr_sample(h, seed + s,
+ * n_trials, ..) writes (seed + s mod 2^64).  Per sample and layer: A_ij = (Y_ij > 0) with the DIAGONAL CLEARED, and G the
+ * undirected simple graph chosen by mode:
+ *   VMR_CUT_UNION    a tie either way, A | A^T   (networkx on `G.to_undirected()`)
+ *   VMR_CUT_MUTUAL   a tie both ways, A & A^T    (the reciprocated network, the one the model's mutuality speaks about)
+ * For node v let C(v) be its component in G; the BRANCHES of v are the components of C(v) with v removed, of sizes s_1..s_b.
+ *   branches[v]    b; 0 for an isolate; v is a CUT POINT iff b >= 2
+ *   pairs_cut[v]   sum_{i<j} s_i s_j = ((sum_i s_i)^2 - sum_i s_i^2) / 2: the unordered pairs of OTHER nodes that are connected
+ *                  in G and no longer connected once v is taken out; at most C(2047, 2): it fits 32 bits
+ *   bridges[v]     the branches that hold exactly one neighbour of v: the tie {v, u} is a bridge of G (the only connection
+ *                  between two parts; global, not the local bridges of vmr_sample_shared_partners) iff u is the only neighbour
+ *                  of v in its branch.  sum_v bridges[v] = 2 x the number of bridges
+ *   rank[v]        #{u : pairs_cut[u] > pairs_cut[v]}: 0 is the node whose removal cuts most, and ALL NON-CUT NODES SHARE A
+ *                  RANK (their pairs_cut is 0) -- as a shell does in vmr_sample_cores, so node_top can count more than top_k
+ *                  nodes per sample (all N of them on a graph without cut points)
+ * Exact integers: no floating point enters the search.  top_k in [1, N].  Host outputs:
+ *   node_sum, node_sumsq   sum_s pairs_cut and sum_s pairs_cut^2, in ascending s (integers below 2^53: exact)   double [L][N]
+ *   node_rank_sum          sum_s rank                                                                uint64 [L][N]
+ *   node_top               #{s : rank < top_k}                                                       uint32 [L][N]
+ *   node_cut               #{s : branches >= 2}                                                      uint32 [L][N]
+ *   node_branch_sum        sum_s branches                                                            uint64 [L][N]
+ *   node_bridge_sum        sum_s bridges                                                             uint64 [L][N]
+ *   summary                (cut points, bridges, max_v pairs_cut, the connected unordered pairs of G =
+ *                          sum over the components of C(|C|, 2) = sum_v sum_i s_i(v) / 2)            uint32 [n_samples][L][4]
+ *   pairs_cut              of every sample                                                           uint32 [n_samples][L][N]
+ *   branches, bridges      of every sample                                                           uint16 [n_samples][L][N]
+ * node_sum may not be NULL, every other output may be.  pairs_cut over the summary's connected pairs is the share of the
+ * sample's connected pairs that the removal of v disconnects.
+ * The samples are packed into the bit rows of vmr_sample_triads and G is formed from them once per chunk.  One workgroup per
+ * (block of 64 nodes, layer, sample) runs the 64 removal experiments of its block at once with the 64-source breadth-first search
+ * of vmr_sample_connectivity: node u carries a 64-bit word in LDS whose bit q belongs to the experiment "node 64 b + q has been
+ * removed"; the removed node starts as seen in its own experiment and is never expanded.  The branches are found in rounds: every
+ * experiment with an unvisited neighbour of its removed node seeds the lowest-numbered one (an integer LDS atomic minimum), the
+ * search runs to closure for all 64 experiments, and the nodes the round reached are counted per experiment.  seen, the frontier
+ * and the next frontier take 24 N bytes of LDS, which bounds N: N <= VMR_CUT_NMAX = 2048; a larger N is refused with VMR_EINVAL
+ * and a message that names the bound.  Integer adds, minima and ORs only, and the samples are folded in ascending s: every
+ * output is bit-identical from run to run and for any chunking.  Reads the CURRENT rho (after vmr_restore: the snapshot's) once
+ * per chunk of samples; any K, any n_trials >= 1, both data formats.  A chunk (L N^2 + 24 L N ceil(N/64) + 22 L N + 16 L bytes
+ * per sample, whichever outputs are asked for, beside 48 L N bytes of per-node accumulators per call; half of the free device
+ * memory at most, 256 samples at most, VMR_NETSTATS_CHUNK at most) is freed before return; a single sample that does not fit is
+ * refused with VMR_EINVAL.
+ * VMR_EINVAL, with a message that names the call and the argument, whatever the state of the handle: n_samples < 1, n_trials < 1,
+ * N above the bound, mode outside 0..1, top_k out of range, node_sum NULL.  Before vmr_set_state: VMR_ESTATE.  Synchronises. */
+#define VMR_CUT_UNION 0
+#define VMR_CUT_MUTUAL 1
+#define VMR_CUT_NMAX 2048   /* nodes at most */
+int vmr_sample_cutpoints(vmr_handle h, uint64_t seed, int n_samples, int n_trials, int mode, int top_k, double* node_sum,
+                         double* node_sumsq, uint64_t* node_rank_sum, uint32_t* node_top, uint32_t* node_cut, uint64_t* node_branch_sum,
+                         uint64_t* node_bridge_sum, uint32_t* summary, uint32_t* pairs_cut, uint16_t* branches, uint16_t* bridges);
+
+/* The same numbers, by the same packing and the same kernels, of n networks the caller supplies -- the inferred network, a ground
+ * truth, a designed graph.  Y: HOST uint8 [n][L][N][N]; an entry > 0 is a tie, the diagonal is ignored.  pairs_cut: host uint32
+ * [n][L][N], required; branches, bridges: host uint16 [n][L][N], summary: host uint32 [n][L][4] as above, or NULL.  The handle
+ * gives N, L, the device and the stream and nothing else: the call works before vmr_set_state and does not touch rho.  Network q
+ * of a call equals what vmr_sample_cutpoints returns for a sample with the same ties.  The networks are uploaded in chunks (L N^2
+ * + 24 L N ceil(N/64) + 10 L N + 16 L bytes per network).  VMR_EINVAL, with a message that names the call and the argument: n <
+ * 1, N above VMR_CUT_NMAX, mode outside 0..1, Y or pairs_cut NULL, a single network whose temporaries do not fit.  Synchronises. */
+int vmr_network_cutpoints(vmr_handle h, const uint8_t* Y, int n, int mode, uint32_t* pairs_cut, uint16_t* branches, uint16_t* bridges,
+                          uint32_t* summary);
+
 /* Posterior predictive checks: n_rep replicated datasets drawn from the fitted model over the support of the handle's own R and
  * reduced where they are drawn -- no replicate is ever written -- and the same reduction of the observed data.
  * Replicate r: Y_r is exactly what vmr_sample(h, seed_y + r, n_trials, ..) writes (mod 2^64; the CURRENT rho, after vmr_restore

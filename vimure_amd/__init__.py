@@ -7,7 +7,8 @@ behind the C-ABI of include/vimure_hip.h.  There is no CPU fallback.
 from . import _lib  # noqa: F401
 from .engine import CaviEngine, EngineError  # noqa: F401
 
-__all__ = ["CaviEngine", "EngineError", "VimureModel", "CascadeStats", "SeedOutreach", "CascadeArgumentError"]
+__all__ = ["CaviEngine", "EngineError", "VimureModel", "CascadeStats", "SeedOutreach", "CascadeArgumentError",
+           "CutpointStats", "CutpointArgumentError"]
 
 
 def __getattr__(name):
@@ -20,7 +21,13 @@ def __getattr__(name):
     if name == "CascadeArgumentError":
         from .engine import CascadeArgumentError
         return CascadeArgumentError
-    if name in ("model", "cascades", "synthetic", "tensor"):
+    if name == "CutpointStats":
+        from .cutpoints import CutpointStats
+        return CutpointStats
+    if name == "CutpointArgumentError":
+        from .engine import CutpointArgumentError
+        return CutpointArgumentError
+    if name in ("model", "cascades", "cutpoints", "synthetic", "tensor"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

@@ -35,6 +35,10 @@ SP_MAX_BINS, SP_NTOTAL = 1024, 4
 SP_TOTALS = ("ties", "supported", "partners", "max_partners")
 SH_MODES = ("union", "weighted")           # VMR_SH_UNION, VMR_SH_WEIGHTED
 SH_SUMMARY = ("n_defined", "effective_size_sum", "constraint_sum")   # the columns of the structural-holes calls' summary
+CUT_NMAX = 2048
+CUT_UNION, CUT_MUTUAL = 0, 1
+CUT_MODES = ("union", "mutual")            # VMR_CUT_UNION, VMR_CUT_MUTUAL
+CUT_SUMMARY = ("n_cut", "n_bridges", "max_pairs_cut", "connected_pairs")   # the columns of the cut-point calls' summary
 EDGE_REPORTED, EDGE_INFERRED = 1, 2
 SCORE_RHO1, SCORE_PROB = 0, 1
 SCORE_NCONF, SCORE_NSUM, SCORE_MAX_THR = 5, 4, 4096
@@ -112,6 +116,8 @@ SIGNATURES = {
     "vmr_network_shared_partners": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p]),
     "vmr_sample_structural_holes": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 11),
     "vmr_network_structural_holes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6),
+    "vmr_sample_cutpoints": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 11),
+    "vmr_network_cutpoints": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4),
     "vmr_ppc_replicates": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
     "vmr_ppc_observed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -44,6 +44,7 @@ def units(dev=False):
          ("census", os.path.join(CSRC, "census.hip"), extra),          # the 16-class triad census of posterior samples and of given networks
          ("partners", os.path.join(CSRC, "partners.hip"), extra),      # shared partners of the ties of posterior samples and of given networks
          ("holes", os.path.join(CSRC, "holes.hip"), extra),            # structural holes of posterior samples and of given networks
+         ("cutpoints", os.path.join(CSRC, "cutpoints.hip"), extra),    # cut points, bridges and fragmentation of posterior samples and of given networks
          ("ppc_rep", os.path.join(CSRC, "ppc_rep.hip"), extra),        # posterior predictive replicates, reduced
          ("edge_table", os.path.join(CSRC, "edge_table.hip"), extra),  # the inferred network as an edge table
          ("score_truth", os.path.join(CSRC, "score_truth.hip"), extra),  # the posterior scored against a ground truth

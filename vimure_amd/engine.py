@@ -82,6 +82,12 @@ class CoresArgumentError(EngineError, ValueError):
     than the peel's working set holds (`_lib.CORE_NMAX`), temporaries that do not fit in the free device memory."""
 
 
+class CutpointArgumentError(EngineError, ValueError):
+    """An argument `sample_cutpoints` / `network_cutpoints` refuse (VMR_EINVAL): a mode other than union or mutual, top_k outside
+    [1, N], n_samples or n_trials below 1, networks of another shape than the handle's, more nodes than the removal experiments'
+    working set holds (`_lib.CUT_NMAX`), temporaries that do not fit in the free device memory."""
+
+
 class CascadeArgumentError(EngineError, ValueError):
     """An argument `sample_outreach` / `sample_seed_outreach` / `network_outreach` / `network_seed_outreach` refuse (VMR_EINVAL): a
     direction other than out, in or union, T outside [1, `_lib.CASC_TMAX`], n_cascades outside [1, `_lib.CASC_KMAX`], top_k
@@ -690,6 +696,55 @@ class CaviEngine:
             return out[0] if one else out
         smd = {name: (sm[0, :, q] if one else sm[..., q]).astype(np.int64) for q, name in enumerate(_CORE_STATS)}
         return (out[0] if one else out), smd
+
+    def sample_cutpoints(self, seed, n_samples, mode="union", top_k=10, n_trials=1, values=False):
+        """Cut points, bridges and fragmentation of n_samples posterior samples, computed on the device (vmr_sample_cutpoints):
+        sample s is `self.sample(seed + s, n_trials)`, A = (Y > 0) with the diagonal cleared, G the undirected graph A | A.T
+        ("union": networkx on `G.to_undirected()`) or A & A.T ("mutual": the reciprocated ties).  The branches of node v are the
+        components of v's component once v is taken out, of sizes s_1..s_b: branches[v] = b (0 for an isolate; v is a cut point
+        iff b >= 2), pairs_cut[v] = sum_{i<j} s_i s_j the pairs of other nodes that lose every path with v, bridges[v] the branches
+        that hold exactly one neighbour of v (the tie to it is a bridge of G).  rank[v] = #{u : pairs_cut[u] > pairs_cut[v]}: all
+        non-cut nodes share a rank, so `node_top` can count more than top_k nodes per sample.  Returns a dict: `node_sum`,
+        `node_sumsq` float64 [L, N] (sum_s pairs_cut, sum_s pairs_cut^2, exact integers), `node_rank_sum`, `node_top` (#{s : rank <
+        top_k}), `node_cut` (#{s : branches >= 2}), `node_branch_sum`, `node_bridge_sum` int64 [L, N], and `n_cut`, `n_bridges`,
+        `max_pairs_cut`, `connected_pairs` int64 [S, L] (the cut points, the bridges, max_v pairs_cut and the connected unordered
+        pairs of G); with values=True also `pairs_cut` uint32, `branches`, `bridges` uint16 [S, L, N].  Every number is the same
+        from run to run and for any chunking.  N is at most `_lib.CUT_NMAX`.  A refused argument raises `CutpointArgumentError`."""
+        md = self._name_code(mode, _lib.CUT_MODES, "mode", CutpointArgumentError)
+        S, LN = max(int(n_samples), 0), (self.L, self.N)
+        sums = {"node_sum": np.zeros(LN, np.float64), "node_sumsq": np.zeros(LN, np.float64)}
+        ints = {"node_rank_sum": np.zeros(LN, np.uint64), "node_top": np.zeros(LN, np.uint32), "node_cut": np.zeros(LN, np.uint32),
+                "node_branch_sum": np.zeros(LN, np.uint64), "node_bridge_sum": np.zeros(LN, np.uint64)}
+        sm = np.zeros((S, self.L, 4), np.uint32)
+        vals = {"pairs_cut": np.zeros((S,) + LN, np.uint32), "branches": np.zeros((S,) + LN, np.uint16),
+                "bridges": np.zeros((S,) + LN, np.uint16)} if values else {}
+        ptrs = [a.ctypes.data for a in sums.values()] + [a.ctypes.data for a in ints.values()] + [sm.ctypes.data]
+        ptrs += [a.ctypes.data for a in vals.values()] if values else [None] * 3
+        self._check(self.lib.vmr_sample_cutpoints(self._h, int(seed) & (2 ** 64 - 1), int(n_samples), int(n_trials), md, int(top_k), *ptrs),
+                    CutpointArgumentError)
+        out = dict(sums)
+        out.update({k: a.astype(np.int64) for k, a in ints.items()})
+        out.update({name: sm[..., q].astype(np.int64) for q, name in enumerate(_lib.CUT_SUMMARY)})
+        out.update(vals)
+        return out
+
+    def network_cutpoints(self, Y, mode="union", summary=False):
+        """The numbers of `sample_cutpoints` of networks the caller supplies (vmr_network_cutpoints), by the same kernels: Y [L, N,
+        N] -> a dict of `pairs_cut` uint32, `branches`, `bridges` uint16 [L, N], or [n, L, N, N] -> [n, L, N]; an entry > 0 is a
+        tie, the diagonal is ignored.  summary=True: the dict also holds `n_cut`, `n_bridges`, `max_pairs_cut`, `connected_pairs`,
+        int64 [L] or [n, L].  The engine gives the shape and the device only: no state is needed and rho is not touched.  A
+        refused argument raises `CutpointArgumentError`."""
+        md = self._name_code(mode, _lib.CUT_MODES, "mode", CutpointArgumentError)
+        ties, one = self._network_ties(Y, CutpointArgumentError)
+        n = ties.shape[0]
+        out = {"pairs_cut": np.zeros((n, self.L, self.N), np.uint32), "branches": np.zeros((n, self.L, self.N), np.uint16),
+               "bridges": np.zeros((n, self.L, self.N), np.uint16)}
+        sm = np.zeros((n, self.L, 4), np.uint32) if summary else None
+        self._check(self.lib.vmr_network_cutpoints(self._h, ties.ctypes.data, n, md, out["pairs_cut"].ctypes.data, out["branches"].ctypes.data,
+                                                   out["bridges"].ctypes.data, sm.ctypes.data if summary else None), CutpointArgumentError)
+        if summary:
+            out.update({name: sm[..., q].astype(np.int64) for q, name in enumerate(_lib.CUT_SUMMARY)})
+        return {k: a[0] for k, a in out.items()} if one else out
 
     def _cascade_args(self, q, direction):
         """(q float64 [L], the direction's code) for the cascade calls; what is not a number or a name is refused here."""

@@ -870,6 +870,30 @@ class VimureModel(TransformerMixin, BaseEstimator):
             counts = eng.sample_cores(seed, n_samples, mode=mode, k_min=k, top_k=top_k, n_trials=n_trials, values=bool(values))
         return CoreStats(self.N, counts, mode=mode, k_min=k, top_k=top_k, inferred=inferred, seed=seed, n_trials=n_trials)
 
+    def posterior_cutpoints(self, mode="union", n_samples=100, seed=None, top_k=10, n_trials=1, values=False, X=None, R=None):
+        """Who holds the network together -- whose departure would split a component, into how many pieces, how many pairs of
+        people would lose every path between them, which single ties are the only connection between two parts -- and how sure
+        is the posterior of it?  Cut points (`networkx.articulation_points`), bridges (`networkx.bridges`) and Borgatti's
+        key-player fragmentation over the posterior of the network, computed on the GPU (vmr_sample_cutpoints): n_samples draws of
+        Y from q(Y) -- sample s is `sample_inferred_model(N=n_trials, seed=seed + s, device=True)[0]` -- and per draw and layer,
+        on the undirected graph A | A.T (mode "union") or A & A.T ("mutual", the reciprocated ties) of A = (Y > 0) without
+        self-loops, for every node the branches its component falls into without it, the pairs of other nodes that removal
+        disconnects (pairs_cut) and its bridges.  Reduced where rho lives to every node's sum and sum of squares of pairs_cut, the
+        sum of its ranks, how often it is among the top_k and a cut point, the sums of its branches and bridges, and each draw's
+        cut points, bridges, largest pairs_cut and connected pairs; only those cross PCIe (values=True: also every draw's
+        pairs_cut, branches and bridges).  All non-cut nodes share a rank, so `top_prob` can count more than top_k nodes.
+        Returns a `cutpoints.CutpointStats`: cut_prob, mean, sd, expected_rank, top_prob, mean_branches, mean_bridges, the same
+        numbers of the point estimate `get_inferred_model()` (`inferred`, by the same kernels), `fragmentation()`, `quantiles()`,
+        `top()`, `key_players()`, `frame()` and `summary()`.  There is no closed form under the mean field, hence no
+        expectations.  At most 2048 nodes.  seed None: the fit's.  Engine as in `calculate_mean_poisson`."""
+        from .cutpoints import CutpointStats
+        if seed is None:
+            seed = self.seed
+        with self._read_engine(X, R) as eng:
+            inferred = eng.network_cutpoints(self.get_inferred_model(), mode=mode)
+            counts = eng.sample_cutpoints(seed, n_samples, mode=mode, top_k=top_k, n_trials=n_trials, values=bool(values))
+        return CutpointStats(self.N, counts, mode=mode, top_k=top_k, inferred=inferred, seed=seed, n_trials=n_trials)
+
     def posterior_cascades(self, q=None, T=3, direction="out", seeds=None, n_cascades=16, n_samples=100, seed=None, cascade_seed=None,
                            n_trials=1, top_k=10, values=False, X=None, R=None):
         """If information enters the network at these nodes and every tie passes it on with probability q, how many nodes has it
